@@ -10,18 +10,23 @@ batch of synthetic 32x512 LR strips per GPU — by default the configuration BAS
 per GPU, 16 glyphs per image, inputs resident in HBM, random-init seeded checkpoints of the reference's exact architecture.
 The headline is measured in the fastest precision mode that MEETS the north-star parity bar (<= 1e-3 max-abs vs the reference's
 CPU forward, character indices bit-exact): "fp16x2" — fp16+8 storage, every multiply evaluated as hi*hi on the fp16 MFMA plus
-one block-scaled fp8 MFMA for both correction products, fp32 accumulation.  The split-half mode fp16x3 (three f16 products, fp32-class
-accuracy), the plain fp16 storage mode (2x faster, ~1e-2 deviation) and the exact fp32 mode are timed in the same run and reported under
-"secondary", all with their measured deviation under "parity" — which also holds the oracle check of the TIMED batch itself
-(one strip per generator chunk), with and without the generator's structure image.
+one block-scaled fp8 MFMA for both correction products, fp32 accumulation.
 (`--batch 64` is BASELINE configs[1]; `--gpus 8 --batch 128` is configs[2].)  N>1: weak scaling, every rank processes its
 own batch and the post-processed SR outputs (uint8 BGR, test_sr.py:198-200) are all-gathered over RCCL — the one collective
 of the path.  Rank 0 prints ONE JSON line.
 
-The default run (N = 1) also carries, under "secondary.configs", a short driver-timed measurement of BASELINE configs[1] (batch 64),
-configs[3] (TSPGAN alone) and configs[4] (mixed widths), each with the roofline fraction of its dominant kernel and a parity sample; under
-"parity" the oracle comparison on TWO weight regimes (marconet_amd/synthetic.py: "tame" and "trained"-like) and — when MARCONET_CKPT_DIR
-holds the reference's real checkpoints (marconet_amd/checkpoints.py) — on those instead of the synthetic ones.
+A plain run does only what the headline needs: set-up, --warmup steps, --steps timed steps, the outputs of the last timed step when
+--dump-outputs DIR is given, and the line (`value`, `ms_per_step` and the configuration; `roofline` and `secondary` are null).
+--dump-outputs DIR: rank 0 writes the arrays its last timed step returned as DIR/<name>.npy in float32; above 64 MB in all, a fixed seeded
+sample of whole images (their indices in DIR/<name>_index.npy).  Inputs and weights are seeded, so two builds can be compared file for file.
+
+--full adds everything else, after the timed steps: the roofline of the dominant kernel (a separate instrumented pass), and at N = 1 the
+CPU baseline and "parity" (the oracle comparison, also of the TIMED batch itself: one strip per generator chunk, with and without the
+generator's structure image, on TWO weight regimes — marconet_amd/synthetic.py: "tame" and "trained"-like — or on the reference's real
+checkpoints when MARCONET_CKPT_DIR holds them, marconet_amd/checkpoints.py).  For the default config it also times, under "secondary", the
+split-half mode fp16x3 (three f16 products, fp32-class accuracy), the plain fp16 storage mode (2x faster, ~1e-2 deviation), the exact
+fp32 mode, and BASELINE configs[1] (batch 64), configs[3] (TSPGAN alone) and configs[4] (mixed widths) under "secondary.configs", each with
+the roofline fraction of its dominant kernel and a parity sample.
 
 Other BASELINE configs as stand-alone lines, each with its own roofline of its dominant kernel:
     --config gan     configs[3]: the test_w.py StyleGAN-prior path alone — 256 x 16 = 4096 glyphs of 128x128 through TSPGAN
@@ -113,7 +118,43 @@ def parse():
                                                        "alone) through the same launch / shard / overlapped all-gather / barrier + max-over-ranks timing / JSON code; "
                                                        "the line says \"dry\": true and carries no throughput claim (tests/test_bench_launch.py)")
     ap.add_argument("--gather-format", default="u8", choices=["u8", "f32"], help="N>1: what is all-gathered — the post-processed uint8 BGR image (0.75 MiB/img) or the fp32 NCHW tensor (3 MiB/img)")
+    ap.add_argument("--full", action="store_true", help="after the headline: roofline pass, secondary measurements, CPU baseline and parity "
+                                                        "(--cpu-images, --no-secondary, --secondary-steps and --no-regimes shape these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step (rank 0) as DIR/<name>.npy, float32, "
+                                                                        "at most 64 MB in all (a fixed seeded sample of whole images above that)")
     return ap.parse_args()
+
+
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs: every file together, .npy headers included
+DUMP_SEED = 20240601
+
+
+def dump_outputs(d, name, images):
+    """--dump-outputs: ``images`` — one tensor indexed by image (or glyph) along dim 0, or a list of per-image tensors of different shapes —
+    → float32 <d>/<name>.npy (a list: <d>/<name>_<index>.npy per image) and the indices written, float64, in <d>/<name>_index.npy.  When all
+    of them exceed DUMP_BYTES, whole images are taken in one fixed seeded order until the budget is reached, so every run writes the same ones."""
+    os.makedirs(d, exist_ok=True)
+    n = len(images)
+    nbytes = [images[i].numel() * 4 for i in range(n)]
+    keep = list(range(n))
+    budget = DUMP_BYTES - (1 << 16)           # headers and the index file
+    if sum(nbytes) > budget:
+        keep, total = [], 0
+        for i in torch.randperm(n, generator=torch.Generator().manual_seed(DUMP_SEED)).tolist():
+            if total + nbytes[i] > budget:
+                break
+            keep.append(i)
+            total += nbytes[i]
+        keep.sort()
+    import numpy as np
+    if isinstance(images, torch.Tensor):
+        idx = torch.tensor(keep, dtype=torch.long, device=images.device)
+        np.save(os.path.join(d, name + ".npy"), images.index_select(0, idx).float().cpu().numpy())
+    else:
+        for i in keep:
+            np.save(os.path.join(d, "%s_%04d.npy" % (name, i)), images[i].float().cpu().numpy())
+    np.save(os.path.join(d, name + "_index.npy"), np.asarray(keep, dtype=np.float64))
+    return keep
 
 
 def host_threads(cap):
@@ -396,14 +437,14 @@ def main():
         # margin of the returned image — TextGenerator.module_call_fp16x3)
 
         def step_():
-            y_ = None
+            ys_ = []                                                  # the structure images of every chunk (what --dump-outputs writes)
             gan.TextGenerator.module_call_fp16x3 = False
             try:
                 for s_ in range(0, N, pipe.glyph_chunk):              # bounded working set (8.6 GB of 128-px maps per 1024 glyphs)
-                    y_ = gan(styles=styles_[s_:s_ + pipe.glyph_chunk], labels=glabels_[s_:s_ + pipe.glyph_chunk], noise=None)[0]
+                    ys_.append(gan(styles=styles_[s_:s_ + pipe.glyph_chunk], labels=glabels_[s_:s_ + pipe.glyph_chunk], noise=None)[0])
             finally:
                 gan.TextGenerator.module_call_fp16x3 = True
-            return y_
+            return ys_
         return styles_, glabels_, step_
 
     def mixed_workload(Bq):
@@ -453,8 +494,7 @@ def main():
         workload = "configs[4]: %d strips/GPU, widths {128..512 step 64}, w/32 glyphs, 64-px buckets, %s" % (B, a.precision)
 
         def step():
-            outs = pipe.forward_mixed_widths(lq, widths, labels, locs)
-            return outs[-1]
+            return pipe.forward_mixed_widths(lq, widths, labels, locs)
 
     for _ in range(a.warmup):
         step()
@@ -462,18 +502,25 @@ def main():
     dt, per_rank_dt, y = timed(step, fence, a.steps, world, dev)
     # HBM in use by the timed workload (inputs, weights, every live activation; torch's caching allocator is the only allocator on the path)
     hbm_peak_gb = round(torch.cuda.max_memory_allocated(dev) / 1e9, 1)
-    # roofline of the dominant kernel: a SEPARATE pass with HIP events around every conv launch (same stream)
-    prof_steps = min(a.steps, 2)
-    roofline, peak = instrumented(step, prof_steps, alg_gf_step, B if a.config == "sr" else None, a.precision)
-    roofline["measured_in"] = "a separate instrumented pass of %d step(s) after the timed region (HIP events around every conv launch)" % prof_steps
-    if y.dtype.is_floating_point:
-        assert torch.isfinite(y).all()
-    # the timed batch's OWN output, sampled: one strip per generator chunk (4096 glyphs / glyph_chunk 1024 = 4 chunks at the default
-    # configuration) — compared with the oracle below (the batch-256 step is the only place where the glyph loop of
-    # MarconetPipeline._core runs more than once)
-    samp_idx = sorted(set([0, B // 3, (2 * B) // 3, B - 1])) if a.config == "sr" else []
-    y_timed = y[samp_idx].float().cpu() if (a.config == "sr" and y.dtype.is_floating_point and y.dim() == 4 and y.shape[1] == 3) else None
-    y_timed_noimg = None
+    if a.dump_outputs and rank == 0:
+        # sr: [B,3,128,2048] fp32 (or [B,128,2048,3] uint8 BGR when that is what is gathered); gan: [B*n,3,128,128]; mixed: [3,128,4W'] per strip
+        dump_outputs(a.dump_outputs, {"sr": "sr", "gan": "tspgan_image", "mixed": "sr_strip"}[a.config], torch.cat(y) if a.config == "gan" else y)
+    roofline = y_timed = y_timed_noimg = None
+    samp_idx = []
+    if a.full:
+        # roofline of the dominant kernel: a SEPARATE pass with HIP events around every conv launch (same stream)
+        prof_steps = min(a.steps, 2)
+        roofline, peak = instrumented(step, prof_steps, alg_gf_step, B if a.config == "sr" else None, a.precision)
+        roofline["measured_in"] = "a separate instrumented pass of %d step(s) after the timed region (HIP events around every conv launch)" % prof_steps
+        for t_ in (y if isinstance(y, list) else [y]):
+            if t_.dtype.is_floating_point:
+                assert torch.isfinite(t_).all()
+        # the timed batch's OWN output, sampled: one strip per generator chunk (4096 glyphs / glyph_chunk 1024 = 4 chunks at the default
+        # configuration) — compared with the oracle below (the batch-256 step is the only place where the glyph loop of
+        # MarconetPipeline._core runs more than once)
+        if a.config == "sr":
+            samp_idx = sorted(set([0, B // 3, (2 * B) // 3, B - 1]))
+            y_timed = y[samp_idx].float().cpu() if (y.dtype.is_floating_point and y.dim() == 4 and y.shape[1] == 3) else None
     del y
     total_images, per_rank_images = images_per_step, [images_per_step]
     if world > 1:
@@ -484,7 +531,7 @@ def main():
         total_images = sum(per_rank_images)
 
     # ---- secondary figures (reported separately, never the headline)
-    if a.config == "sr" and not a.no_secondary:
+    if a.full and a.config == "sr" and not a.no_secondary:
         secondary = {"steps_each": sec_steps}
         # the same step without the generator's 128-px structure image, which only feeds test_sr.py's saved visualisation
         pipe.need_prior_image = False
@@ -565,9 +612,11 @@ def main():
         "roofline": roofline,
         "secondary": secondary,
     }
-    roofline.update({"all_conv_achieved": roofline["all_conv_kernels"]["achieved"], "all_conv_frac": roofline["all_conv_kernels"]["frac"],
-                     "hbm_tail_ms_per_step": roofline["hbm_tail"]["ms_per_step"], "hbm_tail_GB_per_s": roofline["hbm_tail"]["GB_per_s"],
-                     "hbm_tail_frac_of_8TBps": roofline["hbm_tail"]["frac"]})
+    if roofline is not None:
+        roofline.update({"all_conv_achieved": roofline["all_conv_kernels"]["achieved"], "all_conv_frac": roofline["all_conv_kernels"]["frac"],
+                         "hbm_tail_ms_per_step": roofline["hbm_tail"]["ms_per_step"], "hbm_tail_GB_per_s": roofline["hbm_tail"]["GB_per_s"],
+                         "hbm_tail_frac_of_8TBps": roofline["hbm_tail"]["frac"]})
+        roofline["end_to_end_frac_of_peak"] = round(out["value"] / world * gf_image / 1e3 / peak, 4)      # of the dense fp16 (fp32-mode: fp32) MFMA peak
     if a.config == "sr" and secondary:
         # the two neighbours of `value` a reader of the parsed record needs beside it (also under `secondary`): the same step with EVERY generator
         # level in the mode's own arithmetic (what corresponds to "the script's outputs, all <= 1e-3": test_sr.py:207-211 consumes the structure image), and with the
@@ -575,19 +624,18 @@ def main():
         out["value_all_levels_in_mode_precision"] = secondary.get("images_per_s_all_levels_in_mode_precision", out["value"])
         out["value_without_prior_image"] = secondary.get("images_per_s_without_prior_image")
         out["config"]["value_is"] = "defaults: structure image computed in %s, dropped; neighbours: value_all_levels_in_mode_precision, value_without_prior_image" % img_prec
-    if a.config == "sr":
+    if a.full and a.config == "sr":
         out["headline_note"] = ("value: %s mode, product defaults (check_finite on, need_prior_image on, image-only TSPGAN level in %s), un-instrumented. fp16x2 "
                                 "(fp16+8 storage: hi*hi on the f16 MFMA + w_lo8*x_hi8 + w_hi8*x_lo8 as one block-scaled fp8 MFMA) and fp16x3 (split-half, three "
                                 "f16 MFMA products) meet the north-star bar (<= 1e-3, indices bit-exact; see parity); plain fp16 (~1e-2) and exact fp32 are "
                                 "secondary.*_mode_images_per_s; secondary.images_per_s_all_levels_in_mode_precision = no level in a cheaper arithmetic" % (a.precision, img_prec))
-    roofline["end_to_end_frac_of_peak"] = round(out["value"] / world * gf_image / 1e3 / peak, 4)          # of the dense fp16 (fp32-mode: fp32) MFMA peak
     if world > 1 or a.force_gather:
         out["ranks"] = {"world_size": dist.get_world_size(), "backend": dist.get_backend(),
                         "per_rank_images_per_s": [round(c_ * a.steps / t_, 2) for c_, t_ in zip(per_rank_images, per_rank_dt)]}
 
     cpu_model, host_cores, affinity = cpu_info()
     # ---- CPU baseline (the oracle = port of the reference's CPU forward) + parity, rank 0 at N=1 only
-    if rank == 0 and world == 1 and a.cpu_images > 0 and a.config == "sr":
+    if a.full and rank == 0 and world == 1 and a.cpu_images > 0 and a.config == "sr":
         from oracle import marconet_oracle as O
         k = min(a.cpu_images, len(samp_idx))
         sel = samp_idx[:k]                       # the strips the oracle recomputes: spread over the timed batch (one per generator chunk)
@@ -718,7 +766,7 @@ def main():
                          "tests/golden; unpinned by the reference itself: basicsr fused_act (un-vendored; upstream semantics sqrt2*lrelu(x+b)); cv2 INTER_CUBIC is outside "
                          "this forward; cpu_baseline.kind = port (the oracle: /root/reference does not travel to the GPU box)")
         out["parity"] = par
-    elif rank == 0 and world == 1 and a.cpu_images > 0 and a.config == "gan":
+    elif a.full and rank == 0 and world == 1 and a.cpu_images > 0 and a.config == "gan":
         from oracle import marconet_oracle as O
         threads = host_threads(a.cpu_threads)
         torch.set_num_threads(threads)
@@ -736,7 +784,7 @@ def main():
         out["parity"] = {"image_max_abs_%s" % a.precision: round((yk[0].cpu() - ref[0]).abs().max().item(), 6),
                          "prior64_max_abs_%s" % a.precision: round((yk[1].cpu() - ref[1]).abs().max().item(), 6),
                          "image_max_abs_module_call": round((ym[0].cpu() - ref[0]).abs().max().item(), 6)}
-    elif rank == 0 and world == 1 and a.cpu_images > 0 and a.config == "mixed":
+    elif a.full and rank == 0 and world == 1 and a.cpu_images > 0 and a.config == "mixed":
         # configs[4] stand-alone: the narrowest strip against the reference arithmetic at its bucket width, timed on the host
         from oracle import marconet_oracle as O
         threads = host_threads(a.cpu_threads)

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -19,7 +20,7 @@ def _line(*args):
 
 
 def test_default_line_has_the_contract_fields():
-    d = _line("--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "8", "--cpu-images", "1", "--secondary-steps", "1")
+    d = _line("--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "8", "--cpu-images", "1", "--secondary-steps", "1", "--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
               "roofline", "cpu_baseline", "parity"):
         assert k in d, k
@@ -54,5 +55,17 @@ def test_default_line_has_the_contract_fields():
 
 @pytest.mark.parametrize("config", ["gan", "mixed"])
 def test_other_config_lines(config):
-    d = _line("--config", config, "--steps", "1", "--warmup", "1", "--batch", "8")
+    d = _line("--config", config, "--steps", "1", "--warmup", "1", "--batch", "8", "--full")
     assert d["value"] > 0 and "roofline" in d and "cpu_baseline" in d and "parity" in d and d["config"]["workload"].startswith("configs[")
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """without --full: the headline only, and --dump-outputs writes the last timed step's output (24 strips = 75 MB: a seeded sample of 20)"""
+    d = _line("--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "24", "--dump-outputs", str(tmp_path))
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "images/s" and d["dtype"] == "f16x2" and d["higher_is_better"] is True
+    assert d["value"] > 0 and abs(d["value"] - 24 * 1e3 / d["ms_per_step"]) < 0.05 * d["value"]
+    assert d["roofline"] is None and d["secondary"] is None and "cpu_baseline" not in d and "parity" not in d
+    y, idx = np.load(tmp_path / "sr.npy"), np.load(tmp_path / "sr_index.npy")
+    assert y.dtype == np.float32 and y.shape == (20, 3, 128, 2048) and np.isfinite(y).all() and np.abs(y).max() <= 1.0
+    assert idx.dtype == np.float64 and idx.tolist() == sorted(set(idx.tolist())) and 0 <= idx.min() and idx.max() < 24
+    assert sorted(os.listdir(tmp_path)) == ["sr.npy", "sr_index.npy"] and sum(f.stat().st_size for f in tmp_path.iterdir()) <= 64 * 10 ** 6

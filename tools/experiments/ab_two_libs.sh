@@ -19,7 +19,7 @@ tile "$PROD" prod --only x2:s1 --shape 32,128,2048,64,64; tile "$VAR" "$2" --onl
 for rep in $(seq 1 "$REPS"); do
   for which in prod "$2"; do
     lib="$PROD"; [ "$which" != "prod" ] && lib="$VAR"
-    MARCONET_HIP_LIB="$lib" timeout 300 python bench.py --steps 5 --warmup 1 --no-secondary --cpu-images 0 2>/dev/null | python -c "
+    MARCONET_HIP_LIB="$lib" timeout 300 python bench.py --steps 5 --warmup 1 --full --no-secondary --cpu-images 0 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('$which', d['value'], 'img/s', d['ms_per_step'], 'ms | dominant', r['achieved'], 'TFLOP/s | tail', r['hbm_tail_ms_per_step'], 'ms', {k:v['ms_per_step'] for k,v in r['hbm_tail']['by_kernel'].items()}, '| convs by kernel', r['all_conv_kernels']['by_kernel_ms_per_step'])"

@@ -4,7 +4,7 @@
 # gpurun_out/<tag>/ — copy what is to be judged into profiles/.  Steps:
 #   tests            the whole GPU tier (pytest -m gpu) + smoke()
 #   tests:<expr>     pytest -m gpu -k "<expr>"
-#   bench            python bench.py --steps 5 --warmup 2            (the line the driver produces, shorter)
+#   bench            python bench.py --steps 5 --warmup 2 --full     (the whole line: roofline, secondary, CPU baseline, parity)
 #   bench:<args>     python bench.py <args>                           (spaces as '+': bench:--steps+3+--glyph-chunk+2048)
 #   tail             tools/tail_ab.py: the HBM-bound kernels at bench shapes, every A/B form
 #   tile:<args>      tools/tile_power_ab.py <args>
@@ -23,7 +23,7 @@ for step in "$@"; do
       else { timeout 2400 python -m pytest tests -m gpu -q --tb=short; timeout 600 python -c "import __graft_entry__ as g; g.smoke()"; } > "$O/${k}_tests.log" 2>&1; fi
       tail -4 "$O/${k}_tests.log" ;;
     bench)
-      [ -z "$arg" ] && arg="--steps 5 --warmup 2"
+      [ -z "$arg" ] && arg="--steps 5 --warmup 2 --full"
       timeout 1500 python bench.py $arg > "$O/${k}_bench.json" 2> "$O/${k}_bench.err"; tail -c 600 "$O/${k}_bench.json"; echo ;;
     tail) timeout 900 python tools/tail_ab.py $arg > "$O/${k}_tail_ab.txt" 2>&1; tail -40 "$O/${k}_tail_ab.txt" ;;
     tile) timeout 900 python tools/tile_power_ab.py $arg > "$O/${k}_tile_ab.txt" 2>&1; grep -i "tflop" "$O/${k}_tile_ab.txt" | tail -20 ;;
