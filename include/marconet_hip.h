@@ -156,9 +156,7 @@ enum { MNET_CONV_ALGO_AUTO = 0, MNET_CONV_ALGO_REG_STAGED = 1, MNET_CONV_ALGO_LD
                                        * same MFMA sequence as ids 0-6: identical bits.
                                        *   MNET_F16M launches, id 16 (round 6): the 256x256 tile with ONE wave per SIMD — 4 waves x 128x128 outputs, the accumulators
                                        *          in the accumulator register file (conv_dma_w4.hip) — AUTO's fp16+8 choice for cout >= 256, >= 65536 pixels; writes
-                                       *          mnet_conv_desc.gn_partial itself; same MFMA sequence per output as the fp16+8 ids 0-15: identical bytes.  A launch
-                                       *          it is not built for — an activation other than NONE / LRELU / LRELU_SQRT2, ho * wo not a multiple of 32, more than
-                                       *          512 k-slabs — runs on id 15 (the 8-wave tile) under this id, same bytes */,
+                                       *          mnet_conv_desc.gn_partial itself; same MFMA sequence per output as the fp16+8 ids 0-15: identical bytes */,
        MNET_CONV_ALGO_FLAG_ONE_TILE = 256 /* OR-ed in: LDS-DMA kernel launched with one workgroup per tile instead of its
                                             * persistent grid (A/B measurements only; same results) */,
        MNET_CONV_ALGO_FLAG_X1_CENTER = 512 /* OR-ed in (round 4): the SECOND source x1 contributes through the filter's CENTRE tap only —
@@ -178,9 +176,13 @@ int mnet_conv2d_nhwc_ex(const mnet_conv_desc* d, int32_t algo, void* stream);
  * the association of the fp32 sum. */
 int mnet_conv2d_splitk(const mnet_conv_desc* d, int32_t ksplit, float* workspace, void* stream);
 
-/* which kernel `algo` resolves to for this launch, without launching: MNET_CONV_ALGO_REG_STAGED, MNET_CONV_ALGO_SKINNY,
- * MNET_CONV_ALGO_DMA_CFG0 + id or MNET_CONV_ALGO_STRIP_CFG0 + id; negative MNET_E_* on invalid arguments (bench.py buckets
- * its timings by this) */
+/* the kernel that runs this launch under `algo`, without launching: MNET_CONV_ALGO_REG_STAGED, MNET_CONV_ALGO_SKINNY,
+ * MNET_CONV_ALGO_DMA_CFG0 / MNET_CONV_ALGO_DMA_CFG16 + id or MNET_CONV_ALGO_STRIP_CFG0 + id; negative MNET_E_* exactly when
+ * mnet_conv2d_nhwc_ex refuses the launch (bench.py buckets its timings by this).  A pinned LDS-DMA id, like AUTO's choice, is
+ * handed over to another build when its own is not made for the launch (same tile shape, same bytes), and this returns the id that runs:
+ *   MNET_F16M, id 16 with an activation other than NONE / LRELU / LRELU_SQRT2, ho * wo not a multiple of 32 or more than 512 k-slabs → id 15
+ *   MNET_F16M, id 9 with gn_partial → id 8
+ * An id with no build for the storage type (e.g. MNET_F16X2 id 13, the diagnostic ids without MNET_ALLOW_DIAGNOSTIC_KERNELS=1) is MNET_E_ARG. */
 int mnet_conv2d_plan(const mnet_conv_desc* d, int32_t algo);
 
 /* 2*MACs of the launch described by d (for roofline accounting in bench.py) */

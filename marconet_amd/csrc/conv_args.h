@@ -24,16 +24,17 @@ struct ConvArgs {
     float* gn_partial;       // mnet_conv_desc.gn_partial: per (32-pixel fragment, 32-channel group) sum / sum of squares of the output, written by dma_epilogue_mx
 };
 
+// Which kernel runs a launch is decided by conv_resolve (conv_igemm.hip) alone; the launchers below run the id they are given.
+
 // conv_igemm_dma.hip
-bool conv_dma_eligible(const ConvArgs& a, int dtype);
-int conv_dma_pick(const ConvArgs& a);                           // tile configuration id AUTO would use
-int launch_conv_dma(const ConvArgs& a, hipStream_t st, int cfg);   // cfg < 0: conv_dma_pick
+typedef int (*DmaLaunchFn)(const ConvArgs& a, hipStream_t st);
+DmaLaunchFn conv_dma_launcher(int id, const ConvArgs& a);        // the build of LDS-DMA id `id` for a's storage type; nullptr: none (mnet_last_error says why)
+int launch_conv_dma(const ConvArgs& a, hipStream_t st, int id);
 
 // conv_dma_w4.hip (fp16+8 256x256 tile, one wave per SIMD, accumulators in the accumulator file: fp16+8 LDS-DMA id 16)
 int launch_conv_dma_w4(const ConvArgs& a, hipStream_t st);
 
 // conv_strip_dma.hip (3x3 / stride 1: one activation strip per filter row)
-int conv_strip_pick(const ConvArgs& a, int dtype, bool explicit_request);   // strip configuration id, or -1 when not eligible / not preferred
 int launch_conv_strip(const ConvArgs& a, hipStream_t st, int cfg);
 
 // conv_skinny.hip (fp32 1x1 over <= 512 pixels: the TextViT linears of a small batch; bit-identical to the general kernel)

@@ -14,7 +14,7 @@ __device__ __forceinline__ int swz_dma(int row, int chunk) { return row * 128 + 
 
 #define VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 
-// store 8 consecutive output channels co..co+7 of pixel `pix` (DBG: diagnostic variants, see launch_dma_id)
+// store 8 consecutive output channels co..co+7 of pixel `pix` (DBG: diagnostic variants, see conv_dma_launcher)
 template <int DBG, bool X3 = false>
 __device__ __forceinline__ void store8(const ConvArgs& p, const float* v, int pix, int co) {
     if constexpr (X3) {                 // split-half output: 8 hi halves, and 64 bytes further the 8 lo halves
@@ -88,7 +88,7 @@ __device__ __forceinline__ float* kernarg_gn_partial() {
 
 // GN: this instantiation can write the GroupNorm partial sums (ConvArgs::gn_partial).  The software-pipelined tiles are built without it: the extra
 // live values of that block moved hipcc's spill choice into their slab loop (two scratch accesses on the hot path, tools/isa_hot_scratch.py); launches
-// that ask for the sums take the lock-step form of the same tile (conv_dma_pick), which stays clean.
+// that ask for the sums take the lock-step form of the same tile (dma_handover in conv_igemm.hip), which stays clean.
 // ACC: where the accumulator blocks are — `acc.get(fa, px, q)` = value q of block (weight fragment fa, pixel fragment px).  The 8 / 16-wave tiles hand over their VGPR
 // array (AccArray); the one-wave-per-SIMD tile (conv_dma_w4.hip) reads its blocks out of the accumulator file where they are consumed.
 template <int FA, int FB>

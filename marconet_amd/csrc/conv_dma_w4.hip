@@ -715,9 +715,7 @@ int launch_conv_dma_w4(const ConvArgs& a, hipStream_t st) {
     const int lim = dma_grid_limit();
     static const bool env_one_tile = [] { const char* e = getenv("MNET_DMA_ONE_TILE"); return e && atoi(e) != 0; }();
     if (grid > lim && !a.one_tile_per_wg && !env_one_tile) grid = lim & ~7;
-    // the epilogue of this tile takes the per-image scale rows one float per lane (32-pixel fragments inside one image) and has the identity / LeakyReLU arms only:
-    // anything else runs on the 8-wave tile, same bytes
-    if ((a.howo & 31) != 0 || (a.act != MNET_ACT_NONE && a.act != MNET_ACT_LRELU && a.act != MNET_ACT_LRELU_SQRT2)) return launch_conv_dma(a, st, 15);
+    // (a launch this tile is not built for never gets here: conv_resolve hands it to id 15)
     const bool sc = a.out_scale || a.post_scale, rg = a.res || a.gn_partial;
     if (sc) return rg ? launch_w4<true, true>(b, grid, st) : launch_w4<true, false>(b, grid, st);
     return rg ? launch_w4<false, true>(b, grid, st) : launch_w4<false, false>(b, grid, st);

@@ -577,18 +577,164 @@ static int conv_prepare(const mnet_conv_desc* d, int32_t algo, ConvArgs& a) {
     return MNET_OK;
 }
 
-// resolves `algo` to the kernel that runs: MNET_CONV_ALGO_REG_STAGED, MNET_CONV_ALGO_SKINNY, MNET_CONV_ALGO_DMA_CFG0 + id or
-// MNET_CONV_ALGO_STRIP_CFG0 + id (negative: error)
-static int conv_resolve(const mnet_conv_desc* d, int32_t algo, const ConvArgs& a) {
+// ------------------------------------------------------------------------------------------------------------------------------------
+// Kernel selection.  conv_resolve alone decides which kernel runs a launch — hand-overs between LDS-DMA ids included — and
+// mnet_conv2d_plan returns its answer; the launchers run the id they are given.
+//
+// A/B knobs that change the id (environment, read once per process; unset = the production choice):
+//   MNET_DMA_NO_STRIP=1      AUTO never takes the strip kernel (the per-tap LDS-DMA tile instead)
+//   MNET_STRIP_256=1         f16, cout >= 256: AUTO takes the 16-wave 256x256 strip tile
+//   MNET_MX_STRIP256=1       fp16+8, cout >= 256: AUTO takes the 8-wave 256x256 strip tile (round 4)
+//   MNET_STRIP_128=1         f16, cout 128: AUTO takes the 128x256 strip tile
+//   MNET_DMA_CFG_BIG256=id   f16, cout >= 256, >= 65536 pixels: LDS-DMA id (default 16)
+//   MNET_DMA_CFG_BIG128=id   f16, cout 128, >= 65536 pixels: LDS-DMA id (default 9)
+//   MNET_X3_16WAVE=1         split-half, cout >= 128, >= 65536 pixels: the 16-wave tiles 0 / 4 instead of the two knobs below
+//   MNET_X3_CFG256=id        split-half, cout >= 256, >= 65536 pixels: LDS-DMA id (default 11)
+//   MNET_X3_CFG128=id        split-half, cout 128, >= 65536 pixels: LDS-DMA id (default 9)
+//   MNET_MX_CFG256=id        fp16+8, cout >= 256, >= 65536 pixels: LDS-DMA id (default 16)
+//   MNET_MX_CFG128=id        fp16+8, cout 128, >= 65536 pixels: LDS-DMA id (default 8)
+//   MNET_MX_CFG64=id         fp16+8, cout 64, >= 65536 pixels: LDS-DMA id (default 13)
+//   MNET_GN_LOCKSTEP=1       fp16+8 launches that write GroupNorm sums, cout >= 128: where AUTO would take id 15, the lock-step id 11 (round 5's first form)
+// (MNET_ALLOW_DIAGNOSTIC_KERNELS, which admits the diagnostic ids, is read by the id table itself: conv_dma_launcher.)
+// ------------------------------------------------------------------------------------------------------------------------------------
+static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+
+struct SelectKnobs {
+    bool no_strip = env_int("MNET_DMA_NO_STRIP", 0) != 0;
+    bool strip256 = env_int("MNET_STRIP_256", 0) != 0;
+    bool mx_strip256 = env_int("MNET_MX_STRIP256", 0) != 0;
+    bool strip128 = env_int("MNET_STRIP_128", 0) != 0;
+    int big256 = env_int("MNET_DMA_CFG_BIG256", 16);
+    int big128 = env_int("MNET_DMA_CFG_BIG128", 9);
+    int x3_16w = env_int("MNET_X3_16WAVE", 0);
+    int x3_256 = env_int("MNET_X3_CFG256", 11);
+    int x3_128 = env_int("MNET_X3_CFG128", 9);
+    int mx_256 = env_int("MNET_MX_CFG256", 16);
+    int mx_128 = env_int("MNET_MX_CFG128", 8);
+    int mx_64 = env_int("MNET_MX_CFG64", 13);
+    int gn_lockstep = env_int("MNET_GN_LOCKSTEP", 0);
+};
+
+static const SelectKnobs& knobs() {
+    static const SelectKnobs k;
+    return k;
+}
+
+// eligibility of the LDS-DMA path (see the header comment); a launch that fails it runs on the register-staged kernel
+static bool conv_dma_eligible(const ConvArgs& a, int dtype) {
+    if ((dtype != MNET_F16 && dtype != MNET_F16X2 && dtype != MNET_F16M) || a.in_scale || a.act > MNET_ACT_LRELU_SQRT2) return false;
+    if (dtype != MNET_F16 && a.cout % 32 != 0) return false;          // (a.c0 / a.cin / a.K are physical here: f16 view, doubled)
+    if (a.cin % 64 != 0 || a.c0 % 64 != 0 || a.cout < 64 || a.cout % 8 != 0 || a.kh * a.kw > 32 || a.kh > 8 || a.kw > 8) return false;
+    // 31-bit buffer offsets: a pixel tile may touch ceil(256/howo)+1 images
+    const long long imgs = 512 / a.howo + 2;   // largest pixel tile is 512
+    const long long per_img = (long long)a.h * a.w * (a.c0 > a.c1 ? a.c0 : a.c1) * 2;
+    if (per_img * imgs >= 0x7fffffffLL) return false;
+    if ((long long)a.h * a.w * imgs >= (1ll << 23) || (a.c0 > a.c1 ? a.c0 : a.c1) * 2 >= (1 << 23)) return false;   // 24-bit signed multiply of (pixel, bytes per pixel)
+    if ((long long)256 * a.K * 2 >= 0x40000000LL) return false;
+    if ((long long)a.cout * a.K * 2 >= 0x7fffffffLL) return false;
+    return true;
+}
+
+// LDS-DMA tile configuration id AUTO uses for an eligible launch
+static int conv_dma_pick(const ConvArgs& a) {
+    const SelectKnobs& k = knobs();
+    const bool big = a.npix >= 256 * 256;
+    // a launch that would leave a quarter or more of the CUs without a tile (a strip at a time: 4096-16384 pixels) takes the
+    // 128x128 tile instead: twice the workgroups (same k order, same bits)
+    const long long t128 = (a.npix + 127) / 128, t256 = (a.npix + 255) / 256;
+    if (a.split == 2) {
+        // id 15 (round 4) = id 6 with the slab loop software-pipelined across the barrier: +0.5 ... +3.8 % over id 11 (= id 6 with the LDS reads
+        // placed by scheduling hints) on the four shapes that carry the step, +1.2 % end to end, same bytes (profiles/r4g_*)
+        // id 16 (round 6) = the same tile with ONE wave per SIMD (conv_dma_w4.hip: 4 waves x 128x128 outputs, accumulators in a[0:255]): +1.3 ... +2.5 % over id 15 on the
+        // shapes that carry the step at a 2-5 % higher shader clock for the same package power, same bytes (profiles/r6i_*); it writes GroupNorm sums itself
+        // id 13 = id 5 + hints: 260 vs 251
+        const auto lockstep = [&](int id) { return a.gn_partial && id == 15 && k.gn_lockstep ? 11 : id; };
+        if (a.cout >= 256) return big ? lockstep(k.mx_256) : (t128 * ((a.cout + 255) / 256) < 200 ? 10 : 1);
+        if (a.cout >= 128) return big ? lockstep(k.mx_128) : (t256 * ((a.cout + 127) / 128) < 200 ? 10 : 2);
+        return big ? k.mx_64 : 3;
+    }
+    // split-half (fp16x3): the 8-wave forms of the two big tiles.  Three products per slab need a third set of operand
+    // fragments live: the 16-wave tiles (128 VGPRs per wave) spill (59 / 133 VGPRs) and park 62 % of their wave cycles in
+    // s_waitcnt / barriers; with 2 waves per SIMD and 256 VGPRs the same tiles run 19 % faster (measured: 446 vs 372 TFLOP/s
+    // algorithmic on the 256x256 tile, B = 64) — the opposite of the f16 kernel, where the 16-wave form wins by 6 %.
+    // ids 8 / 9 = ids 6 / 7 with the next slab's DMA pieces issued after the first of the three multiply groups instead of right
+    // after the barrier: +5.6 % / +3.7 % (438 vs 414 TFLOP/s on the 256x256 tile, same box, B = 64).  (Two insertion points —
+    // weights after the first group, activations after the second — keep the DMA state live across all three groups: 167-275
+    // VGPRs spill with scratch reloads inside the k-loop, 227 TFLOP/s.)
+    // id 11 = id 8 with the LDS reads placed by scheduling hints (all hi fragments up front, the lo activation fragments under the
+    // first group's MFMAs): 472 vs 465 TFLOP/s (+1.5 %); the 128x512 tile does not gain (id 12 stays an A/B knob)
+    if (a.split && big && a.cout >= 128) return k.x3_16w ? (a.cout >= 256 ? 0 : 4) : (a.cout >= 256 ? k.x3_256 : k.x3_128);
+    // f16 big tiles: ids 8 / 9 = ids 0 / 4 with the next slab's DMA pieces issued between the two half slabs instead of right after
+    // the barrier (+2.8 % on the 256x256 tile: 1140 vs 1109 TFLOP/s, B = 64; same MFMA sequence, same bits).  id 16 = the 8-wave
+    // 256x256 tile with both half slabs' fragments requested up front as well (the second half's LDS reads run under the first
+    // half's MFMAs — it has the registers for it): 1176-1188 vs 1148-1166 TFLOP/s for id 8, 1064 for the plain 8-wave id 6 → AUTO
+    // for cout >= 256; the same form of the 128x512 tile (id 17) is slower than id 9 (22.3 vs 18.3 ms per step)
+    if (a.cout >= 256) return big ? k.big256 : (t128 * ((a.cout + 255) / 256) < 200 ? 10 : 1);
+    if (a.cout >= 128) return big ? k.big128 : (t256 * ((a.cout + 127) / 128) < 200 ? 10 : 2);
+    return big ? 5 : 3;
+}
+
+// tile configuration the strip kernel would use for this launch (0: 256x256, 16 waves; 1: 64x512, 8 waves), or -1 when
+// the launch is not eligible: 3x3 / stride 1 / pad 1, one source tensor, whole-row (or whole-segment) tiles that never
+// straddle an image, and everything conv_dma_eligible already requires
+static int conv_strip_pick(const ConvArgs& a, int dtype, bool explicit_request) {
+    // 256x256 tiles: measured neutral (89.8 + 5.1 vs 94.5 ms per bench step; 128-VGPR budget of its 16 waves is exhausted,
+    // 20 spills) — AUTO keeps the per-tap kernel there unless MNET_STRIP_256=1; the 64x512 tile (8 waves) gains 20 %.
+    const SelectKnobs& k = knobs();
+    if ((dtype != MNET_F16 && dtype != MNET_F16X2 && dtype != MNET_F16M) || !conv_dma_eligible(a, dtype)) return -1;
+    // fp16+8, cout >= 256: the 8-wave 256x256 strip tile — explicit request or MNET_MX_STRIP256=1
+    const bool mx_big = dtype == MNET_F16M && a.cout >= 256 && a.cout % 256 == 0 && (explicit_request || k.mx_strip256);
+    if (dtype != MNET_F16 && a.cout >= 128 && !mx_big) return -1;        // split-half: the 64x512 tile only (the big tiles take the 8-wave per-tap forms)
+    if (a.cout >= 256 && !explicit_request && !k.strip256 && !mx_big) return -1;
+    if (a.kh != 3 || a.kw != 3 || a.sh != 1 || a.sw != 1 || a.ph != 1 || a.pw != 1 || a.c1 != 0 || a.x1) return -1;
+    if (a.ho != a.h || a.wo != a.w) return -1;
+    int cfg, bp;
+    if (a.cout >= 256) { cfg = 0; bp = 256; }
+    else if (a.cout < 128) { cfg = 1; bp = 512; }
+    else {                                                     // cout 128: a 512-pixel strip pair + weights exceed the LDS → 128x256
+        if (!explicit_request && !k.strip128) return -1;
+        cfg = 2; bp = 256;
+    }
+    if (a.npix < 256 * 256 || a.npix % bp != 0) return -1;
+    const int minw = bp == 256 ? 16 : 32;
+    if (a.w < minw || a.w % 16 != 0) return -1;
+    if (a.w < bp ? (bp % a.w != 0 || a.howo % bp != 0) : (a.w % bp != 0)) return -1;
+    if ((long long)a.h * a.w * a.c0 * 2 >= 0x7fffffffLL) return -1;       // one image per buffer descriptor
+    return cfg;
+}
+
+// The hand-overs: a launch that the LDS-DMA build of `id` is not built for runs on the build that is (the same tile shape, the same
+// MFMA sequence per output: the same bytes).  Pinned requests and AUTO's choice alike.
+static int dma_handover(int id, const ConvArgs& a) {
+    if (a.split != 2) return id;
+    // fp16+8 id 16, the one-wave-per-SIMD tile (conv_dma_w4.hip): its slab table holds 512 k-slabs per tile (cin * taps <= 16384 halves), and its
+    // epilogue takes the per-image scale rows one float per lane (32-pixel fragments inside one image) and has the identity / LeakyReLU arms only
+    // → the 8-wave tile 15
+    if (id == 16 && (a.ktiles > 512 || (a.howo & 31) != 0 || (a.act != MNET_ACT_NONE && a.act != MNET_ACT_LRELU && a.act != MNET_ACT_LRELU_SQRT2)))
+        return 15;
+    // launches that write GroupNorm partial sums: the software-pipelined 128x512 tile 9 has no build with that block → its lock-step form 8
+    // (id 15 has one, conv_dma_swp_gn.hip; id 16 writes the sums itself)
+    if (id == 9 && a.gn_partial) return 8;
+    return id;
+}
+
+// LDS-DMA id of a resolved kernel (MNET_CONV_ALGO_DMA_CFG0 + id or MNET_CONV_ALGO_DMA_CFG16 + id - 16), -1 for any other kernel
+static int dma_id(int k) {
+    if (k >= MNET_CONV_ALGO_DMA_CFG16) return k - MNET_CONV_ALGO_DMA_CFG16 + 16;
+    return k >= MNET_CONV_ALGO_DMA_CFG0 && k < MNET_CONV_ALGO_STRIP_CFG0 ? k - MNET_CONV_ALGO_DMA_CFG0 : -1;
+}
+
+static int dma_algo(int id) { return id < 16 ? MNET_CONV_ALGO_DMA_CFG0 + id : MNET_CONV_ALGO_DMA_CFG16 + (id - 16); }
+
+// the kernel `algo` asks for on this launch, before the hand-overs: MNET_CONV_ALGO_REG_STAGED, MNET_CONV_ALGO_SKINNY,
+// MNET_CONV_ALGO_DMA_CFG0 / 16 + id or MNET_CONV_ALGO_STRIP_CFG0 + id (negative: error)
+static int conv_request(const mnet_conv_desc* d, int32_t algo, const ConvArgs& a) {
     algo &= ~(MNET_CONV_ALGO_FLAG_ONE_TILE | MNET_CONV_ALGO_FLAG_X1_CENTER);
-    static const bool no_strip = [] { const char* e = getenv("MNET_DMA_NO_STRIP"); return e && atoi(e) != 0; }();   // A/B knob
     const bool dma_ok = conv_dma_eligible(a, d->dtype);
     if (a.x1_center) {          // only the LDS-DMA kernels walk the second source at one tap
         if (!dma_ok || algo == MNET_CONV_ALGO_REG_STAGED || algo == MNET_CONV_ALGO_SKINNY || (algo >= MNET_CONV_ALGO_STRIP_CFG0 && algo < MNET_CONV_ALGO_DMA_CFG16))
             return mnet_fail(MNET_E_ARG, "conv: MNET_CONV_ALGO_FLAG_X1_CENTER needs a launch the LDS-DMA kernel takes");
-        if (algo >= MNET_CONV_ALGO_DMA_CFG0) return algo;
-        const int id = conv_dma_pick(a);
-        return id < 16 ? MNET_CONV_ALGO_DMA_CFG0 + id : MNET_CONV_ALGO_DMA_CFG16 + (id - 16);
+        return algo >= MNET_CONV_ALGO_DMA_CFG0 ? algo : dma_algo(conv_dma_pick(a));
     }
     const int strip = conv_strip_pick(a, d->dtype, algo >= MNET_CONV_ALGO_STRIP_CFG0);
     if (algo >= MNET_CONV_ALGO_DMA_CFG16) {
@@ -611,17 +757,22 @@ static int conv_resolve(const mnet_conv_desc* d, int32_t algo, const ConvArgs& a
     if (algo >= MNET_CONV_ALGO_LDS_DMA && !dma_ok)
         return mnet_fail(MNET_E_ARG, "conv: LDS-DMA algo needs f16 (cin %% 64 == 0) or split-half (cin %% 32 == 0), cout >= 64, cout %% 8 == 0 and no input transform");
     if (algo >= MNET_CONV_ALGO_DMA_CFG0) return algo;
-    if (algo != MNET_CONV_ALGO_REG_STAGED && strip >= 0 && !no_strip) return MNET_CONV_ALGO_STRIP_CFG0 + strip;
-    if (dma_ok && algo != MNET_CONV_ALGO_REG_STAGED) {
-        const int id = conv_dma_pick(a);
-        return id < 16 ? MNET_CONV_ALGO_DMA_CFG0 + id : MNET_CONV_ALGO_DMA_CFG16 + (id - 16);
-    }
+    if (algo != MNET_CONV_ALGO_REG_STAGED && strip >= 0 && !knobs().no_strip) return MNET_CONV_ALGO_STRIP_CFG0 + strip;
+    if (dma_ok && algo != MNET_CONV_ALGO_REG_STAGED) return dma_algo(conv_dma_pick(a));
     return MNET_CONV_ALGO_REG_STAGED;
 }
 
-// conv_resolve + the one constraint that depends on its answer: only the fp16+8 LDS-DMA / strip epilogue (dma_epilogue_mx) writes gn_partial
-static int conv_resolve_checked(const mnet_conv_desc* d, int32_t algo, const ConvArgs& a) {
-    const int k = conv_resolve(d, algo, a);
+// resolves `algo` to the kernel that runs: MNET_CONV_ALGO_REG_STAGED, MNET_CONV_ALGO_SKINNY, MNET_CONV_ALGO_DMA_CFG0 / 16 + id or
+// MNET_CONV_ALGO_STRIP_CFG0 + id (negative: error — nothing that this refuses is launched, and nothing that it accepts is refused at launch)
+static int conv_resolve(const mnet_conv_desc* d, int32_t algo, const ConvArgs& a) {
+    int k = conv_request(d, algo, a);
+    int id = dma_id(k);
+    if (id >= 0) {
+        id = dma_handover(id, a);
+        if (!conv_dma_launcher(id, a)) return MNET_E_ARG;      // no build of this id for the storage type (message set)
+        k = dma_algo(id);
+    }
+    // only the fp16+8 LDS-DMA / strip epilogue (dma_epilogue_mx) writes gn_partial
     if (k >= 0 && a.gn_partial && k < MNET_CONV_ALGO_DMA_CFG0)
         return mnet_fail(MNET_E_ARG, "conv: gn_partial needs a launch the LDS-DMA / strip kernels take (this one resolves to kernel %d)", k);
     return k;
@@ -631,19 +782,18 @@ extern "C" int mnet_conv2d_plan(const mnet_conv_desc* d, int32_t algo) {
     ConvArgs a;
     const int rc = conv_prepare(d, algo, a);
     if (rc != MNET_OK) return rc;
-    return conv_resolve_checked(d, algo, a);
+    return conv_resolve(d, algo, a);
 }
 
 extern "C" int mnet_conv2d_nhwc_ex(const mnet_conv_desc* d, int32_t algo, void* stream) {
     ConvArgs a;
     const int rc = conv_prepare(d, algo, a);
     if (rc != MNET_OK) return rc;
-    const int k = conv_resolve_checked(d, algo, a);
+    const int k = conv_resolve(d, algo, a);
     if (k < 0) return k;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (k >= MNET_CONV_ALGO_DMA_CFG16) return launch_conv_dma(a, st, k - MNET_CONV_ALGO_DMA_CFG16 + 16);
+    if (dma_id(k) >= 0) return launch_conv_dma(a, st, dma_id(k));
     if (k >= MNET_CONV_ALGO_STRIP_CFG0) return launch_conv_strip(a, st, k - MNET_CONV_ALGO_STRIP_CFG0);
-    if (k >= MNET_CONV_ALGO_DMA_CFG0) return launch_conv_dma(a, st, k - MNET_CONV_ALGO_DMA_CFG0);
     if (k == MNET_CONV_ALGO_SKINNY) return launch_conv_skinny(a, st);
     if (d->dtype == MNET_F16X2) return launch_dtype<hs>(a, st);
     if (d->dtype == MNET_F16M) return launch_dtype<hm>(a, st);

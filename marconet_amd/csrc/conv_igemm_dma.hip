@@ -921,162 +921,98 @@ int launch_dma_swp_gn(const ConvArgs& a, hipStream_t st);      // conv_dma_swp_g
 // partial sums associated differently.
 // ids 7-9: v_mfma_f32_32x32x16_f16 forms (fp32 sums associate differently).
 // ids 11-15: DIAGNOSTIC builds that produce wrong results on purpose (tools/wg_timeline.py, tools/conv_bench.py).
-static int launch_dma_id(int id, const ConvArgs& a, hipStream_t st) {
+// This is the one list of LDS-DMA builds: the planner (conv_resolve) asks it whether an id has a form for the launch's storage type, the launch
+// runs what it returns.  nullptr: no such form (mnet_last_error says why).  A choice between two builds of ONE id (id 15 with GroupNorm sums,
+// id 14 under MNET_DIAG_SWP) is made here; which id runs is not.
+static DmaLaunchFn no_form(const char* fmt, int id) {
+    mnet_fail(MNET_E_ARG, fmt, id);
+    return nullptr;
+}
+
+DmaLaunchFn conv_dma_launcher(int id, const ConvArgs& a) {
+    static const bool allow_diag = [] { const char* e = getenv("MNET_ALLOW_DIAGNOSTIC_KERNELS"); return e && atoi(e) != 0; }();
     if (a.split == 2) { // fp16+8 (MNET_F16M) instantiations: the same tile shapes on 32x32 MFMAs
         switch (id) {
-            case 0: return launch_dma_cfg<256, 256, 4, 4, 2, 32, 0, true, true, false, true>(a, st);
-            case 1: return launch_dma_cfg<256, 128, 4, 2, 3, 32, 0, true, false, false, true>(a, st);
-            case 2: return launch_dma_cfg<128, 256, 2, 4, 3, 32, 0, true, false, false, true>(a, st);
-            case 3: return launch_dma_cfg<64, 256, 1, 8, 3, 32, 0, true, false, false, true>(a, st);
-            case 4: return launch_dma_cfg<128, 512, 2, 8, 2, 32, 0, true, true, false, true>(a, st);
-            case 5: return launch_dma_cfg<64, 512, 1, 8, 2, 32, 0, true, true, false, true>(a, st);
-            case 6: return launch_dma_cfg<256, 256, 2, 4, 2, 32, 0, true, true, false, true>(a, st);          // 8 waves, 128x64 per wave: AUTO for cout >= 256
-            case 7: return launch_dma_cfg<128, 512, 2, 4, 2, 32, 0, true, true, false, true>(a, st);          // 8 waves, 64x128 per wave
-            case 8: return launch_dma_cfg<128, 512, 1, 8, 2, 32, 0, true, true, false, true>(a, st);          // 8 waves, 128x64 per wave
-            case 10: return launch_dma_cfg<128, 128, 2, 4, 4, 32, 0, true, false, false, true>(a, st);
-            case 11: return launch_dma_cfg<256, 256, 2, 4, 2, 32, 0, true, true, true, true>(a, st);          // id 6 + LDS reads placed by scheduling hints
-            case 12: return launch_dma_cfg<128, 512, 1, 8, 2, 32, 0, true, true, true, true>(a, st);          // id 8, same
-            case 13: return launch_dma_cfg<64, 512, 1, 8, 2, 32, 0, true, true, true, true>(a, st);           // id 5, same
-            case 15: return launch_dma_cfg<256, 256, 2, 4, 2, 32, 0, true, false, false, true, true>(a, st);       // id 6 with the slab loop software-pipelined across the barrier (SWP)
-            case 9: return launch_dma_cfg<128, 512, 1, 8, 2, 32, 0, true, false, false, true, true>(a, st);        // id 8, same
-            case 16:                                       // round 6: the 256x256 tile with ONE wave per SIMD (4 waves x 128x128, accumulators in a[0:255]): conv_dma_w4.hip
-                if (a.ktiles > 512) return launch_conv_dma(a, st, 15);   // (its slab table holds 512 k-slabs per tile: cin * taps <= 16384 halves; same bytes from id 15)
-                return launch_conv_dma_w4(a, st);
+            case 0: return launch_dma_cfg<256, 256, 4, 4, 2, 32, 0, true, true, false, true>;
+            case 1: return launch_dma_cfg<256, 128, 4, 2, 3, 32, 0, true, false, false, true>;
+            case 2: return launch_dma_cfg<128, 256, 2, 4, 3, 32, 0, true, false, false, true>;
+            case 3: return launch_dma_cfg<64, 256, 1, 8, 3, 32, 0, true, false, false, true>;
+            case 4: return launch_dma_cfg<128, 512, 2, 8, 2, 32, 0, true, true, false, true>;
+            case 5: return launch_dma_cfg<64, 512, 1, 8, 2, 32, 0, true, true, false, true>;
+            case 6: return launch_dma_cfg<256, 256, 2, 4, 2, 32, 0, true, true, false, true>;          // 8 waves, 128x64 per wave: AUTO for cout >= 256
+            case 7: return launch_dma_cfg<128, 512, 2, 4, 2, 32, 0, true, true, false, true>;          // 8 waves, 64x128 per wave
+            case 8: return launch_dma_cfg<128, 512, 1, 8, 2, 32, 0, true, true, false, true>;          // 8 waves, 128x64 per wave
+            case 10: return launch_dma_cfg<128, 128, 2, 4, 4, 32, 0, true, false, false, true>;
+            case 11: return launch_dma_cfg<256, 256, 2, 4, 2, 32, 0, true, true, true, true>;          // id 6 + LDS reads placed by scheduling hints
+            case 12: return launch_dma_cfg<128, 512, 1, 8, 2, 32, 0, true, true, true, true>;          // id 8, same
+            case 13: return launch_dma_cfg<64, 512, 1, 8, 2, 32, 0, true, true, true, true>;           // id 5, same
+            case 15:        // id 6 with the slab loop software-pipelined across the barrier (SWP).  The tiles of THIS translation unit are built without the
+                            // GroupNorm-sum block (dma_epilogue_mx<..., GN = false>); id 15's build with it is conv_dma_swp_gn.hip (id 9 has none: conv_resolve hands it to 8)
+                if (a.gn_partial) return launch_dma_swp_gn;
+                return launch_dma_cfg<256, 256, 2, 4, 2, 32, 0, true, false, false, true, true>;
+            case 9: return launch_dma_cfg<128, 512, 1, 8, 2, 32, 0, true, false, false, true, true>;        // id 8, same
+            case 16: return launch_conv_dma_w4;            // round 6: the 256x256 tile with ONE wave per SIMD (4 waves x 128x128, accumulators in a[0:255]): conv_dma_w4.hip
             case 14: {                  // DIAGNOSTIC (wrong results): id 11 with per-phase cycle sums written over the output (tools/slab_phases.py)
-                static const bool allow = [] { const char* e = getenv("MNET_ALLOW_DIAGNOSTIC_KERNELS"); return e && atoi(e) != 0; }();
-                if (!allow) return mnet_fail(MNET_E_ARG, "conv: fp16+8 LDS-DMA id 14 is a diagnostic build with wrong results (set MNET_ALLOW_DIAGNOSTIC_KERNELS=1 to use it)");
+                if (!allow_diag) return no_form("conv: fp16+8 LDS-DMA id %d is a diagnostic build with wrong results (set MNET_ALLOW_DIAGNOSTIC_KERNELS=1 to use it)", id);
                 static const bool swp = [] { const char* e = getenv("MNET_DIAG_SWP"); return e && atoi(e) != 0; }();      // the same stamps in the software-pipelined tile (id 15)
-                if (swp) return launch_dma_cfg<256, 256, 2, 4, 2, 32, 6, true, false, false, true, true>(a, st);
-                return launch_dma_cfg<256, 256, 2, 4, 2, 32, 6, true, true, true, true>(a, st);
+                if (swp) return launch_dma_cfg<256, 256, 2, 4, 2, 32, 6, true, false, false, true, true>;
+                return launch_dma_cfg<256, 256, 2, 4, 2, 32, 6, true, true, true, true>;
             }
-            default: return mnet_fail(MNET_E_ARG, "conv: LDS-DMA tile configuration %d has no fp16+8 form", id);
+            default: return no_form("conv: LDS-DMA tile configuration %d has no fp16+8 form", id);
         }
     }
     if (a.split) {      // split-half (fp16x3) instantiations of the production tile configurations
         switch (id) {
-            case 0: return launch_dma_cfg<256, 256, 4, 4, 2, 16, 0, true>(a, st);
-            case 1: return launch_dma_cfg<256, 128, 4, 2, 3, 16, 0, true>(a, st);
-            case 2: return launch_dma_cfg<128, 256, 2, 4, 3, 16, 0, true>(a, st);
-            case 3: return launch_dma_cfg<64, 256, 1, 8, 3, 16, 0, true>(a, st);
-            case 4: return launch_dma_cfg<128, 512, 2, 8, 2, 16, 0, true>(a, st);
-            case 5: return launch_dma_cfg<64, 512, 1, 8, 2, 16, 0, true>(a, st);
-            case 6: return launch_dma_cfg<256, 256, 2, 4, 2, 16, 0, true>(a, st);          // 8 waves, 128x64 per wave: AUTO for cout >= 256
-            case 7: return launch_dma_cfg<128, 512, 2, 4, 2, 16, 0, true>(a, st);          // 8 waves, 64x128 per wave: AUTO for cout 128
-            case 8: return launch_dma_cfg<256, 256, 2, 4, 2, 16, 0, true, true>(a, st);    // id 6 with the DMA pieces after the first multiply group
-            case 9: return launch_dma_cfg<128, 512, 2, 4, 2, 16, 0, true, true>(a, st);    // id 7, same
-            case 11: return launch_dma_cfg<256, 256, 2, 4, 2, 16, 0, true, true, true>(a, st);   // id 8 + LDS reads placed by scheduling hints
-            case 12: return launch_dma_cfg<128, 512, 2, 4, 2, 16, 0, true, true, true>(a, st);   // id 9, same
-            case 10: return launch_dma_cfg<128, 128, 2, 4, 4, 16, 0, true>(a, st);
-            case 20: return launch_dma_cfg<256, 256, 2, 4, 2, 32, 0, true, true>(a, st);          // id 8 on v_mfma_f32_32x32x16_f16
-            case 21: return launch_dma_cfg<128, 512, 2, 4, 2, 32, 0, true, true>(a, st);          // id 9, same
-            default: return mnet_fail(MNET_E_ARG, "conv: LDS-DMA tile configuration %d has no split-half form", id);
+            case 0: return launch_dma_cfg<256, 256, 4, 4, 2, 16, 0, true>;
+            case 1: return launch_dma_cfg<256, 128, 4, 2, 3, 16, 0, true>;
+            case 2: return launch_dma_cfg<128, 256, 2, 4, 3, 16, 0, true>;
+            case 3: return launch_dma_cfg<64, 256, 1, 8, 3, 16, 0, true>;
+            case 4: return launch_dma_cfg<128, 512, 2, 8, 2, 16, 0, true>;
+            case 5: return launch_dma_cfg<64, 512, 1, 8, 2, 16, 0, true>;
+            case 6: return launch_dma_cfg<256, 256, 2, 4, 2, 16, 0, true>;          // 8 waves, 128x64 per wave: AUTO for cout >= 256
+            case 7: return launch_dma_cfg<128, 512, 2, 4, 2, 16, 0, true>;          // 8 waves, 64x128 per wave: AUTO for cout 128
+            case 8: return launch_dma_cfg<256, 256, 2, 4, 2, 16, 0, true, true>;    // id 6 with the DMA pieces after the first multiply group
+            case 9: return launch_dma_cfg<128, 512, 2, 4, 2, 16, 0, true, true>;    // id 7, same
+            case 11: return launch_dma_cfg<256, 256, 2, 4, 2, 16, 0, true, true, true>;   // id 8 + LDS reads placed by scheduling hints
+            case 12: return launch_dma_cfg<128, 512, 2, 4, 2, 16, 0, true, true, true>;   // id 9, same
+            case 10: return launch_dma_cfg<128, 128, 2, 4, 4, 16, 0, true>;
+            case 20: return launch_dma_cfg<256, 256, 2, 4, 2, 32, 0, true, true>;          // id 8 on v_mfma_f32_32x32x16_f16
+            case 21: return launch_dma_cfg<128, 512, 2, 4, 2, 32, 0, true, true>;          // id 9, same
+            default: return no_form("conv: LDS-DMA tile configuration %d has no split-half form", id);
         }
     }
+    // MNET_F16 ids 11-15 are DIAGNOSTIC builds that produce WRONG results on purpose (tools/wg_timeline.py, tools/conv_bench.py):
+    // refused unless the process opts in, so that a C-ABI host cannot select one by accident (the same ids are production
+    // tiles for MNET_F16X2 / MNET_F16M launches, which never reach this table)
+    if (id >= 11 && id <= 15 && !allow_diag)
+        return no_form("conv: MNET_F16 LDS-DMA id %d is a diagnostic build with wrong results (set MNET_ALLOW_DIAGNOSTIC_KERNELS=1 to use it)", id);
     switch (id) {
-        case 0: return launch_dma_cfg<256, 256, 4, 4, 2>(a, st);
-        case 1: return launch_dma_cfg<256, 128, 4, 2, 3>(a, st);
-        case 2: return launch_dma_cfg<128, 256, 2, 4, 3>(a, st);
-        case 3: return launch_dma_cfg<64, 256, 1, 8, 3>(a, st);
-        case 4: return launch_dma_cfg<128, 512, 2, 8, 2>(a, st);
-        case 5: return launch_dma_cfg<64, 512, 1, 8, 2>(a, st);
-        case 6: return launch_dma_cfg<256, 256, 2, 4, 2>(a, st);          // 8 waves, 128x64 per wave
-        case 7: return launch_dma_cfg<256, 256, 4, 4, 2, 32>(a, st);
-        case 8: return launch_dma_cfg<256, 256, 4, 4, 2, 16, 0, false, true>(a, st);       // id 0 with the DMA pieces issued between the two half slabs
-        case 9: return launch_dma_cfg<128, 512, 2, 8, 2, 16, 0, false, true>(a, st);       // id 4, same
-        case 16: return launch_dma_cfg<256, 256, 2, 4, 2, 16, 0, false, true, true>(a, st);   // 8 waves (128x64 per wave), both half slabs' fragments requested up
-                                                                                            // front (the second half's LDS reads run under the first half's MFMAs),
-                                                                                            // DMA pieces between the halves: AUTO for cout >= 256
-        case 17: return launch_dma_cfg<128, 512, 2, 4, 2, 16, 0, false, true, true>(a, st);   // the same form of the 128x512 tile (64x128 per wave)
-        case 10: return launch_dma_cfg<128, 128, 2, 4, 4>(a, st);          // small launches: twice the workgroups of ids 1 / 2, 3 slabs in flight
-        case 11: case 12: case 13: case 14: case 15: {
-            // MNET_F16 ids 11-15 are DIAGNOSTIC builds that produce WRONG results on purpose (tools/wg_timeline.py, tools/conv_bench.py):
-            // refused unless the process opts in, so that a C-ABI host cannot select one by accident (the same ids are production
-            // tiles for MNET_F16X2 / MNET_F16M launches, which never reach this table)
-            static const bool allow = [] { const char* e = getenv("MNET_ALLOW_DIAGNOSTIC_KERNELS"); return e && atoi(e) != 0; }();
-            if (!allow) return mnet_fail(MNET_E_ARG, "conv: MNET_F16 LDS-DMA id %d is a diagnostic build with wrong results (set MNET_ALLOW_DIAGNOSTIC_KERNELS=1 to use it)", id);
-            break;
-        }
-        default: break;
-    }
-    switch (id) {
-        case 11: return launch_dma_cfg<256, 256, 4, 4, 2, 16, 4>(a, st);  // DIAGNOSTIC: all tiles store over tile 0; stamps after tile 0
-        case 12: return launch_dma_cfg<256, 256, 4, 4, 2, 16, 5>(a, st);  // DIAGNOSTIC: no output stores; stamps after tile 0
-        case 13: return launch_dma_cfg<256, 256, 4, 4, 2, 16, 3>(a, st);  // DIAGNOSTIC: per-tile time stamps written over the output
-        case 14: return launch_dma_cfg<256, 256, 4, 4, 2, 16, 1>(a, st);  // DIAGNOSTIC: activations read from a 256 KiB window
-        case 15: return launch_dma_cfg<256, 256, 4, 4, 2, 16, 2>(a, st);  // DIAGNOSTIC: no DMA after a tile's first k-slab
-        default: return mnet_fail(MNET_E_ARG, "conv: unknown LDS-DMA tile configuration %d", id);
+        case 0: return launch_dma_cfg<256, 256, 4, 4, 2>;
+        case 1: return launch_dma_cfg<256, 128, 4, 2, 3>;
+        case 2: return launch_dma_cfg<128, 256, 2, 4, 3>;
+        case 3: return launch_dma_cfg<64, 256, 1, 8, 3>;
+        case 4: return launch_dma_cfg<128, 512, 2, 8, 2>;
+        case 5: return launch_dma_cfg<64, 512, 1, 8, 2>;
+        case 6: return launch_dma_cfg<256, 256, 2, 4, 2>;          // 8 waves, 128x64 per wave
+        case 7: return launch_dma_cfg<256, 256, 4, 4, 2, 32>;
+        case 8: return launch_dma_cfg<256, 256, 4, 4, 2, 16, 0, false, true>;       // id 0 with the DMA pieces issued between the two half slabs
+        case 9: return launch_dma_cfg<128, 512, 2, 8, 2, 16, 0, false, true>;       // id 4, same
+        case 16: return launch_dma_cfg<256, 256, 2, 4, 2, 16, 0, false, true, true>;   // 8 waves (128x64 per wave), both half slabs' fragments requested up
+                                                                                    // front (the second half's LDS reads run under the first half's MFMAs),
+                                                                                    // DMA pieces between the halves: AUTO for cout >= 256
+        case 17: return launch_dma_cfg<128, 512, 2, 4, 2, 16, 0, false, true, true>;   // the same form of the 128x512 tile (64x128 per wave)
+        case 10: return launch_dma_cfg<128, 128, 2, 4, 4>;          // small launches: twice the workgroups of ids 1 / 2, 3 slabs in flight
+        case 11: return launch_dma_cfg<256, 256, 4, 4, 2, 16, 4>;  // DIAGNOSTIC: all tiles store over tile 0; stamps after tile 0
+        case 12: return launch_dma_cfg<256, 256, 4, 4, 2, 16, 5>;  // DIAGNOSTIC: no output stores; stamps after tile 0
+        case 13: return launch_dma_cfg<256, 256, 4, 4, 2, 16, 3>;  // DIAGNOSTIC: per-tile time stamps written over the output
+        case 14: return launch_dma_cfg<256, 256, 4, 4, 2, 16, 1>;  // DIAGNOSTIC: activations read from a 256 KiB window
+        case 15: return launch_dma_cfg<256, 256, 4, 4, 2, 16, 2>;  // DIAGNOSTIC: no DMA after a tile's first k-slab
+        default: return no_form("conv: unknown LDS-DMA tile configuration %d", id);
     }
 }
 
-int conv_dma_pick(const ConvArgs& a) {
-    const bool big = a.npix >= 256 * 256;
-    static const int env_big256 = [] { const char* e = getenv("MNET_DMA_CFG_BIG256"); return e ? atoi(e) : 16; }();   // A/B knob
-    // a launch that would leave a quarter or more of the CUs without a tile (a strip at a time: 4096-16384 pixels) takes the
-    // 128x128 tile instead: twice the workgroups (same k order, same bits)
-    const long long t128 = (a.npix + 127) / 128, t256 = (a.npix + 255) / 256;
-    // split-half (fp16x3): the 8-wave forms of the two big tiles.  Three products per slab need a third set of operand
-    // fragments live: the 16-wave tiles (128 VGPRs per wave) spill (59 / 133 VGPRs) and park 62 % of their wave cycles in
-    // s_waitcnt / barriers; with 2 waves per SIMD and 256 VGPRs the same tiles run 19 % faster (measured: 446 vs 372 TFLOP/s
-    // algorithmic on the 256x256 tile, B = 64) — the opposite of the f16 kernel, where the 16-wave form wins by 6 %.
-    static const int env_x3_16w = [] { const char* e = getenv("MNET_X3_16WAVE"); return e ? atoi(e) : 0; }();                 // A/B knob
-    // ids 8 / 9 = ids 6 / 7 with the next slab's DMA pieces issued after the first of the three multiply groups instead of right
-    // after the barrier: +5.6 % / +3.7 % (438 vs 414 TFLOP/s on the 256x256 tile, same box, B = 64).  (Two insertion points —
-    // weights after the first group, activations after the second — keep the DMA state live across all three groups: 167-275
-    // VGPRs spill with scratch reloads inside the k-loop, 227 TFLOP/s.)
-    static const int env_x3_128 = [] { const char* e = getenv("MNET_X3_CFG128"); return e ? atoi(e) : 9; }();                 // A/B knobs
-    // id 11 = id 8 with the LDS reads placed by scheduling hints (all hi fragments up front, the lo activation fragments under the
-    // first group's MFMAs): 472 vs 465 TFLOP/s (+1.5 %); the 128x512 tile does not gain (id 12 stays an A/B knob)
-    static const int env_x3_256 = [] { const char* e = getenv("MNET_X3_CFG256"); return e ? atoi(e) : 11; }();
-    if (a.split == 2) {
-        // A/B knobs.  id 15 (round 4) = id 6 with the slab loop software-pipelined across the barrier: +0.5 ... +3.8 % over id 11 (= id 6 with the LDS reads
-        // placed by scheduling hints) on the four shapes that carry the step, +1.2 % end to end, same bytes (profiles/r4g_*)
-        // id 16 (round 6) = the same tile with ONE wave per SIMD (conv_dma_w4.hip: 4 waves x 128x128 outputs, accumulators in a[0:255]): +1.3 ... +2.5 % over id 15 on the
-        // shapes that carry the step at a 2-5 % higher shader clock for the same package power, same bytes (profiles/r6i_*); it writes GroupNorm sums itself
-        static const int env_mx_256 = [] { const char* e = getenv("MNET_MX_CFG256"); return e ? atoi(e) : 16; }();
-        static const int env_mx_128 = [] { const char* e = getenv("MNET_MX_CFG128"); return e ? atoi(e) : 8; }();
-        // (launches that write GroupNorm partial sums: id 15 runs its SGN build, conv_dma_swp_gn.hip; the software-pipelined 128x512 tile has no such build → its lock-step form 8)
-        static const int env_gn_lockstep = [] { const char* e = getenv("MNET_GN_LOCKSTEP"); return e ? atoi(e) : 0; }();     // A/B knob: 1 = round-5's first form (id 15 → 11)
-        const auto no_swp = [&](int id) { return a.gn_partial ? (id == 15 && env_gn_lockstep ? 11 : (id == 9 ? 8 : id)) : id; };
-        if (a.cout >= 256) return big ? no_swp(env_mx_256) : (t128 * ((a.cout + 255) / 256) < 200 ? 10 : 1);
-        if (a.cout >= 128) return big ? no_swp(env_mx_128) : (t256 * ((a.cout + 127) / 128) < 200 ? 10 : 2);
-        static const int env_mx_64 = [] { const char* e = getenv("MNET_MX_CFG64"); return e ? atoi(e) : 13; }();       // id 13 = id 5 + hints: 260 vs 251
-        return big ? env_mx_64 : 3;
-    }
-    if (a.split && big && a.cout >= 128) return env_x3_16w ? (a.cout >= 256 ? 0 : 4) : (a.cout >= 256 ? env_x3_256 : env_x3_128);
-    // f16 big tiles: ids 8 / 9 = ids 0 / 4 with the next slab's DMA pieces issued between the two half slabs instead of right after
-    // the barrier (+2.8 % on the 256x256 tile: 1140 vs 1109 TFLOP/s, B = 64; same MFMA sequence, same bits).  id 16 = the 8-wave
-    // 256x256 tile with both half slabs' fragments requested up front as well (the second half's LDS reads run under the first
-    // half's MFMAs — it has the registers for it): 1176-1188 vs 1148-1166 TFLOP/s for id 8, 1064 for the plain 8-wave id 6 → AUTO
-    // for cout >= 256; the same form of the 128x512 tile (id 17) is slower than id 9 (22.3 vs 18.3 ms per step)
-    static const int env_big128 = [] { const char* e = getenv("MNET_DMA_CFG_BIG128"); return e ? atoi(e) : 9; }();   // A/B knob
-    if (a.cout >= 256) return big ? env_big256 : (t128 * ((a.cout + 255) / 256) < 200 ? 10 : 1);
-    if (a.cout >= 128) return big ? env_big128 : (t256 * ((a.cout + 127) / 128) < 200 ? 10 : 2);
-    return big ? 5 : 3;
-}
-
-int launch_conv_dma(const ConvArgs& a, hipStream_t st, int cfg) {
-    int id = cfg >= 0 ? cfg : conv_dma_pick(a);
-    // launches that write GroupNorm partial sums: the software-pipelined tiles of THIS translation unit are built without that block (dma_epilogue_mx<..., GN = false>);
-    // id 15 has a build with it in conv_dma_swp_gn.hip, id 9 hands over to its lock-step form 8 (the same tile shape, the same MFMA sequence, the same bytes)
-    if (a.gn_partial && a.split == 2) {       // (id 16, the one-wave-per-SIMD tile, writes the sums itself)
-        if (id == 15) return launch_dma_swp_gn(a, st);
-        if (id == 9) id = 8;
-    }
-    return launch_dma_id(id, a, st);
-}
-
-// eligibility of the LDS-DMA path (see header comment); the caller falls back to the register-staged kernel
-bool conv_dma_eligible(const ConvArgs& a, int dtype) {
-    if ((dtype != MNET_F16 && dtype != MNET_F16X2 && dtype != MNET_F16M) || a.in_scale || a.act > MNET_ACT_LRELU_SQRT2) return false;
-    if (dtype != MNET_F16 && a.cout % 32 != 0) return false;          // (a.c0 / a.cin / a.K are physical here: f16 view, doubled)
-    if (a.cin % 64 != 0 || a.c0 % 64 != 0 || a.cout < 64 || a.cout % 8 != 0 || a.kh * a.kw > 32 || a.kh > 8 || a.kw > 8) return false;
-    // 31-bit buffer offsets: a pixel tile may touch ceil(256/howo)+1 images
-    const long long imgs = 512 / a.howo + 2;   // largest pixel tile is 512
-    const long long per_img = (long long)a.h * a.w * (a.c0 > a.c1 ? a.c0 : a.c1) * 2;
-    if (per_img * imgs >= 0x7fffffffLL) return false;
-    if ((long long)a.h * a.w * imgs >= (1ll << 23) || (a.c0 > a.c1 ? a.c0 : a.c1) * 2 >= (1 << 23)) return false;   // 24-bit signed multiply of (pixel, bytes per pixel)
-    if ((long long)256 * a.K * 2 >= 0x40000000LL) return false;
-    if ((long long)a.cout * a.K * 2 >= 0x7fffffffLL) return false;
-    return true;
+int launch_conv_dma(const ConvArgs& a, hipStream_t st, int id) {
+    const DmaLaunchFn launch = conv_dma_launcher(id, a);
+    return launch ? launch(a, st) : MNET_E_ARG;
 }
 #endif  // MNET_DMA_SWP_GN_TU

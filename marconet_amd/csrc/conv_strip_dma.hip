@@ -388,37 +388,6 @@ static int launch_strip_cfg(const ConvArgs& a, hipStream_t st) {
     return MNET_OK;
 }
 
-// tile configuration the strip kernel would use for this launch (0: 256x256, 16 waves; 1: 64x512, 8 waves), or -1 when
-// the launch is not eligible: 3x3 / stride 1 / pad 1, one source tensor, whole-row (or whole-segment) tiles that never
-// straddle an image, and everything conv_dma_eligible already requires
-int conv_strip_pick(const ConvArgs& a, int dtype, bool explicit_request) {
-    // 256x256 tiles: measured neutral (89.8 + 5.1 vs 94.5 ms per bench step; 128-VGPR budget of its 16 waves is exhausted,
-    // 20 spills) — AUTO keeps the per-tap kernel there unless MNET_STRIP_256=1; the 64x512 tile (8 waves) gains 20 %.
-    static const bool auto256 = [] { const char* e = getenv("MNET_STRIP_256"); return e && atoi(e) != 0; }();
-    if ((dtype != MNET_F16 && dtype != MNET_F16X2 && dtype != MNET_F16M) || !conv_dma_eligible(a, dtype)) return -1;
-    // fp16+8, cout >= 256: the 8-wave 256x256 strip tile (round 4) — explicit request or MNET_MX_STRIP256=1 (A/B knob)
-    static const bool mx256 = [] { const char* e = getenv("MNET_MX_STRIP256"); return e && atoi(e) != 0; }();
-    const bool mx_big = dtype == MNET_F16M && a.cout >= 256 && a.cout % 256 == 0 && (explicit_request || mx256);
-    if (dtype != MNET_F16 && a.cout >= 128 && !mx_big) return -1;        // split-half: the 64x512 tile only (the big tiles take the 8-wave per-tap forms)
-    if (a.cout >= 256 && !explicit_request && !auto256 && !mx_big) return -1;
-    if (a.kh != 3 || a.kw != 3 || a.sh != 1 || a.sw != 1 || a.ph != 1 || a.pw != 1 || a.c1 != 0 || a.x1) return -1;
-    if (a.ho != a.h || a.wo != a.w) return -1;
-    int cfg, bp;
-    if (a.cout >= 256) { cfg = 0; bp = 256; }
-    else if (a.cout < 128) { cfg = 1; bp = 512; }
-    else {                                                     // cout 128: a 512-pixel strip pair + weights exceed the LDS → 128x256
-        static const bool s128 = [] { const char* e = getenv("MNET_STRIP_128"); return e && atoi(e) != 0; }();   // A/B knob
-        if (!explicit_request && !s128) return -1;
-        cfg = 2; bp = 256;
-    }
-    if (a.npix < 256 * 256 || a.npix % bp != 0) return -1;
-    const int minw = bp == 256 ? 16 : 32;
-    if (a.w < minw || a.w % 16 != 0) return -1;
-    if (a.w < bp ? (bp % a.w != 0 || a.howo % bp != 0) : (a.w % bp != 0)) return -1;
-    if ((long long)a.h * a.w * a.c0 * 2 >= 0x7fffffffLL) return -1;       // one image per buffer descriptor
-    return cfg;
-}
-
 int launch_conv_strip(const ConvArgs& a, hipStream_t st, int cfg) {
     if (a.split == 2) {
         if (cfg == 1) return launch_strip_cfg<64, 512, 1, 8, true, true>(a, st);

@@ -15,7 +15,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import ops
 from .glyphs import GlyphTables
 from .packing import (PRECISIONS, SPLIT_DTYPE, PackCache, is_split, default_precision, equal_linear_scale, pack_conv_weight,
                       pack_linear_weight, pack_vec, pack_wsq, padded_cout, rgb_pad, torch_dtype)
@@ -549,7 +549,7 @@ class TSPSRNet(nn.Module, _Precision):
         type / kernel keeps that pass (mnet_groupnorm_affine)."""
         L = pk[name]
         n, h, w, _ = x.shape
-        if ops.can_emit_gn_partial(x, x1, L["cout"], L["stride"], h, w):
+        if ops.can_emit_gn_partial(x, x1, L["cout"], L["stride"], h, w, act):
             # (can_emit_gn_partial has asked the planner: this launch goes to a kernel whose epilogue writes the sums; any error below is a real one)
             part = ops.gn_partial_buffer(n, h, w, L["cout"], x.device)
             y = self._c(pk, name, x, act, x1=x1, valid_w=valid_w, gn_partial=part)
@@ -581,7 +581,7 @@ class TSPSRNet(nn.Module, _Precision):
             L = pk[name + ".conv2+out"]       # the 1x1 skip conv as extra K of conv2: no separate launch, no residual read in the epilogue
             # only the LDS-DMA kernels walk a second source at one tap: ask the planner (cached per shape) whether this launch is theirs; one they do
             # not take runs the two-launch form below
-            if ops.plan_is_lds_dma(ops.conv_plan(h, L["cout"], 3, 3, (1, 1), (1, 1), x1=x, algo=_lib.ALGO_FLAG_X1_CENTER)):
+            if ops.plan_is_lds_dma(ops.conv_plan(h, L["cout"], 3, 3, (1, 1), (1, 1), x1=x, x1_center=True)):
                 return ops.conv2d(h, L["w"], L["cout"], 3, 3, (1, 1), (1, 1), x1=x, bias=L["b"], valid_w=valid_w, x1_center=True)
         if (name + ".conv_out") in pk:
             co = pk[name + ".conv_out"]

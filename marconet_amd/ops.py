@@ -48,6 +48,10 @@ def _p(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def _addr(t):
+    return None if t is None else t.data_ptr()
+
+
 def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -133,6 +137,34 @@ class _Stats:
 stats = _Stats()
 
 
+def _out_size(h, w, kh, kw, stride, pad):
+    return (h + 2 * pad[0] - kh) // stride[0] + 1, (w + 2 * pad[1] - kw) // stride[1] + 1
+
+
+def _conv_desc(x0, x1, cout, kh, kw, stride, pad, wgt, y, in_scale=None, in_shift=None, in_swish=False, valid_w=None, out_scale=None,
+               bias=None, residual=None, res_mod=0, act=ACT_NONE, post_scale=None, gn_partial=None):
+    """mnet_conv_desc of ``conv2d(x0, …)`` (and of ``conv_plan``'s question about it): the sources as tensors, every other buffer as a
+    device address or None"""
+    n, h, w, c0 = x0.shape
+    d = ConvDesc()
+    d.dtype = _dt(x0)
+    d.x0, d.c0 = x0.data_ptr(), c0
+    d.x1, d.c1 = (None, 0) if x1 is None else (x1.data_ptr(), x1.shape[3])
+    d.n, d.h, d.w = n, h, w
+    d.wgt = wgt
+    d.cout, d.kh, d.kw = cout, kh, kw
+    d.stride_h, d.stride_w, d.pad_h, d.pad_w = stride[0], stride[1], pad[0], pad[1]
+    d.ho, d.wo = _out_size(h, w, kh, kw, stride, pad)
+    d.in_scale, d.in_shift, d.in_swish = in_scale, in_shift, 1 if in_swish else 0
+    d.valid_w = valid_w
+    d.out_scale, d.bias, d.residual, d.res_mod = out_scale, bias, residual, res_mod
+    d.act = act
+    d.post_scale = post_scale
+    d.y = y
+    d.gn_partial = gn_partial
+    return d
+
+
 @_plumbing
 def conv2d(x0, wgt, cout, kh=1, kw=1, stride=(1, 1), pad=(0, 0), x1=None, in_scale=None, in_shift=None,
            in_swish=False, valid_w=None, out_scale=None, bias=None, residual=None, res_mod=0, act=ACT_NONE,
@@ -152,38 +184,18 @@ def conv2d(x0, wgt, cout, kh=1, kw=1, stride=(1, 1), pad=(0, 0), x1=None, in_sca
     if wgt.dtype != x0.dtype or wgt.numel() != need:
         raise RuntimeError("conv2d: weight dtype/shape mismatch (%s %s vs cout=%d k=%dx%d cin=%d)"
                            % (wgt.dtype, tuple(wgt.shape), cout, kh, kw, c0 + c1))
-    ho = (h + 2 * pad[0] - kh) // stride[0] + 1
-    wo = (w + 2 * pad[1] - kw) // stride[1] + 1
+    ho, wo = _out_size(h, w, kh, kw, stride, pad)
     if out is None:
         out = new_tensor((n, ho, wo, cout), x0.dtype, x0.device)
     elif tuple(out.shape) != (n, ho, wo, cout) or out.dtype != x0.dtype:
         raise RuntimeError("conv2d: out is %s %s, expected %s %s" % (tuple(out.shape), out.dtype, (n, ho, wo, cout), x0.dtype))
-    d = ConvDesc()
-    d.dtype = _dt(x0)
-    d.x0, d.c0 = x0.data_ptr(), c0
-    d.x1, d.c1 = (None if x1 is None else x1.data_ptr()), c1
-    d.n, d.h, d.w = n, h, w
-    d.wgt = wgt.data_ptr()
-    d.cout, d.kh, d.kw = cout, kh, kw
-    d.stride_h, d.stride_w, d.pad_h, d.pad_w = stride[0], stride[1], pad[0], pad[1]
-    d.ho, d.wo = ho, wo
-    d.in_scale = None if in_scale is None else in_scale.data_ptr()
-    d.in_shift = None if in_shift is None else in_shift.data_ptr()
-    d.in_swish = 1 if in_swish else 0
-    d.valid_w = None if valid_w is None else valid_w.data_ptr()
-    d.out_scale = None if out_scale is None else out_scale.data_ptr()
-    d.bias = None if bias is None else bias.data_ptr()
-    d.residual = None if residual is None else residual.data_ptr()
-    d.res_mod = res_mod
-    d.act = act
-    d.post_scale = None if post_scale is None else post_scale.data_ptr()
-    d.y = out.data_ptr()
-    d.gn_partial = None
     if gn_partial is not None:
         _need_cuda(gn_partial)
         if gn_partial.dtype != torch.float32 or gn_partial.numel() != (n * ho * wo // 32) * (cout // 32) * 2:
             raise RuntimeError("conv2d: gn_partial must be fp32 [n*ho*wo/32, cout/32, 2]")
-        d.gn_partial = gn_partial.data_ptr()
+    d = _conv_desc(x0, x1, cout, kh, kw, stride, pad, wgt=wgt.data_ptr(), y=out.data_ptr(), in_scale=_addr(in_scale), in_shift=_addr(in_shift),
+                   in_swish=in_swish, valid_w=_addr(valid_w), out_scale=_addr(out_scale), bias=_addr(bias), residual=_addr(residual),
+                   res_mod=res_mod, act=act, post_scale=_addr(post_scale), gn_partial=_addr(gn_partial))
     for t, nm in ((in_scale, "in_scale"), (in_shift, "in_shift"), (out_scale, "out_scale"), (bias, "bias"),
                   (post_scale, "post_scale")):
         if t is not None and t.dtype != torch.float32:
@@ -299,29 +311,34 @@ def gn_partial_buffer(n, h, w, c, device):
 
 
 _PLAN_CACHE = {}
+_PLAN_ADDR = 1 << 20      # a buffer the launch will pass but the question has not allocated: the planner checks its presence and alignment, never what is behind it
 
 
-def conv_plan(x0, cout, kh=1, kw=1, stride=(1, 1), pad=(0, 0), x1=None, algo=0):
-    """mnet_conv2d_plan for the launch geometry of ``conv2d(x0, …, x1=…)``: the kernel ``algo`` resolves to (_lib.ALGO_REG_STAGED, ALGO_SKINNY,
-    ALGO_DMA_CFG0 + id, ALGO_STRIP_CFG0 + id, ALGO_DMA_CFG16 + id), or a negative MNET_E_* when the planner refuses it.  Nothing is launched; the
-    answer depends on geometry and storage type only and is cached per (dtype, shape, filter, algo) — the callers that choose between two forms
-    of a layer ask this instead of launching and parsing an error message."""
+def _align(t):
+    """the alignment of a source that the planner's answer can depend on (16 / 128 bytes)"""
+    return None if t is None else (128 if t.data_ptr() % 128 == 0 else 16 if t.data_ptr() % 16 == 0 else 0)
+
+
+def conv_plan(x0, cout, kh=1, kw=1, stride=(1, 1), pad=(0, 0), x1=None, act=ACT_NONE, in_scale=False, residual=False, out_scale=False,
+              gn_partial=False, x1_center=False, algo=0):
+    """mnet_conv2d_plan for ``conv2d(x0, …, x1=…, act=…)``: the kernel ``algo`` resolves to (_lib.ALGO_REG_STAGED, ALGO_SKINNY, ALGO_DMA_CFG0 + id,
+    ALGO_STRIP_CFG0 + id, ALGO_DMA_CFG16 + id), or a negative MNET_E_* when the planner refuses it.  The flags say which of in_scale, residual,
+    out_scale / post_scale and gn_partial the launch will pass, and whether it sets x1_center.  Nothing is launched; the callers that choose
+    between two forms of a layer ask this instead of launching and parsing an error message.  Accepted answers are cached per everything they
+    depend on (storage type, shape, filter, flags, algo and the alignment of x0 / x1); refusals are not."""
     n, h, w, c0 = x0.shape
-    c1 = 0 if x1 is None else x1.shape[3]
-    key = (_dt(x0), n, h, w, c0, c1, cout, kh, kw, tuple(stride), tuple(pad), algo)
+    if x1_center:
+        algo |= _lib.ALGO_FLAG_X1_CENTER
+    key = (_dt(x0), n, h, w, c0, None if x1 is None else x1.shape[3], _align(x0), _align(x1), cout, kh, kw, tuple(stride), tuple(pad), act,
+           bool(in_scale), bool(residual), bool(out_scale), bool(gn_partial), algo)
     k = _PLAN_CACHE.get(key)
     if k is None:
-        lib = _lib.load()
-        d = ConvDesc()
-        d.dtype = key[0]
-        d.x0, d.c0 = x0.data_ptr(), c0
-        d.x1, d.c1 = (None if x1 is None else x1.data_ptr()), c1
-        d.n, d.h, d.w = n, h, w
-        d.wgt = d.y = x0.data_ptr()            # (the planner checks presence and alignment of the pointers, nothing behind them)
-        d.cout, d.kh, d.kw = cout, kh, kw
-        d.stride_h, d.stride_w, d.pad_h, d.pad_w = stride[0], stride[1], pad[0], pad[1]
-        d.ho, d.wo = (h + 2 * pad[0] - kh) // stride[0] + 1, (w + 2 * pad[1] - kw) // stride[1] + 1
-        k = _PLAN_CACHE[key] = int(lib.mnet_conv2d_plan(ctypes.byref(d), algo))
+        addr = [_PLAN_ADDR if present else None for present in (in_scale, residual, out_scale, gn_partial)]
+        d = _conv_desc(x0, x1, cout, kh, kw, stride, pad, wgt=_PLAN_ADDR, y=_PLAN_ADDR, in_scale=addr[0], residual=addr[1], out_scale=addr[2],
+                       act=act, gn_partial=addr[3])
+        k = int(_lib.load().mnet_conv2d_plan(ctypes.byref(d), algo))
+        if k >= 0:
+            _PLAN_CACHE[key] = k
     return k
 
 
@@ -330,14 +347,14 @@ def plan_is_lds_dma(k):
     return _lib.ALGO_DMA_CFG0 <= k < _lib.ALGO_STRIP_CFG0 or k >= _lib.ALGO_DMA_CFG16
 
 
-def can_emit_gn_partial(x0, x1, cout, stride, ho, wo):
-    """the launches whose epilogue can write GroupNorm partial sums (mnet_conv_desc.gn_partial): fp16+8 storage, and a launch the planner gives to the
-    LDS-DMA / strip kernels (3x3 'same' geometry of this network's GroupNorm producers)"""
+def can_emit_gn_partial(x0, x1, cout, stride, ho, wo, act=ACT_NONE):
+    """the launches whose epilogue can write GroupNorm partial sums (mnet_conv_desc.gn_partial): fp16+8 storage, and a launch with gn_partial the
+    planner accepts (it gives those to the LDS-DMA / strip kernels; 3x3 'same' geometry of this network's GroupNorm producers)"""
     c = x0.shape[3] + (0 if x1 is None else x1.shape[3])
     if not (x0.dtype == MX_DTYPE and tuple(stride) == (1, 1) and cout >= 64 and cout % 32 == 0 and c % 32 == 0 and x0.shape[3] % 32 == 0
             and (ho * wo) % 32 == 0 and not _NO_EPILOGUE_GN):
         return False
-    return conv_plan(x0, cout, 3, 3, stride, (1, 1), x1=x1) >= _lib.ALGO_DMA_CFG0
+    return conv_plan(x0, cout, 3, 3, stride, (1, 1), x1=x1, act=act, gn_partial=True) >= _lib.ALGO_DMA_CFG0
 
 
 def groupnorm_affine_from_partial(partial, n, h, w, c, gamma, beta, eps=1e-6, valid_w=None):

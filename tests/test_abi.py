@@ -33,6 +33,32 @@ def test_library_exports_every_declared_symbol():
     assert lib.mnet_abi_version() == _lib.ABI_VERSION == 4
 
 
+def test_conv_plan_asks_about_the_launch_it_will_make():
+    """ops.conv_plan builds conv2d's descriptor (no device needed: only shapes, flags and the alignment of the sources enter the answer): the
+    activation counts, and an answer for a misaligned view is neither cached nor served for an aligned tensor of the same shape"""
+    from marconet_amd import _lib, ops
+    from marconet_amd.packing import MX_DTYPE
+    x = torch.empty((64, 32, 32, 64), dtype=torch.float16)
+    assert ops.conv_plan(x, 256, 3, 3, (1, 1), (1, 1)) == _lib.ALGO_DMA_CFG16
+    assert ops.conv_plan(x, 256, 3, 3, (1, 1), (1, 1), act=ops.ACT_TANH) == _lib.ALGO_REG_STAGED          # no tanh in the LDS-DMA epilogue
+    assert ops.conv_plan(x, 256, 3, 3, (1, 1), (1, 1), in_scale=True) == _lib.ALGO_REG_STAGED              # input transform
+    shape = (64, 32, 32, 64)
+    numel = int(np.prod(shape))
+    buf = torch.empty(numel + 64, dtype=MX_DTYPE)
+    off = (-buf.data_ptr() % 128) // 4
+    misaligned, aligned = buf[off + 4:off + 4 + numel].view(shape), buf[off:off + numel].view(shape)      # 16- / 128-byte aligned
+    for gn in (False, True):
+        assert ops.conv_plan(misaligned, 256, 3, 3, (1, 1), (1, 1), gn_partial=gn) == -2                   # fp16+8 needs 128-byte alignment
+        assert ops.conv_plan(aligned, 256, 3, 3, (1, 1), (1, 1), gn_partial=gn) == _lib.ALGO_DMA_CFG16
+        assert ops.conv_plan(misaligned, 256, 3, 3, (1, 1), (1, 1), gn_partial=gn) == -2
+    assert ops.conv_plan(aligned, 256, 3, 3, (1, 1), (1, 1), act=ops.ACT_RELU) == _lib.ALGO_DMA_CFG0 + 15   # handed over from id 16
+    assert ops.conv_plan(aligned, 128, 3, 3, (1, 1), (1, 1), gn_partial=True, algo=_lib.ALGO_DMA_CFG0 + 9) == _lib.ALGO_DMA_CFG0 + 8
+    assert ops.conv_plan(aligned, 256, 3, 3, (2, 2), (1, 1), gn_partial=True) < 0                           # gn_partial needs stride 1
+    assert ops.plan_is_lds_dma(ops.conv_plan(x, 256, 3, 3, (1, 1), (1, 1), x1=x, x1_center=True))
+    xf = torch.empty(shape, dtype=torch.float32)
+    assert ops.conv_plan(xf, 256, 3, 3, (1, 1), (1, 1), x1=xf, x1_center=True) == -1                       # LDS-DMA kernels only
+
+
 def test_conv_desc_layout_matches_c():
     """compile a tiny C program against the header and compare sizeof/offsetof with the ctypes mirror"""
     from marconet_amd._lib import ConvDesc
@@ -105,6 +131,29 @@ def test_argument_validation_without_device():
     assert lib.mnet_conv2d_plan(ctypes.byref(d2), _lib.ALGO_LDS_DMA) == -1
     d2.c0 = 64; d2.dtype = 0
     assert lib.mnet_conv2d_plan(ctypes.byref(d2), _lib.ALGO_AUTO) == _lib.ALGO_REG_STAGED          # fp32
+    # the planner names the kernel that runs: hand-overs between LDS-DMA builds, and ids with no build for the storage type refused
+    d4 = _lib.ConvDesc()
+    d4.dtype = 3; d4.x0 = d4.wgt = d4.y = 128; d4.n = 64; d4.h = d4.ho = 32; d4.w = d4.wo = 32       # fp16+8, 65536 pixels
+    d4.c0 = 64; d4.cout = 256; d4.kh = d4.kw = 3; d4.stride_h = d4.stride_w = 1; d4.pad_h = d4.pad_w = 1
+    assert lib.mnet_conv2d_plan(ctypes.byref(d4), _lib.ALGO_DMA_CFG16) == _lib.ALGO_DMA_CFG16      # the one-wave-per-SIMD tile (id 16)
+    d4.act = 1                                                                                     # RELU: no arm in id 16's epilogue
+    assert lib.mnet_conv2d_plan(ctypes.byref(d4), _lib.ALGO_DMA_CFG16) == _lib.ALGO_DMA_CFG0 + 15
+    assert lib.mnet_conv2d_plan(ctypes.byref(d4), _lib.ALGO_AUTO) == _lib.ALGO_DMA_CFG0 + 15
+    d4.act = 0; d4.n = 73; d4.h = d4.ho = d4.w = d4.wo = 30                                        # ho * wo = 900, not a multiple of 32
+    assert lib.mnet_conv2d_plan(ctypes.byref(d4), _lib.ALGO_DMA_CFG16) == _lib.ALGO_DMA_CFG0 + 15
+    d4.n = 64; d4.h = d4.ho = d4.w = d4.wo = 32; d4.c0 = 1856                                      # 9 * 3712 / 64 = 522 k-slabs > 512
+    assert lib.mnet_conv2d_plan(ctypes.byref(d4), _lib.ALGO_DMA_CFG16) == _lib.ALGO_DMA_CFG0 + 15
+    d4.c0 = 64; d4.cout = 128; d4.gn_partial = 128                                                 # GroupNorm sums: id 9 has no build with them
+    assert lib.mnet_conv2d_plan(ctypes.byref(d4), _lib.ALGO_DMA_CFG0 + 9) == _lib.ALGO_DMA_CFG0 + 8
+    assert lib.mnet_conv2d_plan(ctypes.byref(d4), _lib.ALGO_DMA_CFG0 + 15) == _lib.ALGO_DMA_CFG0 + 15  # (id 15 has: a build, not an id)
+    d4.gn_partial = None
+    assert lib.mnet_conv2d_plan(ctypes.byref(d4), _lib.ALGO_DMA_CFG0 + 9) == _lib.ALGO_DMA_CFG0 + 9
+    assert lib.mnet_conv2d_plan(ctypes.byref(d4), _lib.ALGO_DMA_CFG0 + 14) == -1 and b"diagnostic" in lib.mnet_last_error()
+    d4.dtype = 2                                                                                   # split-half: no id 13
+    assert lib.mnet_conv2d_plan(ctypes.byref(d4), _lib.ALGO_DMA_CFG0 + 13) == -1 and b"split-half" in lib.mnet_last_error()
+    d4.dtype = 1; d4.x0 = d4.wgt = d4.y = 16                                                       # f16: ids 11-15 are diagnostic builds
+    assert lib.mnet_conv2d_plan(ctypes.byref(d4), _lib.ALGO_DMA_CFG0 + 12) == -1 and b"diagnostic" in lib.mnet_last_error()
+    assert lib.mnet_conv2d_plan(ctypes.byref(d4), _lib.ALGO_DMA_CFG16 + 4) == -1 and b"unknown" in lib.mnet_last_error()
     # fp32 1x1 over a few tokens (the TextViT linears of a small batch) → the skinny kernel; above 512 pixels the general one
     d3 = _lib.ConvDesc()
     d3.dtype = 0; d3.x0 = 16; d3.wgt = 16; d3.y = 16; d3.n = d3.h = d3.ho = 1; d3.w = d3.wo = 64

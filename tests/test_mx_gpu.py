@@ -692,7 +692,7 @@ def test_one_wave_per_simd_tile_groupnorm_sums(case):
 
 def test_one_wave_per_simd_tile_scale_rows_of_maps_that_are_not_multiples_of_32_pixels():
     """w4_epilogue stages out_scale / post_scale through the LDS one float per lane, which needs a 32-pixel fragment inside ONE image (ho * wo % 32 == 0); a request for
-    id 16 on any other map is handed to the 8-wave tile by the launcher (as is an activation other than identity / LeakyReLU) — same bytes as the lock-step tile either
+    id 16 on any other map is handed to the 8-wave tile by the planner (as is an activation other than identity / LeakyReLU) — same bytes as the lock-step tile either
     way (fragments straddling images, a pixel tail, ragged widths; the last shape runs on id 16 itself)"""
     ops = _ops()
     for (n, h, w) in ((20, 10, 10), (7, 12, 20), (9, 16, 16)):          # 100 / 240 / 256 pixels per image
@@ -704,3 +704,29 @@ def test_one_wave_per_simd_tile_scale_rows_of_maps_that_are_not_multiples_of_32_
         vw = torch.tensor([w - (i % 3) for i in range(n)], dtype=torch.int32, device=DEV)
         outs = [ops.conv2d(x, wp, cout, 3, 3, (1, 1), (1, 1), out_scale=osc, post_scale=psc, bias=bias, act=3, valid_w=vw, algo=_tile(i)).cpu().view(torch.uint8) for i in (6, W4)]
         assert torch.equal(outs[0], outs[1]), (n, h, w)
+
+
+@pytest.mark.parametrize("case", [
+    # cout, cin, (n, h, w), act, GroupNorm sums, pinned id, the id the planner names
+    (256, 64, (4, 32, 32), 1, False, W4, 15),       # RELU: no arm in id 16's epilogue
+    (256, 64, (20, 10, 10), 3, False, W4, 15),      # ho * wo = 100, not a multiple of 32
+    (256, 1856, (1, 8, 32), 3, False, W4, 15),      # 522 k-slabs per tile, id 16's slab table holds 512
+    (256, 1856, (1, 8, 32), 3, True, W4, 15),       # the same with GroupNorm sums (id 15's build with the sums block)
+    (128, 64, (4, 32, 32), 2, True, 9, 8),          # GroupNorm sums: the software-pipelined 128x512 tile has no build with them
+])
+def test_planner_names_the_kernel_a_handed_over_request_runs(case):
+    """mnet_conv2d_plan answers a pinned request that another build takes over with that build's id: the request and a launch pinned to the
+    named id give the same bytes (output and GroupNorm sums)"""
+    ops = _ops()
+    cout, cin, (n, h, w), act, gn, pinned, named = case
+    x = _to_mx(_rnd((n, cin, h, w), 211))
+    wp = _pack_w(_rnd((cout, cin, 3, 3), 212, 1.0 / math.sqrt(cin * 9)))
+    bias = _rnd((cout,), 213, 0.3).to(DEV)
+    assert ops.conv_plan(x, cout, 3, 3, (1, 1), (1, 1), act=act, gn_partial=gn, algo=_tile(pinned)) == _tile(named)
+    got = []
+    for i in (pinned, named):
+        part = ops.gn_partial_buffer(n, h, w, cout, DEV) if gn else None
+        y = ops.conv2d(x, wp, cout, 3, 3, (1, 1), (1, 1), bias=bias, act=act, algo=_tile(i), gn_partial=part)
+        torch.cuda.synchronize()
+        got.append([y.cpu().view(torch.uint8)] + ([part.cpu()] if gn else []))
+    assert all(torch.equal(a, b) for a, b in zip(got[0], got[1]))
