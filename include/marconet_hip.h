@@ -136,7 +136,8 @@ int mnet_conv2d_nhwc(const mnet_conv_desc* d, void* stream);
  *      8w (128x64 per wave), id 7 / 8 = 128x512 8w (64x128 / 128x64 per wave), ids 11 / 12 / 13 = ids 6 / 8 / 5 with the LDS reads
  *      placed by scheduling hints; ids 15 / 9 (round 4) = ids 6 / 8 with the slab loop software-pipelined across the slab barrier (the scaled
  *      MFMAs of slab s-1 and one DMA piece of slab s+1 behind each, then the f16 MFMAs of slab s); AUTO takes 15 (cout >= 256) / 8 (cout 128) /
- *      13 (cout 64) for >= 65536 output pixels; every id runs the same MFMA sequence per output (same bytes whatever the launch size selects);
+ *      13 (cout 64) for >= 65536 output pixels; every id runs the same MFMA sequence per output (same bytes whatever the launch size selects,
+ *      signed zeros included: an absent bias adds nothing, so a -0 stays a -0);
  *      id 14: DIAGNOSTIC build (per-phase cycle sums written over the output, tools/slab_phases.py), refused unless MNET_ALLOW_DIAGNOSTIC_KERNELS=1
  *   MNET_F16 ids 11-15 ONLY: diagnostic builds used by tools/wg_timeline.py and tools/conv_bench.py; they produce WRONG results and
  *      are refused (MNET_E_ARG) unless the process sets MNET_ALLOW_DIAGNOSTIC_KERNELS=1 */

@@ -86,7 +86,7 @@ static_assert(FA * FB == NDMA, "one DMA piece behind each scaled MFMA");
 //     out_scale / post_scale windows (rows of the fragment's image) one step ahead;
 //   * the residual block of step t + 1 (7 loads per lane) is requested BEFORE the stores of step t, so the wait in front of step t + 1's arithmetic leaves those stores in flight.
 // The one-float-per-lane form needs the 32 pixels of a fragment in ONE image (ho * wo % 32 == 0) and the arithmetic has the identity / LeakyReLU arms only: the launcher
-// hands every other launch to the 8-wave tile.  Straight-line arithmetic (round 6, last pass): a bias the launch does not have is zeros, a scale vector it does not have is
+// hands every other launch to the 8-wave tile.  Straight-line arithmetic (round 6, last pass): a bias the launch does not have is -0, a scale vector it does not have is
 // ones, 2^-8 rides in the fma with the bias (or in out_scale) — every runtime branch in the step split hipcc's scheduling region and copied the 32 values at its join.
 // ACC::block(fa, px) takes a block's 16 values out of the accumulator file where they are consumed.  `par`: this wave's parameter area (w4::PB bytes).
 // SC / RG: the launch has out_scale or post_scale / a residual or GroupNorm sums.  Four builds of the kernel (launch_conv_dma_w4 picks): a tile without them runs an
@@ -117,7 +117,9 @@ __device__ __forceinline__ void w4_epilogue(const ConvArgs& p_, const ACC& acc, 
     // window sits at float index `lane`; its half's 32 values are the 8 chunks at float index 32 h.  (channels >= cout: any in-range value — those blocks are not stored)
     float* const par_f = reinterpret_cast<float*>(par);
 #pragma unroll
-    for (int b = 0; b < NB; ++b) par_f[b * 64 + lane] = p.bias ? p.bias[min(cob[b] + lane, p.cout - 1)] : 0.f;      // (no bias: zeros — the add below is unconditional)
+    // (no bias: -0, the additive identity — the add below is unconditional, and x + -0 = x keeps a -0 (a negative out_scale times a zero accumulator) as
+    //  dma_epilogue_mx, which skips the add, keeps it; +0 would store +0 there: other bytes)
+    for (int b = 0; b < NB; ++b) par_f[b * 64 + lane] = p.bias ? p.bias[min(cob[b] + lane, p.cout - 1)] : -0.f;
     struct Step { float osc1, psc1; u32x4 rh[4], rl[2]; unsigned re8; int pixb, pix, n_img, vw; };
     auto request = [&](int t, Step& S) __attribute__((always_inline)) {     // addresses + parameter loads of step t (no use of the values here)
         const int px = t / NB, b = t % NB;
