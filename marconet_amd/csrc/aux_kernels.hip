@@ -1106,7 +1106,7 @@ __global__ void __launch_bounds__(256) nonfinite_flag_kernel(const T* __restrict
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0)                  // the tail (< 16 bytes)
-        for (long long i = nv * N; i < n; ++i) { const float f = (float)x[i]; bad |= !(fabsf(f) <= 3.0e38f); }
+        for (long long i = nv * N; i < n; ++i) { const float f = (float)x[i]; bad |= !(fabsf(f) <= 3.402823466e38f); }      // FLT_MAX: finite values above 3.0e38 are finite
     if (bad) *flag = 1;
 }
 
