@@ -53,8 +53,7 @@ class TextContextEncoderV2(nn.Module, _Precision):
         super().__init__()
         self.resnet = resnet45()
         self.transformer = TextEncoder(num_classes=num_classes, dim=512, max_length=16)
-        self.precision = default_precision()
-        self.resnet.precision = self.precision
+        self.set_precision(default_precision())
 
     @staticmethod
     def resnet_precision(precision):
@@ -71,10 +70,9 @@ class TextContextEncoderV2(nn.Module, _Precision):
     def forward(self, lq):
         with torch.no_grad(), ops.on_device(lq):
             rp = self.resnet_precision(self.precision)
-            self.resnet.precision = rp
             dtype = torch_dtype(rp)
             x = ops.nchw_to_nhwc(lq.contiguous().float(), dtype, c_ld=rgb_pad(dtype))
-            feat = self.resnet.forward_nhwc(x)
+            feat = self.resnet.forward_nhwc(x, rp)
             feat = ops.convert(feat, torch.float32)          # the ViT always runs in fp32
             return self.transformer.forward_nhwc(feat)
 
@@ -223,23 +221,28 @@ class TextGenerator(nn.Module):
         return pk
 
     # ------------------------------------------------------------------ forward pieces
-    def _mod(self, L, idx, bcast=0):
-        """this layer's column window of the batched modulation EqualLinear (:283), one row per entry of ``idx`` (None: per style)
-        → (rows, eps_scale, scale_b).  The rows are divided by 2^e (largest magnitude in [0.5, 1): mnet_style_rows), so the modulated
+    @staticmethod
+    def _mod(mod, L, per_glyph=True, bcast=0):
+        """``mod`` = (S, gidx), local to one forward_nhwc call: the batched modulation EqualLinear (:283) of every layer and the
+        glyph→style index (None: ``styles`` holds one row per glyph).  This layer's column window of S, one row per glyph
+        (``per_glyph=False``: per distinct style) → (rows, eps_scale, scale_b).
+        The rows are divided by 2^e (largest magnitude in [0.5, 1): mnet_style_rows), so the modulated
         activations x·s never exceed |x| in the half-precision storage modes; eps_scale = 4^-e makes the demodulation absorb the
         factor exactly, scale_b = 2^e [rows, bcast] undoes it for a conv without demodulation (ToRGB).  Power-of-two factors:
         bit-identical to the un-normalised evaluation (tests/test_modules_gpu.py::test_style_normalisation_is_exact)."""
+        S, idx = mod[0], mod[1] if per_glyph else None
         if _STYLE_NORM:
-            return ops.style_rows(self._S, L["mod_off"], L["cin"], idx, bcast)
-        return ops.gather_rows(self._S, L["mod_off"], L["cin"], idx), None, None
+            return ops.style_rows(S, L["mod_off"], L["cin"], idx, bcast)
+        return ops.gather_rows(S, L["mod_off"], L["cin"], idx), None, None
 
-    def _style(self, L):
+    @classmethod
+    def _style(cls, mod, L):
         """→ (modulation rows per glyph, demodulation table rsqrt(Σ (scale·W·s)² + 1e-8) per glyph (:286))"""
-        s, eps, _ = self._mod(L, self._gidx)
-        if self._gidx is None:
+        s, eps, _ = cls._mod(mod, L)
+        if mod[1] is None:
             return s, ops.demod(s, L["wsq_t"], eps)
-        su, eps_u, _ = self._mod(L, None)                           # demodulation once per distinct style, gathered per glyph
-        return s, ops.gather_rows(ops.demod(su, L["wsq_t"], eps_u), idx=self._gidx)
+        su, eps_u, _ = cls._mod(mod, L, per_glyph=False)            # demodulation once per distinct style, gathered per glyph
+        return s, ops.gather_rows(ops.demod(su, L["wsq_t"], eps_u), idx=mod[1])
 
     @staticmethod
     def _styled(L, x, s, d, premodulated, post=None, out=None):
@@ -249,12 +252,14 @@ class TextGenerator(nn.Module):
         return ops.conv2d(x, L["w"], L["cout"], 3, 3, (1, 1), (1, 1), in_scale=None if premodulated else s,
                           out_scale=d, bias=L["bias"], act=ops.ACT_LRELU_SQRT2, post_scale=post, out=out)
 
-    def _to_rgb(self, L, x, skip):
+    @classmethod
+    def _to_rgb(cls, mod, L, x, skip):
         """ToRGB.forward (:313-321) as ONE streaming kernel: modulated 1x1 conv + bias + up-sampled skip (:318-319) + tanh → fp32 RGB0"""
-        s, _, sb = self._mod(L, self._gidx, bcast=1)
+        s, _, sb = cls._mod(mod, L, bcast=1)
         return ops.torgb(x, L["w"], s, sb, L["bias"], skip)
 
-    def forward_nhwc(self, styles, labels, need_image=True, style_index=None, p64_out=None, p32_out=None, image_precision=None):
+    def forward_nhwc(self, styles, labels, need_image=True, style_index=None, p64_out=None, p32_out=None, image_precision=None,
+                     precision=None):
         """→ (image NHWC fp32 [N,128,128c,4] (RGB0), prior64 NHWC [N,64,64c,256], prior32 NHWC [N,32,32c,512]).
         ``style_index`` (int64 [N], optional): ``styles`` then holds only the DISTINCT style vectors (one per image in
         test_sr.py:183, where every glyph of an image gets the same w) and glyph i uses styles[style_index[i]] — the style
@@ -265,23 +270,24 @@ class TextGenerator(nn.Module):
         but the visualisation image (models/networks.py:148-164; 35 % of the generator's FLOPs) and ``image`` is None.
         ``image_precision`` (batched SR driver only, for an image it drops — its ``return_prior=True`` form keeps the mode's arithmetic): precision mode of the levels BEHIND the two
         prior levels — they feed nothing but the structure image (:161-164), so the driver keeps the reference's work but does not
-        spend SR-grade arithmetic on it; prior64 / prior32 (and hence the SR output) are bit-identical with and without it."""
-        pk = self._cache.get(self, self.precision, self._build)
-        dtype = torch_dtype(self.precision)
-        pk_img = pk if image_precision in (None, self.precision) else self._cache.get(self, image_precision, self._build)
+        spend SR-grade arithmetic on it; prior64 / prior32 (and hence the SR output) are bit-identical with and without it.
+        ``precision``: the mode this call runs in (None: ``self.precision``)."""
+        precision = self.precision if precision is None else precision
+        pk = self._cache.get(self, precision, self._build)
+        dtype = torch_dtype(precision)
+        pk_img = pk if image_precision in (None, precision) else self._cache.get(self, image_precision, self._build)
         lat = ops.pixelnorm(styles)                                            # :170-171
         for w, b in pk["mlp"]:
             lat = ops.linear(lat, w, self.style_dim, bias=b, act=ops.ACT_LRELU_SQRT2)
         # every layer's modulation at once: [styles, Σ cin]; _mod() / _style() take per-layer column windows of it, per glyph
-        self._S = ops.linear(lat, pk["mod_all_w"], pk["mod_total"], bias=pk["mod_all_b"])
-        self._gidx = style_index
-        s, d = self._style(pk["conv1"])
+        mod = (ops.linear(lat, pk["mod_all_w"], pk["mod_total"], bias=pk["mod_all_b"]), style_index)
+        s, d = self._style(mod, pk["conv1"])
         # SelectText (:205-215) with conv1's modulation ·s riding in the gather (the gathered constant has no other reader): conv1 then runs
         # without a modulation prologue, i.e. on the LDS-DMA kernels like every other StyledConv (0.97 -> 0.2 ms per 1024 glyphs, 0.56 -> 0.1 ms
         # for one strip's 16) — `_FUSE_CONV1_MOD = False` keeps the prologue form
         x = ops.embed_gather(pk["emb"], labels, dtype, self.class_num, scale=s if _FUSE_CONV1_MOD else None)
         x = self._styled(pk["conv1"], x, s, d, premodulated=_FUSE_CONV1_MOD)
-        skip = self._to_rgb(pk["rgb1"], x, None) if need_image else None
+        skip = self._to_rgb(mod, pk["rgb1"], x, None) if need_image else None
         p64 = p32 = None
         for lvl in range(len(pk["rgbs"])):
             if not need_image and p64 is not None and p32 is not None:
@@ -294,8 +300,8 @@ class TextGenerator(nn.Module):
                     x = ops.convert(x, up_dtype)                              # (the general case: its own pass)
                 # else: the up-sample below reads the prior level in the mode's storage and writes plain f16 (round 5: no convert pass)
             La, Lb = pkl["convs"][2 * lvl], pkl["convs"][2 * lvl + 1]
-            sa, da = self._style(La)
-            sb, db = self._style(Lb)
+            sa, da = self._style(mod, La)
+            sb, db = self._style(mod, Lb)
             xu = ops.upsample2x(x, scale=sa, out_dtype=up_dtype if up_dtype != x.dtype else None)   # bilinear ×2 (:293) with ·s_a fused
             xa = self._styled(La, xu, sa, da, premodulated=True, post=sb)      # emits x_a·s_b (x_a has no other reader)
             del xu
@@ -303,7 +309,7 @@ class TextGenerator(nn.Module):
             x = self._styled(Lb, xa, sb, db, premodulated=True, out=p64_out if wx == 64 else (p32_out if wx == 32 else None))
             del xa
             if need_image:
-                skip = self._to_rgb(pk["rgbs"][lvl], x, skip)
+                skip = self._to_rgb(mod, pk["rgbs"][lvl], x, skip)
             if x.shape[2] == 64:              # ABSOLUTE width, like the reference (:155,158): with c characters per
                 p64 = x                       # sample the map is 4c·2^k wide, so c = 2 hands out the 32x64 / 16x32 levels
             if x.shape[2] == 32:
@@ -314,7 +320,8 @@ class TextGenerator(nn.Module):
                                "(models/networks.py:155-160 selects the prior levels by absolute width)" % labels.shape[1])
         return skip, p64, p32
 
-    def forward(self, styles, labels, noise=None):
+    def forward(self, styles, labels, noise=None, *, precision=None):
+        """``precision``: the mode of this call (None: ``self.precision``)"""
         with torch.no_grad(), ops.on_device(styles):
             styles = styles.contiguous().float()
             labels = labels.to(styles.device).contiguous().long()
@@ -328,12 +335,10 @@ class TextGenerator(nn.Module):
             # it (models/networks.py:313-321).  So the MODULE call runs the whole generator in fp16x3 when its mode is fp16x2 (3.8e-5; 21 % of a strip's FLOPs at a third
             # instead of half the fp16 rate — paid by test_w.py / test_sr.py-style callers only: the batched driver, MarconetPipeline, calls forward_nhwc itself and keeps
             # the priors in the mode's arithmetic, with the image-only level in fp16x3 when it returns the image: returned_image_precision)
-            mode = self.precision
-            self.precision = "fp16x3" if (mode == "fp16x2" and self.module_call_fp16x3) else mode
-            try:
-                img, p64, p32 = self.forward_nhwc(styles, labels)
-            finally:
-                self.precision = mode
+            mode = self.precision if precision is None else precision
+            if mode == "fp16x2" and self.module_call_fp16x3:
+                mode = "fp16x3"
+            img, p64, p32 = self.forward_nhwc(styles, labels, precision=mode)
             out = ops.nhwc_to_nchw(img, c=3), ops.nhwc_to_nchw(p64), ops.nhwc_to_nchw(p32)
             # keep the NHWC originals reachable so TSPSRNet can skip the NCHW→NHWC round trip
             # (valid only while the NCHW tensor is unmodified: its version counter and address are recorded with the shadow)
@@ -348,8 +353,7 @@ class TSPGAN(nn.Module, _Precision):
         self.precision = default_precision()
 
     def forward(self, styles, labels, noise):
-        self.TextGenerator.precision = self.precision
-        return self.TextGenerator(styles, labels, noise)
+        return self.TextGenerator(styles, labels, noise, precision=self.precision)
 
 
 # =====================================================================================================

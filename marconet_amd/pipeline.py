@@ -31,7 +31,6 @@ class MarconetPipeline:
         self.encoder, self.gan, self.sr = encoder, gan, sr
         self.glyph_chunk = glyph_chunk
         self.check_finite = check_finite
-        self._finite = None
         precision = default_precision() if precision is None else precision
         # True (default): the generator also produces its 128-px structure image, as test_sr.py:183 does (it is only ever
         # used for the saved visualisation, test_sr.py:203-232).  False is an opt-in for throughput serving.
@@ -66,7 +65,9 @@ class MarconetPipeline:
         ``return_prior=True`` → ``(that, prior_cha)``: the generator's structure images of all glyphs, fp32 NCHW [ΣN,3,128,128] in
         strip order — what test_sr.py:183 names ``prior_cha`` and :207-212 turn into the panel's last row.  The levels behind the two
         prior levels then run in the MODE's arithmetic (``prior_image_precision="auto"`` demotes them to plain fp16 only while the
-        image is dropped), so the returned image holds the same bar as ``TSPGAN.forward``'s; the SR output is the same bits either way."""
+        image is dropped) — in the fp16x2 mode in fp16x3 (``networks.returned_image_precision``), while the levels up to the priors
+        keep fp16x2: 5.4e-4 on the image, inside the 1e-3 bar but not ``TSPGAN.forward``'s 3.8e-5, which runs the WHOLE generator in
+        fp16x3 (see the comment there); the SR output is the same bits either way."""
         dev = lq.device
         counts = [int(l.shape[0]) for l in labels]
         if return_prior and not self.need_prior_image:
@@ -74,16 +75,16 @@ class MarconetPipeline:
         with ops.on_device(lq):
             lab, img_of = self._host_prep(labels, counts, dev)
             prior = torch.empty((sum(counts), 128, 128, 4), dtype=torch.float32, device=dev) if return_prior else None
-            y = self._core(lq, lab, img_of, counts, locs, None, return_nhwc, output, prior_images=prior)
-            self._raise_if_not_finite()
+            y, flag = self._core(lq, lab, img_of, counts, locs, None, return_nhwc, output, prior_images=prior)
+            self._raise_if_not_finite(flag)
             return (y, ops.nhwc_to_nchw(prior, c=3) if sum(counts) else prior.new_zeros((0, 3, 128, 128))) if return_prior else y
 
-    def _raise_if_not_finite(self):
+    def _raise_if_not_finite(self, flag):
         """half-range modes (fp16 / fp16x3 / fp16x2 store |activation| < 65504): an overflow turns into NaN on its way through the
         GroupNorm statistics of the following layers (and the last layer writes an infinite pre-activation as NaN instead of
         tanh's +-1), so the SR result carries it; one flag is read back per batch."""
-        # _finite: int32 flags written by mnet_nonfinite_flag (1 = inf / NaN found) — ONE device→host copy, tested on the host
-        if self._checks() and self._finite is not None and any(self._finite.cpu().tolist()):
+        # flag: int32 flags written by mnet_nonfinite_flag (1 = inf / NaN found; None: check off) — ONE device→host copy, tested on the host
+        if flag is not None and any(flag.cpu().tolist()):
             raise FloatingPointError("marconet_amd: non-finite SR output in %s mode (activations beyond the fp16 range 65504?) — use "
                                      "precision='fp32' for these weights" % self.precision)
 
@@ -102,15 +103,15 @@ class MarconetPipeline:
     @torch.no_grad()
     def _core(self, lq, lab, img_of, counts, locs, tables, return_nhwc=False, output="nchw_f32", prior_images=None):
         """the device-side part of forward_batch: nothing here touches host data (it can be captured in a HIP graph).
-        ``prior_images`` (fp32 [ΣN,128,128,4] or None): filled with the generator's structure images, chunk by chunk"""
+        ``prior_images`` (fp32 [ΣN,128,128,4] or None): filled with the generator's structure images, chunk by chunk.
+        → (output, finiteness flag of the SR result: int32 [1] on the device, or None with the check off)"""
         _, _, w = self.encoder(lq)                                    # test_sr.py:146
         tg = self.gan.TextGenerator
-        tg.precision = self.precision
         if sum(counts):
             # w0.repeat(n,1) per image (test_sr.py:183): the generator gets the B distinct styles + the glyph→image index
             # the generator runs in chunks of glyphs (bounded working set for huge batches) and writes its two prior levels
             # straight into the all-glyph buffers TSPSRNet reads (no concatenation pass: 34 GB of copies per step at batch 256)
-            G, gdt = lab.shape[0], torch_dtype(tg.precision)
+            G, gdt = lab.shape[0], torch_dtype(self.precision)
             p64 = new_tensor((G, 64, 64, 256), gdt, lq.device)
             p32 = new_tensor((G, 32, 32, 512), gdt, lq.device)
             # a returned image is computed in the mode's arithmetic; a dropped one under ``prior_image_precision`` (see forward_batch)
@@ -120,25 +121,23 @@ class MarconetPipeline:
                 e = min(G, s + self.glyph_chunk)
                 if _NO_STYLE_DEDUPE:
                     img = tg.forward_nhwc(w.index_select(0, img_of[s:e]).contiguous(), lab[s:e].contiguous(),
-                                          need_image=self.need_prior_image, p64_out=p64[s:e], p32_out=p32[s:e], image_precision=img_prec)[0]
+                                          need_image=self.need_prior_image, p64_out=p64[s:e], p32_out=p32[s:e], image_precision=img_prec,
+                                          precision=self.precision)[0]
                 else:
                     img = tg.forward_nhwc(w, lab[s:e].contiguous(), need_image=self.need_prior_image, style_index=img_of[s:e].contiguous(),
-                                          p64_out=p64[s:e], p32_out=p32[s:e], image_precision=img_prec)[0]
+                                          p64_out=p64[s:e], p32_out=p32[s:e], image_precision=img_prec, precision=self.precision)[0]
                 if prior_images is not None:
                     prior_images[s:e].copy_(img)
             sr_dtype = torch_dtype(self.sr.precision)                 # the three nets may run in different precision modes
             p64, p32 = ops.convert(p64, sr_dtype), ops.convert(p32, sr_dtype)
         else:
             p64 = p32 = None
-        if output != "u8_bgr" and not return_nhwc:
-            y = self.sr.forward_packed(lq, p64, p32, counts, counts, locs, nchw_out=True, tables=tables)   # test_sr.py:197
-            self._finite = ops.nonfinite_flag(y) if self._checks() else None    # device-side flag (mnet_nonfinite_flag): no synchronisation here
-            return y
-        y = self.sr.forward_packed(lq, p64, p32, counts, counts, locs, tables=tables)
-        self._finite = ops.nonfinite_flag(y) if self._checks() else None
+        nchw = output != "u8_bgr" and not return_nhwc
+        y = self.sr.forward_packed(lq, p64, p32, counts, counts, locs, nchw_out=nchw, tables=tables)   # test_sr.py:197
+        flag = ops.nonfinite_flag(y) if self._checks() else None          # device-side flag (mnet_nonfinite_flag): no synchronisation here
         if output == "u8_bgr":                                           # test_sr.py:198-200 fused: [B,128,2048,3] uint8
-            return ops.sr_postprocess(y, u8=True)
-        return y if return_nhwc else ops.nhwc_to_nchw(y, c=3)
+            y = ops.sr_postprocess(y, u8=True)
+        return y, flag
 
 
     def forward_mixed_widths(self, lq, content_widths, labels, locs, bucket=64):
@@ -169,18 +168,15 @@ class MarconetPipeline:
             widths.append(min(512, (w_ + bucket - 1) // bucket * bucket))
         _, _, w = self.encoder(lq)
         tg = self.gan.TextGenerator
-        tg.precision = self.precision
         starts = [0]
         for c in counts:
             starts.append(starts[-1] + c)
         p64 = p32 = None
         if starts[-1]:
-            lab = torch.cat([l.reshape(-1, 1) for l in labels if l.shape[0]], dim=0).to(dev).long().contiguous()
-            if int(lab.min()) < 0 or int(lab.max()) >= tg.class_num:
-                raise RuntimeError("label index out of range [0,%d)" % tg.class_num)
+            lab, _ = MarconetPipeline._host_prep(self, labels, counts, dev)     # (this method needs only self.gan of a duck-typed self)
             img_of = torch.repeat_interleave(torch.arange(B, device=dev), torch.tensor(counts, device=dev))
             _, p64, p32 = tg.forward_nhwc(w.index_select(0, img_of).contiguous(), lab, need_image=self.need_prior_image,
-                                          image_precision=self._image_precision())
+                                          image_precision=self._image_precision(), precision=self.precision)
         out = [None] * B
         buckets = sorted(set(widths))
         flags = torch.empty((len(buckets),), dtype=torch.int32, device=dev) if self._checks() else None     # one finiteness flag per bucket
@@ -205,8 +201,7 @@ class MarconetPipeline:
                 ops.nonfinite_flag(y, out=flags[kb:kb + 1])
             for k, b in enumerate(idx):
                 out[b] = y[k]
-        self._finite = flags
-        self._raise_if_not_finite()
+        self._raise_if_not_finite(flags)
         return out
 
 
@@ -353,10 +348,8 @@ class GraphedForward:
             torch.cuda.current_stream(dev).wait_stream(side)
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
-                self.out = pipe._core(self.lq, self.lab, self.img_of, self.counts, None, self.tables, output=output)
-            # the finiteness flag THIS graph refreshes on every replay (pipe._finite is reassigned by every other forward of the
-            # pipe — an eager forward_batch, another GraphedForward — and must not be read here)
-            self._flag = pipe._finite
+                # _flag: the finiteness flag this graph refreshes on every replay (None: captured with the check off)
+                self.out, self._flag = pipe._core(self.lq, self.lab, self.img_of, self.counts, None, self.tables, output=output)
             self._checks = pipe._checks()
             self._quiet_without_flag = pipe.precision == "fp32" and pipe.check_finite is None     # as captured
 

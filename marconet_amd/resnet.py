@@ -66,9 +66,10 @@ class ResNet(nn.Module):
         return pk
 
     # ------------------------------------------------------------------ forward
-    def forward_nhwc(self, x):
-        """x: NHWC [B,32,512,8] (RGB zero-padded to 8 channels) in the compute dtype → NHWC [B,8,512,512]."""
-        pk = self._cache.get(self, self.precision, self._build)
+    def forward_nhwc(self, x, precision=None):
+        """x: NHWC [B,32,512,8] (RGB zero-padded to 8 channels) in the compute dtype → NHWC [B,8,512,512].
+        ``precision``: the mode whose packed weights this call uses (None: ``self.precision``) — x is in that mode's dtype."""
+        pk = self._cache.get(self, self.precision if precision is None else precision, self._build)
         x = ops.conv2d(x, pk["conv1"], 32, 3, 3, (1, 1), (1, 1), act=ops.ACT_RELU)
         for li in range(1, 6):
             for bi, blk in enumerate(getattr(self, "layer%d" % li)):

@@ -779,3 +779,151 @@ def test_packed_blob_drives_the_same_forward(nets, ckpts, tmp_path, precision):
         assert torch.equal(got, want)
     finally:
         pipe.set_precision("fp32")
+
+
+# ------------------------------------------------------------------------------------------------ the precision mode is an argument
+# The smallest shapes the nets accept: one 32x512 strip with two glyphs.
+def _small_problem():
+    lq = synth.make_lq(611, 1, [512]).to(DEV)
+    labels = synth.make_labels(612, 2)
+    return lq, labels, synth.make_locs([2], [512]), synth.make_styles(613, 2).to(DEV)
+
+
+def _f32(t):
+    from marconet_amd import ops
+    return t if t.dtype == torch.float32 else ops.convert(t, torch.float32)
+
+
+def _same_bits(a, b):
+    return len(a) == len(b) and all(u.shape == v.shape and torch.equal(_f32(u), _f32(v)) for u, v in zip(a, b))
+
+
+def _module_state(nets):
+    """attribute names and precision mode of every module of the three nets"""
+    return {"%d.%s" % (i, name): (tuple(m.__dict__), getattr(m, "precision", None))
+            for i, net in enumerate(nets) for name, m in net.named_modules()}
+
+
+@pytest.mark.parametrize("precision", ["fp16x2", "fp32"])
+def test_a_forward_leaves_the_modules_as_it_found_them(nets, precision):
+    """no call form — module calls, the batched driver with and without the returned image, mixed widths, a HIP-graph capture and
+    replay, a forward that raises — assigns an attribute of a module (its ``precision`` least of all) or leaves a new one behind"""
+    from marconet_amd import networks, resnet
+    from marconet_amd.pipeline import GraphedForward, MarconetPipeline
+    enc, gan, sr = nets
+    lq, labels, locs, styles = _small_problem()
+    lab = labels.to(DEV)
+    pipe = MarconetPipeline(*nets, precision=precision)
+
+    def every_form(graph):
+        enc(lq)
+        _, p64, p32 = gan(styles, lab, None)
+        sr(lq, [p64], [p32], locs.to(DEV))
+        pipe.forward_batch(lq, [labels], locs)
+        pipe.forward_batch(lq, [labels], locs, return_prior=True)
+        pipe.forward_mixed_widths(lq, [512], [labels], locs)
+        if graph:
+            GraphedForward(pipe, 1, [2])(lq, [labels], locs)
+
+    try:
+        every_form(graph=False)                                    # warm-up: the packing for this mode is done
+        before, writes = _module_state(nets), []
+        with pytest.MonkeyPatch.context() as mp:
+            for cls in (networks.TextContextEncoderV2, resnet.ResNet, networks.TSPGAN, networks.TextGenerator, networks.TSPSRNet):
+                def record(self, name, value):
+                    writes.append((type(self).__name__, name))
+                    torch.nn.Module.__setattr__(self, name, value)
+                mp.setattr(cls, "__setattr__", record, raising=False)
+            every_form(graph=True)
+            assert writes == [] and _module_state(nets) == before
+            with pytest.raises(RuntimeError, match="out of range"):
+                gan(styles, torch.tensor([[3], [gan.TextGenerator.class_num]], device=DEV), None)
+            assert writes == [] and _module_state(nets) == before
+        assert not hasattr(pipe, "_finite")
+    finally:
+        pipe.set_precision("fp32")
+
+
+def test_precision_argument_and_attribute_mean_the_same(nets):
+    """TextGenerator.forward_nhwc(precision=m) gives the bits of the same call on a generator whose mode IS m; the fp16x2 module call
+    is that fp16x3 result (``module_call_fp16x3``), or the mode's own with the switch off — and the attribute reads fp16x2 throughout"""
+    from marconet_amd import ops
+    gan, tg = nets[1], nets[1].TextGenerator
+    _, labels, _, styles = _small_problem()
+    lab = labels.to(DEV)
+    nchw = lambda r: (ops.nhwc_to_nchw(r[0], c=3), ops.nhwc_to_nchw(r[1]), ops.nhwc_to_nchw(r[2]))
+    try:
+        for mode in ("fp16x3", "fp16x2"):                           # warm-up, one forward per mode
+            tg.forward_nhwc(styles, lab, precision=mode)
+        gan.set_precision("fp16x3")
+        want = tg.forward_nhwc(styles, lab)
+        gan.set_precision("fp16x2")
+        assert tg.precision == "fp16x2"
+        assert _same_bits(tg.forward_nhwc(styles, lab, precision="fp16x3"), want) and tg.precision == "fp16x2"
+        own = tg.forward_nhwc(styles, lab)
+        assert tg.module_call_fp16x3
+        assert _same_bits(gan(styles, lab, None), nchw(want)) and tg.precision == "fp16x2"
+        tg.module_call_fp16x3 = False
+        assert _same_bits(gan(styles, lab, None), nchw(own)) and tg.precision == "fp16x2"
+    finally:
+        tg.module_call_fp16x3 = True
+        gan.set_precision("fp32")
+
+
+def test_pipeline_mode_reaches_the_generator_without_touching_it(nets):
+    """tools/precision_probe.py's form — the three nets switched one by one, ``pipe.precision`` naming the generator's mode: the
+    generator runs in the pipeline's mode, and still holds what its owner set"""
+    from marconet_amd.pipeline import MarconetPipeline
+    enc, gan, sr = nets
+    lq, labels, locs, _ = _small_problem()
+    pipe = MarconetPipeline(*nets, precision="fp16x3")
+    try:
+        pipe.forward_batch(lq, [labels], locs, return_prior=True)                  # warm-up
+        gan.set_precision("fp32")
+        pipe.precision = "fp16x3"
+        got = pipe.forward_batch(lq, [labels], locs, return_prior=True)
+        assert gan.TextGenerator.precision == "fp32" and gan.precision == "fp32"
+        pipe.set_precision("fp16x3")
+        want = pipe.forward_batch(lq, [labels], locs, return_prior=True)
+        assert _same_bits(got, want)
+    finally:
+        pipe.set_precision("fp32")
+
+
+def test_encoder_resnet_mode_is_set_without_a_forward(nets, monkeypatch):
+    """the encoder's ResNet keeps the three-product arithmetic in the fp16x2 mode (TextContextEncoderV2.resnet_precision) from the
+    constructor and from set_precision on, not from the first forward on; the encoder's fp16x2 output is its fp16x3 output"""
+    from marconet_amd import networks
+    fresh = networks.TextContextEncoderV2().set_precision("fp16x2")
+    assert fresh.precision == "fp16x2" and fresh.resnet.precision == "fp16x3"
+    monkeypatch.setenv("MARCONET_PRECISION", "fp16x2")
+    built = networks.TextContextEncoderV2()
+    assert built.precision == "fp16x2" and built.resnet.precision == "fp16x3"
+    enc = nets[0]
+    lq = _small_problem()[0]
+    try:
+        for mode in ("fp16x3", "fp16x2"):                           # warm-up
+            enc.set_precision(mode)(lq)
+        a = enc.set_precision("fp16x2")(lq)
+        b = enc.set_precision("fp16x3")(lq)
+        assert _same_bits(a, b)
+    finally:
+        enc.set_precision("fp32")
+
+
+def test_finiteness_flags_belong_to_their_call(nets):
+    """a GraphedForward reads the flag its own graph refreshes, whatever the pipe has run since its capture"""
+    from marconet_amd.pipeline import GraphedForward, MarconetPipeline
+    lq, labels, locs, _ = _small_problem()
+    pipe = MarconetPipeline(*nets, precision="fp16x2")
+    try:
+        pipe.forward_batch(lq, [labels], locs)                                     # warm-up
+        gf = GraphedForward(pipe, 1, [2])
+        gf(lq, [labels], locs, check=False)
+        pipe.forward_batch(lq, [labels], locs)
+        pipe.forward_mixed_widths(lq, [512], [labels], locs)
+        assert gf.has_flag and gf._flag.numel() == 1
+        gf.raise_if_not_finite()
+        assert not hasattr(pipe, "_finite")
+    finally:
+        pipe.set_precision("fp32")

@@ -30,7 +30,7 @@ def main():
     print("%-8s %-8s %-8s   max-abs     mean-abs" % ("encoder", "gan", "sr"))
     for pe, pg, ps in itertools.product(("fp16", "fp32"), repeat=3):
         pipe.encoder.set_precision(pe); pipe.gan.set_precision(pg); pipe.sr.set_precision(ps)
-        pipe.precision = pg          # forward_batch passes this to the generator
+        pipe.precision = pg          # the mode forward_batch hands to the generator as an argument (and sizes the prior buffers for)
         y = pipe.forward_batch(lqd, labd, locd).cpu()
         d = (y - ref).abs()
         print("%-8s %-8s %-8s   %.3e   %.3e" % (pe, pg, ps, d.max().item(), d.mean().item()))
