@@ -382,6 +382,11 @@ __global__ void __launch_bounds__(256) adain_crop_kernel(const T* __restrict__ p
     const T* pbase = prior + (size_t)g * S * S * C + (size_t)ch * N;
     const T* fbase = feat + (size_t)img * S * FW * C + (size_t)ch * N;
     const int npx = S * gw;
+    // The sums are taken of (value - pivot), the pivot being the channel's value at the window's first pixel: a channel whose mean is 1e4 times its spread
+    // loses 8 digits in sum(x^2) - n mean^2 otherwise, and the fused and the three-launch form (other association) then differ by ulps of fp32 in the std
+    float pk[N], fk[N];
+    unpackr<T>(ldraw<T>(pbase + (size_t)y1 * C), pk);
+    unpackr<T>(ldraw<T>(fbase + (size_t)x1 * C), fk);
     double ps_[N], pss[N], fs_[N], fss[N];
 #pragma unroll
     for (int j = 0; j < N; ++j) { ps_[j] = pss[j] = fs_[j] = fss[j] = 0.0; }
@@ -392,14 +397,19 @@ __global__ void __launch_bounds__(256) adain_crop_kernel(const T* __restrict__ p
         unpackr<T>(ldraw<T>(fbase + ((size_t)y * FW + (x1 + x)) * C), b);
 #pragma unroll
         for (int j = 0; j < N; ++j) {
-            ps_[j] += (double)a[j]; pss[j] += (double)a[j] * (double)a[j];
-            fs_[j] += (double)b[j]; fss[j] += (double)b[j] * (double)b[j];
+            const double da = (double)a[j] - (double)pk[j], db = (double)b[j] - (double)fk[j];     // exact
+            ps_[j] += da; pss[j] += da * da;
+            fs_[j] += db; fss[j] += db * db;
         }
     }
 #pragma unroll
     for (int j = 0; j < N; ++j) {
         double* r = red + ((size_t)t * N + j) * 4;
         r[0] = ps_[j]; r[1] = pss[j]; r[2] = fs_[j]; r[3] = fss[j];
+    }
+    if (pl == 0) {                      // the pivots, in the slots thread c overwrites with the means
+#pragma unroll
+        for (int j = 0; j < N; ++j) { stat[ch * N + j] = pk[j]; stat[2 * C + ch * N + j] = fk[j]; }
     }
     __syncthreads();
     // thread c (< C) folds the pixel lanes of channel c
@@ -411,20 +421,20 @@ __global__ void __launch_bounds__(256) adain_crop_kernel(const T* __restrict__ p
             a0 += r[0]; a1 += r[1]; b0 += r[2]; b1 += r[3];
         }
         const double cnt = (double)npx;
-        const double pm = a0 / cnt, fm = b0 / cnt;
+        const double pd = a0 / cnt, fd = b0 / cnt;                      // means of (value - pivot)
+        const double pm = (double)stat[c] + pd, fm = (double)stat[2 * C + c] + fd;
+        double pdev = a1 - cnt * pd * pd, fdev = b1 - cnt * fd * fd;    // sums of squared deviations from the mean
+        if (pdev < 0) pdev = 0; if (fdev < 0) fdev = 0;
         // unbiased variance (torch .var default, networks.py:522) + eps 1e-5, then sqrt
-        double pv = (a1 - cnt * pm * pm) / (cnt - 1.0), fv = (b1 - cnt * fm * fm) / (cnt - 1.0);
-        if (pv < 0) pv = 0; if (fv < 0) fv = 0;
+        const double pv = pdev / (cnt - 1.0), fv = fdev / (cnt - 1.0);
         stat[c] = (float)pm; stat[C + c] = sqrtf((float)pv + 1e-5f);
         stat[2 * C + c] = (float)fm; stat[3 * C + c] = sqrtf((float)fv + 1e-5f);
         if (gn_scale) {     // per-channel sum / sum of squares of the [.., 2C] OUTPUT over the window, in closed form:
                             // channel c (restyled prior) = (p - pm)/ps*fs + fm → sum = cnt*fm, sumsq = r^2 * sum (p-pm)^2 + cnt*fm^2
                             // channel C + c (feature crop) = the accumulated sums themselves
             const double r = (double)stat[3 * C + c] / (double)stat[C + c];
-            double dev = a1 - cnt * pm * pm;
-            if (dev < 0) dev = 0;
-            gsum[c] = cnt * fm;            gsum[2 * C + c] = r * r * dev + cnt * fm * fm;
-            gsum[C + c] = b0;              gsum[3 * C + c] = b1;
+            gsum[c] = cnt * fm;            gsum[2 * C + c] = r * r * pdev + cnt * fm * fm;
+            gsum[C + c] = cnt * fm;        gsum[3 * C + c] = fdev + cnt * fm * fm;
         }
     }
     __syncthreads();
@@ -483,6 +493,8 @@ static int adain_launch(const void* prior, const void* feat, void* out, int32_t 
     //  apply): 102 GB of real traffic per step in 18.8 ms = 5.4 TB/s, the copy ceiling of this chip; `roofline.hbm_tail` books the algorithmic 69 GB.)
     const size_t lds = (size_t)256 * N * 4 * sizeof(double) + (size_t)4 * C * sizeof(float) + (size_t)4 * C * sizeof(double) +
                        (size_t)(2 * C / 32) * 2 * sizeof(float);
+    // a workgroup can have 160 KiB of LDS: C = 2048 in an 8-wide storage asks for 164,864 bytes — refused here, before any HIP call, like adain_split's lds2
+    MNET_CHECK_ARG(lds <= 160 * 1024, "adain: C=%d too large (%zu bytes of LDS per workgroup, 163840 at most)", C, lds);
     static thread_local size_t lds_all[256][4] = {};                   // attribute raised once per (device, size) (not during graph capture replays)
     size_t* lds_set = lds_all[DeviceOnce::dev()];
     if (dtype == MNET_F16X2) {
@@ -531,7 +543,7 @@ template <typename T>
 __global__ void __launch_bounds__(256) adain_stats_kernel(const T* __restrict__ prior, const T* __restrict__ feat, int S, int C, int FW,
                                                           const int* __restrict__ g_img, const int* __restrict__ g_x1,
                                                           const int* __restrict__ g_y1, const int* __restrict__ g_w,
-                                                          double* __restrict__ partial, int slices) {
+                                                          double* __restrict__ partial, float* __restrict__ stat_g, int slices) {
     constexpr int N = Vec<T>::N;
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
     double* red = reinterpret_cast<double*>(dyn);                       // [256][N][4]
@@ -543,6 +555,14 @@ __global__ void __launch_bounds__(256) adain_stats_kernel(const T* __restrict__ 
     const T* fbase = feat + (size_t)img * S * FW * C + (size_t)ch * N;
     const int npx = S * gw, per = (npx + slices - 1) / slices;
     const int p_end = min(npx, (sl + 1) * per);
+    float pk[N], fk[N];                                                  // the pivots of adain_crop_kernel: the same for every slice of the glyph
+    unpackr<T>(ldraw<T>(pbase + (size_t)y1 * C), pk);
+    unpackr<T>(ldraw<T>(fbase + (size_t)x1 * C), fk);
+    if (sl == 0 && pl == 0) {                                            // handed to adain_finalize_kernel in the rows it overwrites with the means
+        float* st = stat_g + (size_t)g * 4 * C + (size_t)ch * N;
+#pragma unroll
+        for (int j = 0; j < N; ++j) { st[j] = pk[j]; st[2 * C + j] = fk[j]; }
+    }
     double ps_[N], pss[N], fs_[N], fss[N];
 #pragma unroll
     for (int j = 0; j < N; ++j) { ps_[j] = pss[j] = fs_[j] = fss[j] = 0.0; }
@@ -553,8 +573,9 @@ __global__ void __launch_bounds__(256) adain_stats_kernel(const T* __restrict__ 
         unpackr<T>(ldraw<T>(fbase + ((size_t)y * FW + (x1 + x)) * C), b);
 #pragma unroll
         for (int j = 0; j < N; ++j) {
-            ps_[j] += (double)a[j]; pss[j] += (double)a[j] * (double)a[j];
-            fs_[j] += (double)b[j]; fss[j] += (double)b[j] * (double)b[j];
+            const double da = (double)a[j] - (double)pk[j], db = (double)b[j] - (double)fk[j];     // exact
+            ps_[j] += da; pss[j] += da * da;
+            fs_[j] += db; fss[j] += db * db;
         }
     }
 #pragma unroll
@@ -593,17 +614,17 @@ __global__ void __launch_bounds__(256) adain_finalize_kernel(const double* __res
             a0 += r[0]; a1 += r[1]; b0 += r[2]; b1 += r[3];
         }
         const double cnt = (double)npx;
-        const double pm = a0 / cnt, fm = b0 / cnt;
-        double pv = (a1 - cnt * pm * pm) / (cnt - 1.0), fv = (b1 - cnt * fm * fm) / (cnt - 1.0);
-        if (pv < 0) pv = 0; if (fv < 0) fv = 0;
+        const double pd = a0 / cnt, fd = b0 / cnt;                      // the sums are of (value - pivot); adain_stats_kernel left the pivots in st
+        const double pm = (double)st[c] + pd, fm = (double)st[2 * C + c] + fd;
+        double pdev = a1 - cnt * pd * pd, fdev = b1 - cnt * fd * fd;
+        if (pdev < 0) pdev = 0; if (fdev < 0) fdev = 0;
+        const double pv = pdev / (cnt - 1.0), fv = fdev / (cnt - 1.0);
         const float psd = sqrtf((float)pv + 1e-5f), fsd = sqrtf((float)fv + 1e-5f);
         st[c] = (float)pm; st[C + c] = psd; st[2 * C + c] = (float)fm; st[3 * C + c] = fsd;
         if (gn_scale) {
             const double r = (double)fsd / (double)psd;
-            double dev = a1 - cnt * pm * pm;
-            if (dev < 0) dev = 0;
-            gsum[c] = cnt * fm;            gsum[2 * C + c] = r * r * dev + cnt * fm * fm;
-            gsum[C + c] = b0;              gsum[3 * C + c] = b1;
+            gsum[c] = cnt * fm;            gsum[2 * C + c] = r * r * pdev + cnt * fm * fm;
+            gsum[C + c] = cnt * fm;        gsum[3 * C + c] = fdev + cnt * fm * fm;
         }
     }
     if (!gn_scale) return;
@@ -690,10 +711,10 @@ extern "C" int mnet_adain_crop_concat_split(const void* prior, const void* feat,
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(adain_stats_kernel<hm>), hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 8 * 4 * 8);
         attr_once.mark();
     }
-    if (dtype == MNET_F16) hipLaunchKernelGGL(adain_stats_kernel<f16>, dim3(slices, G), dim3(256), lds1, st, (const f16*)prior, (const f16*)feat, S, C, feat_w, g_img, g_x1, g_y1, g_w, partial, slices);
-    else if (dtype == MNET_F16X2) hipLaunchKernelGGL(adain_stats_kernel<hs>, dim3(slices, G), dim3(256), lds1, st, (const hs*)prior, (const hs*)feat, S, C, feat_w, g_img, g_x1, g_y1, g_w, partial, slices);
-    else if (dtype == MNET_F16M) hipLaunchKernelGGL(adain_stats_kernel<hm>, dim3(slices, G), dim3(256), lds1, st, (const hm*)prior, (const hm*)feat, S, C, feat_w, g_img, g_x1, g_y1, g_w, partial, slices);
-    else hipLaunchKernelGGL(adain_stats_kernel<float>, dim3(slices, G), dim3(256), lds1, st, (const float*)prior, (const float*)feat, S, C, feat_w, g_img, g_x1, g_y1, g_w, partial, slices);
+    if (dtype == MNET_F16) hipLaunchKernelGGL(adain_stats_kernel<f16>, dim3(slices, G), dim3(256), lds1, st, (const f16*)prior, (const f16*)feat, S, C, feat_w, g_img, g_x1, g_y1, g_w, partial, stat, slices);
+    else if (dtype == MNET_F16X2) hipLaunchKernelGGL(adain_stats_kernel<hs>, dim3(slices, G), dim3(256), lds1, st, (const hs*)prior, (const hs*)feat, S, C, feat_w, g_img, g_x1, g_y1, g_w, partial, stat, slices);
+    else if (dtype == MNET_F16M) hipLaunchKernelGGL(adain_stats_kernel<hm>, dim3(slices, G), dim3(256), lds1, st, (const hm*)prior, (const hm*)feat, S, C, feat_w, g_img, g_x1, g_y1, g_w, partial, stat, slices);
+    else hipLaunchKernelGGL(adain_stats_kernel<float>, dim3(slices, G), dim3(256), lds1, st, (const float*)prior, (const float*)feat, S, C, feat_w, g_img, g_x1, g_y1, g_w, partial, stat, slices);
     MNET_LAUNCH_CHECK("adain_stats");
     hipLaunchKernelGGL(adain_finalize_kernel, dim3(G), dim3(256), lds2, st, partial, slices, S, C, g_w, stat, gamma, beta, eps, scale, shift);
     MNET_LAUNCH_CHECK("adain_finalize");
@@ -708,6 +729,13 @@ extern "C" int mnet_adain_crop_concat_split(const void* prior, const void* feat,
 // ============================================================================ ordered glyph scatter
 // grid (x-chunks of one feature row, image): a thread owns one 16-byte channel chunk of one COLUMN; the glyph that owns the
 // column (last glyph of the image whose window covers it) is looked up once and reused for all S rows
+// fl(fl(a * b) + c): the reference's two PyTorch operations.  `__fadd_rn(__fmul_rn(a, b), c)` does NOT say that: the intrinsics are plain `*` / `+` to the
+// compiler and were contracted into one v_fmac_f32 (a single rounding, an ulp away from the reference on ~1 element in 4); the pragma is what holds them apart
+__device__ __forceinline__ float mul_add_unfused(float a, float b, float c) {
+#pragma clang fp contract(off)
+    const float m = a * b;
+    return m + c;
+}
 #ifndef MNET_SCATTER_RUN
 #define MNET_SCATTER_RUN 8
 #endif
@@ -758,7 +786,7 @@ __global__ void __launch_bounds__(256) glyph_scatter_kernel(const T* __restrict_
             unpackr<T>(rf[k], f); unpackr<T>(rs[k], sc); unpackr<T>(rh[k], sh);
 #pragma unroll
             for (int j = 0; j < N; ++j) {
-                const float r = __fadd_rn(__fmul_rn(f[j], sc[j]), sh[j]);    // res = f*scale + shift  (:448)
+                const float r = mul_add_unfused(f[j], sc[j], sh[j]);         // res = f*scale + shift  (:448)
                 o[j] = __fadd_rn(f[j], r);                                    // ori + res             (:449)
             }
             straw<T>(op + (size_t)(y0 + k) * row, packr<T>(o));

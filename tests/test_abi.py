@@ -177,6 +177,15 @@ def test_argument_validation_without_device():
     assert lib.mnet_adain_crop_concat_split(16, 16, 16, 1, 1, 32, 256, 512, 16, 16, 16, 16, None, None, 1e-6, None, None, None, 16, 16, None) == -1
     assert lib.mnet_adain_crop_concat_split(16, 16, 16, 1, 1, 32, 256, 512, 16, 16, 16, 16, 16, None, 1e-6, None, None, 16, 16, 16, None) == -1
     assert b"go together" in lib.mnet_last_error()
+    # C = 2048 in an 8-wide storage: the fused AdaIN kernel would need 164,864 bytes of LDS, a workgroup has 160 KiB — an argument error (-1, before
+    # any HIP call: nothing is enqueued), in both entry points and every 8-wide storage, like adain_split's `lds2 > 65536`
+    for dt in (1, 2, 3):
+        assert lib.mnet_adain_crop_concat_gn(128, 128, 128, dt, 1, 8, 2048, 8, 16, 16, 16, 16, 16, 16, 1e-6, 16, 16, None) == -1
+        assert b"adain: C=2048 too large (164864 bytes" in lib.mnet_last_error()
+        assert lib.mnet_adain_crop_concat(128, 128, 128, dt, 1, 8, 2048, 8, 16, 16, 16, 16, None) == -1
+        assert b"adain: C=2048 too large" in lib.mnet_last_error()
+    assert lib.mnet_adain_crop_concat_split(128, 128, 128, 1, 1, 8, 2048, 8, 16, 16, 16, 16, None, None, 1e-6, None, None, 16, 16, 16, None) == -1
+    assert b"adain_split: C=2048 too large" in lib.mnet_last_error()
     # round-2 entry points
     assert lib.mnet_pack_weights(16, 8, 8, 3, 3, 16, None, 1.0, 1, 8, 8, 16, None, None) == -1 and b"go together" in lib.mnet_last_error()
     assert lib.mnet_pack_weights(16, 8, 8, 3, 3, 16, 16, 1.0, 1, 8, 8, 16, None, None) == -1 and b"workspace" in lib.mnet_last_error()
