@@ -6,8 +6,6 @@
 #include <cstdlib>
 #include "common.h"
 
-static inline bool is_split4(int dt) { return dt == MNET_F16X2 || dt == MNET_F16M; }      // the two 4-byte blocked storages
-
 // ============================================================================ layout: NCHW fp32 <-> NHWC T
 template <typename T>
 __global__ void __launch_bounds__(256) nchw_to_nhwc_kernel(const float* __restrict__ src, T* __restrict__ dst,
@@ -55,16 +53,16 @@ __global__ void __launch_bounds__(256) nhwc_to_nchw_kernel(const T* __restrict__
 extern "C" int mnet_nchw_to_nhwc(const float* src, void* dst, int32_t dst_dtype, int32_t n, int32_t c, int32_t h,
                                  int32_t w, int32_t c_ld, void* stream) {
     MNET_CHECK_ARG(src && dst && n > 0 && c > 0 && h > 0 && w > 0 && c_ld >= c, "nchw_to_nhwc: bad args");
-    MNET_CHECK_ARG(dst_dtype == MNET_F32 || dst_dtype == MNET_F16 || is_split4(dst_dtype), "nchw_to_nhwc: bad dtype");
+    MNET_CHECK_ARG(is_storage(dst_dtype), "nchw_to_nhwc: bad dtype");
     MNET_CHECK_ALIGN(!is_split4(dst_dtype) || (c_ld % 32 == 0 && aligned128(dst)), "nchw_to_nhwc: split-half output needs c_ld %% 32 == 0 and a 128-byte aligned base");
     MNET_CHECK_ARG(n <= 65535 && (c_ld + 31) / 32 <= 65535, "nchw_to_nhwc: grid too large");
     const int HW = h * w;
     dim3 grid((HW + 31) / 32, (c_ld + 31) / 32, n), block(32, 8);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dst_dtype == MNET_F16) hipLaunchKernelGGL(nchw_to_nhwc_kernel<f16>, grid, block, 0, st, src, (f16*)dst, c, HW, c_ld);
-    else if (dst_dtype == MNET_F16X2) hipLaunchKernelGGL(nchw_to_nhwc_kernel<hs>, grid, block, 0, st, src, (hs*)dst, c, HW, c_ld);
-    else if (dst_dtype == MNET_F16M) hipLaunchKernelGGL(nchw_to_nhwc_kernel<hm>, grid, block, 0, st, src, (hm*)dst, c, HW, c_ld);
-    else hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, grid, block, 0, st, src, (float*)dst, c, HW, c_ld);
+    dispatch_storage(dst_dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(nchw_to_nhwc_kernel<T>, grid, block, 0, st, src, (T*)dst, c, HW, c_ld);
+    });
     MNET_LAUNCH_CHECK("nchw_to_nhwc");
     return MNET_OK;
 }
@@ -72,16 +70,16 @@ extern "C" int mnet_nchw_to_nhwc(const float* src, void* dst, int32_t dst_dtype,
 extern "C" int mnet_nhwc_to_nchw(const void* src, int32_t src_dtype, float* dst, int32_t n, int32_t c, int32_t h,
                                  int32_t w, int32_t c_ld, void* stream) {
     MNET_CHECK_ARG(src && dst && n > 0 && c > 0 && h > 0 && w > 0 && c_ld >= c, "nhwc_to_nchw: bad args");
-    MNET_CHECK_ARG(src_dtype == MNET_F32 || src_dtype == MNET_F16 || is_split4(src_dtype), "nhwc_to_nchw: bad dtype");
+    MNET_CHECK_ARG(is_storage(src_dtype), "nhwc_to_nchw: bad dtype");
     MNET_CHECK_ALIGN(!is_split4(src_dtype) || (c_ld % 32 == 0 && aligned128(src)), "nhwc_to_nchw: split-half input needs c_ld %% 32 == 0 and a 128-byte aligned base");
     MNET_CHECK_ARG(n <= 65535 && (c + 31) / 32 <= 65535, "nhwc_to_nchw: grid too large");
     const int HW = h * w;
     dim3 grid((HW + 31) / 32, (c + 31) / 32, n), block(32, 8);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (src_dtype == MNET_F16) hipLaunchKernelGGL(nhwc_to_nchw_kernel<f16>, grid, block, 0, st, (const f16*)src, dst, c, HW, c_ld);
-    else if (src_dtype == MNET_F16X2) hipLaunchKernelGGL(nhwc_to_nchw_kernel<hs>, grid, block, 0, st, (const hs*)src, dst, c, HW, c_ld);
-    else if (src_dtype == MNET_F16M) hipLaunchKernelGGL(nhwc_to_nchw_kernel<hm>, grid, block, 0, st, (const hm*)src, dst, c, HW, c_ld);
-    else hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, grid, block, 0, st, (const float*)src, dst, c, HW, c_ld);
+    dispatch_storage(src_dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(nhwc_to_nchw_kernel<T>, grid, block, 0, st, (const T*)src, dst, c, HW, c_ld);
+    });
     MNET_LAUNCH_CHECK("nhwc_to_nchw");
     return MNET_OK;
 }
@@ -205,9 +203,9 @@ __global__ void __launch_bounds__(256) upsample2x_kernel(const T* __restrict__ s
 extern "C" int mnet_upsample2x_convert_nhwc(const void* src, int32_t dtype, void* dst, int32_t dst_dtype, int32_t n, int32_t h, int32_t w,
                                             int32_t c, const float* scale, void* stream) {
     MNET_CHECK_ARG(src && dst && n > 0 && h > 0 && w > 0 && c > 0 && n <= 65535, "upsample2x: bad args");
-    MNET_CHECK_ARG(dtype == MNET_F32 || dtype == MNET_F16 || is_split4(dtype), "upsample2x: bad dtype");
+    MNET_CHECK_ARG(is_storage(dtype), "upsample2x: bad dtype");
     MNET_CHECK_ARG(dst_dtype == dtype || (dst_dtype == MNET_F16 && is_split4(dtype)), "upsample2x: the output is the input's storage type, or MNET_F16 for a split-half / fp16+8 input");
-    const int N = dtype == MNET_F32 ? 4 : 8;
+    const int N = chunk_n(dtype);
     MNET_CHECK_ALIGN(c % N == 0 && aligned16(src) && aligned16(dst) && aligned16(scale), "upsample2x: c %% %d != 0 or unaligned", N);
     MNET_CHECK_ALIGN(!is_split4(dtype) || (c % 32 == 0 && aligned128(src)), "upsample2x: split-half needs c %% 32 == 0, 128-byte aligned");
     MNET_CHECK_ALIGN(!is_split4(dst_dtype) || aligned128(dst), "upsample2x: split-half output must be 128-byte aligned");
@@ -215,13 +213,15 @@ extern "C" int mnet_upsample2x_convert_nhwc(const void* src, int32_t dtype, void
     const long long per = (long long)((h + MNET_UPS_RUN - 1) / MNET_UPS_RUN) * w * (c / N);      // one thread per (chunk, column, run of MNET_UPS_RUN input rows)
     const int gx = (int)((per + 255) / 256 < 2048 ? (per + 255) / 256 : 2048);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dst_dtype != dtype) {
-        if (dtype == MNET_F16X2) hipLaunchKernelGGL((upsample2x_kernel<hs, f16>), dim3(gx, n), dim3(256), 0, st, (const hs*)src, (f16*)dst, h, w, c, scale, (unsigned)per);
-        else hipLaunchKernelGGL((upsample2x_kernel<hm, f16>), dim3(gx, n), dim3(256), 0, st, (const hm*)src, (f16*)dst, h, w, c, scale, (unsigned)per);
-    } else if (dtype == MNET_F16) hipLaunchKernelGGL(upsample2x_kernel<f16>, dim3(gx, n), dim3(256), 0, st, (const f16*)src, (f16*)dst, h, w, c, scale, (unsigned)per);
-    else if (dtype == MNET_F16X2) hipLaunchKernelGGL(upsample2x_kernel<hs>, dim3(gx, n), dim3(256), 0, st, (const hs*)src, (hs*)dst, h, w, c, scale, (unsigned)per);
-    else if (dtype == MNET_F16M) hipLaunchKernelGGL(upsample2x_kernel<hm>, dim3(gx, n), dim3(256), 0, st, (const hm*)src, (hm*)dst, h, w, c, scale, (unsigned)per);
-    else hipLaunchKernelGGL(upsample2x_kernel<float>, dim3(gx, n), dim3(256), 0, st, (const float*)src, (float*)dst, h, w, c, scale, (unsigned)per);
+    dispatch_storage(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        auto launch = [&](auto dtag) {
+            using TD = typename decltype(dtag)::type;
+            hipLaunchKernelGGL((upsample2x_kernel<T, TD>), dim3(gx, n), dim3(256), 0, st, (const T*)src, (TD*)dst, h, w, c, scale, (unsigned)per);
+        };
+        if constexpr (is_split4_type<T>) { if (dst_dtype != dtype) return launch(TypeTag<f16>{}); }      // the one other output: plain f16 from a blocked storage
+        launch(tag);
+    });
     MNET_LAUNCH_CHECK("upsample2x");
     return MNET_OK;
 }
@@ -276,6 +276,16 @@ __global__ void __launch_bounds__(256) gn_partial_kernel(const T* __restrict__ x
     }
 }
 
+// (fp64 sum, sum of squares, count, eps) of a group -> its mean (fp64: each caller rounds it where it always did) and 1/sqrt(var + eps); the variance
+// is clamped at 0.  GroupNorm's one finalize: gn_finalize_kernel, gn_finalize_frag_kernel and the AdaIN kernels' group affine.
+struct MeanRstd { double mean; float rstd; };
+__device__ __forceinline__ MeanRstd gn_mean_rstd(double S, double SS, double cnt, float eps) {
+    const double mean = S / cnt;
+    double var = SS / cnt - mean * mean;
+    if (var < 0.0) var = 0.0;
+    return {mean, (float)(1.0 / sqrt(var + (double)eps))};
+}
+
 // stage 2: one thread per (n, channel)
 __global__ void gn_finalize_kernel(const double* __restrict__ partial, int slices, int n_img, int H, int W, int C,
                                    const int* __restrict__ valid_w, const float* __restrict__ gamma,
@@ -290,14 +300,10 @@ __global__ void gn_finalize_kernel(const double* __restrict__ partial, int slice
         S += o[0]; SS += o[1];
     }
     const int vw = valid_w ? min(valid_w[n], W) : W;
-    const double cnt = (double)H * vw * 32.0;
-    const double mean = S / cnt;
-    double var = SS / cnt - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float ga = gamma[c] * rstd;
+    const MeanRstd m = gn_mean_rstd(S, SS, (double)H * vw * 32.0, eps);
+    const float ga = gamma[c] * m.rstd;
     scale[id] = ga;
-    shift[id] = beta[c] - (float)mean * ga;
+    shift[id] = beta[c] - (float)m.mean * ga;
 }
 
 extern "C" int mnet_groupnorm_affine(const void* x, int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c,
@@ -305,15 +311,15 @@ extern "C" int mnet_groupnorm_affine(const void* x, int32_t dtype, int32_t n, in
                                      double* partial, int32_t slices, float* scale, float* shift, void* stream) {
     MNET_CHECK_ARG(x && gamma && beta && partial && scale && shift, "groupnorm: null pointer");
     MNET_CHECK_ARG(n > 0 && h > 0 && w > 0 && c > 0 && slices > 0 && n <= 65535, "groupnorm: bad geometry");
-    MNET_CHECK_ARG(dtype == MNET_F32 || dtype == MNET_F16 || is_split4(dtype), "groupnorm: bad dtype");
-    const int N = dtype == MNET_F32 ? 4 : 8;
+    MNET_CHECK_ARG(is_storage(dtype), "groupnorm: bad dtype");
+    const int N = chunk_n(dtype);
     MNET_CHECK_ALIGN(c % 32 == 0 && 256 % (c / N) == 0 && aligned16(x), "groupnorm: c=%d unsupported", c);
     MNET_CHECK_ALIGN(!is_split4(dtype) || aligned128(x), "groupnorm: split-half tensors must be 128-byte aligned");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == MNET_F16) hipLaunchKernelGGL(gn_partial_kernel<f16>, dim3(slices, n), dim3(256), 0, st, (const f16*)x, h, w, c, valid_w, partial, slices);
-    else if (dtype == MNET_F16X2) hipLaunchKernelGGL(gn_partial_kernel<hs>, dim3(slices, n), dim3(256), 0, st, (const hs*)x, h, w, c, valid_w, partial, slices);
-    else if (dtype == MNET_F16M) hipLaunchKernelGGL(gn_partial_kernel<hm>, dim3(slices, n), dim3(256), 0, st, (const hm*)x, h, w, c, valid_w, partial, slices);
-    else hipLaunchKernelGGL(gn_partial_kernel<float>, dim3(slices, n), dim3(256), 0, st, (const float*)x, h, w, c, valid_w, partial, slices);
+    dispatch_storage(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(gn_partial_kernel<T>, dim3(slices, n), dim3(256), 0, st, (const T*)x, h, w, c, valid_w, partial, slices);
+    });
     MNET_LAUNCH_CHECK("gn_partial");
     const int tot = n * c;
     hipLaunchKernelGGL(gn_finalize_kernel, dim3((tot + 255) / 256), dim3(256), 0, st, partial, slices, n, h, w, c,
@@ -335,16 +341,12 @@ __global__ void __launch_bounds__(64) gn_finalize_frag_kernel(const float* __res
     for (int f = lane; f < frags; f += 64) { const f32x2 v = pp[(size_t)f * G]; S += (double)v[0]; SS += (double)v[1]; }
     S = wave_sum_d(S); SS = wave_sum_d(SS);
     const int vw = valid_w ? min(valid_w[n], W) : W;
-    const double cnt = (double)H * vw * 32.0;
-    const double mean = S / cnt;
-    double var = SS / cnt - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
+    const MeanRstd m = gn_mean_rstd(S, SS, (double)H * vw * 32.0, eps);
     if (lane < 32) {
         const int c = g * 32 + lane;
-        const float ga = gamma[c] * rstd;
+        const float ga = gamma[c] * m.rstd;
         scale[(size_t)n * C + c] = ga;
-        shift[(size_t)n * C + c] = beta[c] - (float)mean * ga;
+        shift[(size_t)n * C + c] = beta[c] - (float)m.mean * ga;
     }
 }
 
@@ -360,41 +362,55 @@ extern "C" int mnet_groupnorm_affine_from_partial(const float* partial, int32_t 
 }
 
 // ============================================================================ AdaIN + crop + concat (per glyph)
-// one workgroup per glyph. pass 1: fp64 sums of the prior crop and the feature crop per channel;
-// pass 2: write [S,S,2C] (zeros beyond the glyph's width).
+// Two forms of one computation, both compositions of the pieces below.  Fused (adain_crop_kernel): one workgroup per glyph; pass 1: fp64 sums of the
+// prior crop and the feature crop per channel; pass 2: write [S,S,2C] (zeros beyond the glyph's width).  In three launches for few glyphs: further down.
+// The statistics [4][C] (pm, ps, fm, fs) sit behind a pointer: LDS in the fused kernel, `stat_g` in the three-launch form.
+
+// what a thread knows of its glyph: the window, and its own chunk column ch and pixel lane pl among the 256 threads
 template <typename T>
-__global__ void __launch_bounds__(256) adain_crop_kernel(const T* __restrict__ prior, const T* __restrict__ feat,
-                                                         T* __restrict__ out, int S, int C, int FW,
-                                                         const int* __restrict__ g_img, const int* __restrict__ g_x1,
-                                                         const int* __restrict__ g_y1, const int* __restrict__ g_w,
-                                                         const float* __restrict__ gn_gamma, const float* __restrict__ gn_beta,
-                                                         float gn_eps, float* __restrict__ gn_scale, float* __restrict__ gn_shift) {
+struct AdainWin {
+    const T* pbase; const T* fbase;                 // row 0 of the glyph's prior [G,S,S,C] and of its image's feature map [B,S,FW,C], at this thread's chunk
+    int S, C, FW, x1, y1, gw, cpp, plane, ch, pl, t;
+    __device__ __forceinline__ AdainWin(const T* prior, const T* feat, int S_, int C_, int FW_, const int* g_img, const int* g_x1, const int* g_y1,
+                                        const int* g_w, int g, int t_) {
+        constexpr int N = Vec<T>::N;
+        S = S_; C = C_; FW = FW_; t = t_;
+        cpp = C / N; plane = 256 / cpp; ch = t % cpp; pl = t / cpp;
+        const int img = g_img[g];
+        x1 = g_x1[g]; y1 = g_y1[g]; gw = g_w[g];
+        pbase = prior + (size_t)g * S * S * C + (size_t)ch * N;
+        fbase = feat + (size_t)img * S * FW * C + (size_t)ch * N;
+    }
+};
+
+// accumulate: this thread's fp64 sums over its lane's pixels of slice sl (of `slices`) of the window -> red[256][N][4] (sum, sum of squares of the prior, of the feature).
+// The sums are taken of (value - pivot), the pivot being the channel's value at the window's first pixel: a channel whose mean is 1e4 times its spread
+// loses 8 digits in sum(x^2) - n mean^2 otherwise, and the fused and the three-launch form (other association) then differ by ulps of fp32 in the std.
+// own_piv: this thread hands the pivots on in stat[c] / stat[2C + c] (stat [4][C]), the slots adain_channel_stats overwrites with the means — before the
+// loop, so that only their fp64 forms stay in registers across it.
+template <typename T>
+__device__ __forceinline__ void adain_accumulate(const AdainWin<T>& w, int sl, int slices, double* red, float* stat, bool own_piv) {
     constexpr int N = Vec<T>::N;
-    extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
-    const int g = blockIdx.x, t = threadIdx.x;
-    const int cpp = C / N, plane = 256 / cpp;
-    const int ch = t % cpp, pl = t / cpp;
-    const int img = g_img[g], x1 = g_x1[g], y1 = g_y1[g], gw = g_w[g];
-    double* red = reinterpret_cast<double*>(dyn);                       // [256][N][4]  (only N*4 per thread)
-    float* stat = reinterpret_cast<float*>(dyn + (size_t)256 * N * 4 * sizeof(double));   // [4][C]: pm, ps, fm, fs
-    double* gsum = reinterpret_cast<double*>(stat + 4 * C);              // [2][2C]: per output channel sum, sum of squares
-    float* gmr = reinterpret_cast<float*>(gsum + 4 * C);                 // [2C/32][2]: group mean, rstd
-    const T* pbase = prior + (size_t)g * S * S * C + (size_t)ch * N;
-    const T* fbase = feat + (size_t)img * S * FW * C + (size_t)ch * N;
-    const int npx = S * gw;
-    // The sums are taken of (value - pivot), the pivot being the channel's value at the window's first pixel: a channel whose mean is 1e4 times its spread
-    // loses 8 digits in sum(x^2) - n mean^2 otherwise, and the fused and the three-launch form (other association) then differ by ulps of fp32 in the std
+    const int C = w.C;
+    const T *pbase = w.pbase, *fbase = w.fbase;
+    const int npx = w.S * w.gw, per = (npx + slices - 1) / slices;
+    const int p_end = min(npx, (sl + 1) * per);
     float pk[N], fk[N];
-    unpackr<T>(ldraw<T>(pbase + (size_t)y1 * C), pk);
-    unpackr<T>(ldraw<T>(fbase + (size_t)x1 * C), fk);
-    double ps_[N], pss[N], fs_[N], fss[N];
+    unpackr<T>(ldraw<T>(pbase + (size_t)w.y1 * C), pk);
+    unpackr<T>(ldraw<T>(fbase + (size_t)w.x1 * C), fk);
+    if (own_piv) {
 #pragma unroll
-    for (int j = 0; j < N; ++j) { ps_[j] = pss[j] = fs_[j] = fss[j] = 0.0; }
-    for (int p = pl; p < npx; p += plane) {
-        const int y = p / gw, x = p - y * gw;
+        for (int j = 0; j < N; ++j) { stat[w.ch * N + j] = pk[j]; stat[2 * C + w.ch * N + j] = fk[j]; }
+    }
+    // (vectors, not double[N]: what the compiler made of the arrays while this loop stood in the kernels; as arrays in a function of its own they become
+    //  4 N scalars, which the vectoriser regroups with more registers in flight — adain_stats_kernel<hs> 128 VGPRs against 123)
+    typedef double f64xN __attribute__((ext_vector_type(N)));
+    f64xN ps_ = 0.0, pss = 0.0, fs_ = 0.0, fss = 0.0;
+    for (int p = sl * per + w.pl; p < p_end; p += w.plane) {
+        const int y = p / w.gw, x = p - y * w.gw;
         float a[N], b[N];
-        unpackr<T>(ldraw<T>(pbase + ((size_t)y * S + (y1 + x)) * C), a);
-        unpackr<T>(ldraw<T>(fbase + ((size_t)y * FW + (x1 + x)) * C), b);
+        unpackr<T>(ldraw<T>(pbase + ((size_t)y * w.S + (w.y1 + x)) * C), a);
+        unpackr<T>(ldraw<T>(fbase + ((size_t)y * w.FW + (w.x1 + x)) * C), b);
 #pragma unroll
         for (int j = 0; j < N; ++j) {
             const double da = (double)a[j] - (double)pk[j], db = (double)b[j] - (double)fk[j];     // exact
@@ -404,67 +420,79 @@ __global__ void __launch_bounds__(256) adain_crop_kernel(const T* __restrict__ p
     }
 #pragma unroll
     for (int j = 0; j < N; ++j) {
-        double* r = red + ((size_t)t * N + j) * 4;
+        double* r = red + ((size_t)w.t * N + j) * 4;
         r[0] = ps_[j]; r[1] = pss[j]; r[2] = fs_[j]; r[3] = fss[j];
     }
-    if (pl == 0) {                      // the pivots, in the slots thread c overwrites with the means
-#pragma unroll
-        for (int j = 0; j < N; ++j) { stat[ch * N + j] = pk[j]; stat[2 * C + ch * N + j] = fk[j]; }
+}
+
+struct AdainSums { double a0, a1, b0, b1; };         // of one channel: sum, sum of squares of (prior - pivot); the same of the feature
+
+// fold: the sums of channel c over its pixel lanes, in lane order
+template <typename T>
+__device__ __forceinline__ AdainSums adain_fold(const AdainWin<T>& w, const double* red, int c) {
+    constexpr int N = Vec<T>::N;
+    const int chn = c / N, j = c % N;
+    AdainSums s = {0, 0, 0, 0};
+    for (int q = 0; q < w.plane; ++q) {
+        const double* r = red + ((size_t)(q * w.cpp + chn) * N + j) * 4;
+        s.a0 += r[0]; s.a1 += r[1]; s.b0 += r[2]; s.b1 += r[3];
+    }
+    return s;
+}
+
+// channel statistics: the sums s of (value - pivot) over cnt pixels and the pivots in stat[c] / stat[2C + c] -> stat[c], [C + c], [2C + c], [3C + c] = prior
+// mean, prior std, feature mean, feature std; gn: also gsum [2][2C], the sum / sum of squares of the [.., 2C] OUTPUT per channel over the window
+__device__ __forceinline__ void adain_channel_stats(AdainSums s, double cnt, float* stat, int C, int c, double* gsum, bool gn) {
+    const double pd = s.a0 / cnt, fd = s.b0 / cnt;                      // means of (value - pivot)
+    const double pm = (double)stat[c] + pd, fm = (double)stat[2 * C + c] + fd;
+    double pdev = s.a1 - cnt * pd * pd, fdev = s.b1 - cnt * fd * fd;    // sums of squared deviations from the mean
+    if (pdev < 0) pdev = 0; if (fdev < 0) fdev = 0;
+    // unbiased variance (torch .var default, networks.py:522) + eps 1e-5, then sqrt
+    const double pv = pdev / (cnt - 1.0), fv = fdev / (cnt - 1.0);
+    const float psd = sqrtf((float)pv + 1e-5f), fsd = sqrtf((float)fv + 1e-5f);
+    stat[c] = (float)pm; stat[C + c] = psd; stat[2 * C + c] = (float)fm; stat[3 * C + c] = fsd;
+    if (gn) {           // in closed form: channel c (restyled prior) = (p - pm)/ps*fs + fm → sum = cnt*fm, sumsq = r^2 * sum (p-pm)^2 + cnt*fm^2
+                        // channel C + c (feature crop) = the accumulated sums themselves
+        const double r = (double)fsd / (double)psd;
+        gsum[c] = cnt * fm;            gsum[2 * C + c] = r * r * pdev + cnt * fm * fm;
+        gsum[C + c] = cnt * fm;        gsum[3 * C + c] = fdev + cnt * fm * fm;
+    }
+}
+
+// group affine: GroupNorm(2C/32 groups) of the concatenated output (networks.py:508: norm1 of conv_*_fuse) from gsum → gn_scale / gn_shift of glyph g.
+// gmr [2C/32][2]: group mean, rstd (LDS, like gsum)
+__device__ __forceinline__ void adain_group_affine(const double* gsum, float* gmr, int C, int npx, int g, int t, const float* gn_gamma, const float* gn_beta,
+                                                   float gn_eps, float* gn_scale, float* gn_shift) {
+    const int G2 = 2 * C / 32;
+    for (int gq = t; gq < G2; gq += 256) {
+        double s1 = 0.0, s2 = 0.0;
+        for (int k = 0; k < 32; ++k) { s1 += gsum[gq * 32 + k]; s2 += gsum[2 * C + gq * 32 + k]; }
+        const MeanRstd m = gn_mean_rstd(s1, s2, (double)npx * 32.0, gn_eps);
+        gmr[2 * gq] = (float)m.mean; gmr[2 * gq + 1] = m.rstd;
     }
     __syncthreads();
-    // thread c (< C) folds the pixel lanes of channel c
-    for (int c = t; c < C; c += 256) {
-        const int chn = c / N, j = c % N;
-        double a0 = 0, a1 = 0, b0 = 0, b1 = 0;
-        for (int q = 0; q < plane; ++q) {
-            const double* r = red + ((size_t)(q * cpp + chn) * N + j) * 4;
-            a0 += r[0]; a1 += r[1]; b0 += r[2]; b1 += r[3];
-        }
-        const double cnt = (double)npx;
-        const double pd = a0 / cnt, fd = b0 / cnt;                      // means of (value - pivot)
-        const double pm = (double)stat[c] + pd, fm = (double)stat[2 * C + c] + fd;
-        double pdev = a1 - cnt * pd * pd, fdev = b1 - cnt * fd * fd;    // sums of squared deviations from the mean
-        if (pdev < 0) pdev = 0; if (fdev < 0) fdev = 0;
-        // unbiased variance (torch .var default, networks.py:522) + eps 1e-5, then sqrt
-        const double pv = pdev / (cnt - 1.0), fv = fdev / (cnt - 1.0);
-        stat[c] = (float)pm; stat[C + c] = sqrtf((float)pv + 1e-5f);
-        stat[2 * C + c] = (float)fm; stat[3 * C + c] = sqrtf((float)fv + 1e-5f);
-        if (gn_scale) {     // per-channel sum / sum of squares of the [.., 2C] OUTPUT over the window, in closed form:
-                            // channel c (restyled prior) = (p - pm)/ps*fs + fm → sum = cnt*fm, sumsq = r^2 * sum (p-pm)^2 + cnt*fm^2
-                            // channel C + c (feature crop) = the accumulated sums themselves
-            const double r = (double)stat[3 * C + c] / (double)stat[C + c];
-            gsum[c] = cnt * fm;            gsum[2 * C + c] = r * r * pdev + cnt * fm * fm;
-            gsum[C + c] = cnt * fm;        gsum[3 * C + c] = fdev + cnt * fm * fm;
-        }
+    for (int c = t; c < 2 * C; c += 256) {
+        const float ga = gn_gamma[c] * gmr[2 * (c / 32) + 1];
+        gn_scale[(size_t)g * 2 * C + c] = ga;
+        gn_shift[(size_t)g * 2 * C + c] = gn_beta[c] - gmr[2 * (c / 32)] * ga;
     }
-    __syncthreads();
-    if (gn_scale) {         // GroupNorm(2C/32 groups) of the concatenated output (networks.py:508: norm1 of conv_*_fuse) → affine
-        const int G2 = 2 * C / 32;
-        for (int gq = t; gq < G2; gq += 256) {
-            double s1 = 0.0, s2 = 0.0;
-            for (int k = 0; k < 32; ++k) { s1 += gsum[gq * 32 + k]; s2 += gsum[2 * C + gq * 32 + k]; }
-            const double cnt = (double)npx * 32.0;
-            const double mean = s1 / cnt;
-            double var = s2 / cnt - mean * mean;
-            if (var < 0.0) var = 0.0;
-            gmr[2 * gq] = (float)mean; gmr[2 * gq + 1] = (float)(1.0 / sqrt(var + (double)gn_eps));
-        }
-        __syncthreads();
-        for (int c = t; c < 2 * C; c += 256) {
-            const float ga = gn_gamma[c] * gmr[2 * (c / 32) + 1];
-            gn_scale[(size_t)g * 2 * C + c] = ga;
-            gn_shift[(size_t)g * 2 * C + c] = gn_beta[c] - gmr[2 * (c / 32)] * ga;
-        }
-    }
-    T* obase = out + (size_t)g * S * S * 2 * C;
-    const int c0 = ch * N;
-    for (int p = pl; p < S * S; p += plane) {
-        const int y = p / S, x = p - y * S;
+}
+
+// apply: this thread's lane of the pixels of slice sl (of `slices`) of the glyph's S x S x 2C output obase: the restyled prior, then the feature crop; zeros beyond gw
+template <typename T>
+__device__ __forceinline__ void adain_apply(const AdainWin<T>& w, const float* stat, T* obase, int sl, int slices) {
+    constexpr int N = Vec<T>::N;
+    const int C = w.C, S = w.S;
+    const T *pbase = w.pbase, *fbase = w.fbase;
+    const int c0 = w.ch * N;
+    const int per = (S * S + slices - 1) / slices, p_end = min(S * S, (sl + 1) * per);
+    for (int p = sl * per + w.pl; p < p_end; p += w.plane) {
+        const int y = p / w.S, x = p - y * w.S;
         Raw<T> oa = zero_raw<T>(), ob = zero_raw<T>();
-        if (x < gw) {
+        if (x < w.gw) {
             float a[N], o[N];
-            unpackr<T>(ldraw<T>(pbase + ((size_t)y * S + (y1 + x)) * C), a);
-            ob = ldraw<T>(fbase + ((size_t)y * FW + (x1 + x)) * C);
+            unpackr<T>(ldraw<T>(pbase + ((size_t)y * w.S + (w.y1 + x)) * C), a);
+            ob = ldraw<T>(fbase + ((size_t)y * w.FW + (w.x1 + x)) * C);
 #pragma unroll
             for (int j = 0; j < N; ++j) {
                 const int c = c0 + j;
@@ -477,13 +505,39 @@ __global__ void __launch_bounds__(256) adain_crop_kernel(const T* __restrict__ p
     }
 }
 
+template <typename T>
+__global__ void __launch_bounds__(256) adain_crop_kernel(const T* __restrict__ prior, const T* __restrict__ feat,
+                                                         T* __restrict__ out, int S, int C, int FW,
+                                                         const int* __restrict__ g_img, const int* __restrict__ g_x1,
+                                                         const int* __restrict__ g_y1, const int* __restrict__ g_w,
+                                                         const float* __restrict__ gn_gamma, const float* __restrict__ gn_beta,
+                                                         float gn_eps, float* __restrict__ gn_scale, float* __restrict__ gn_shift) {
+    constexpr int N = Vec<T>::N;
+    extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
+    const int g = blockIdx.x, t = threadIdx.x;
+    const AdainWin<T> w(prior, feat, S, C, FW, g_img, g_x1, g_y1, g_w, g, t);
+    double* red = reinterpret_cast<double*>(dyn);                       // [256][N][4]  (only N*4 per thread)
+    float* stat = reinterpret_cast<float*>(dyn + (size_t)256 * N * 4 * sizeof(double));   // [4][C]: pm, ps, fm, fs
+    double* gsum = reinterpret_cast<double*>(stat + 4 * C);              // [2][2C]: per output channel sum, sum of squares
+    float* gmr = reinterpret_cast<float*>(gsum + 4 * C);                 // [2C/32][2]: group mean, rstd
+    const int npx = S * w.gw;
+    adain_accumulate<T>(w, 0, 1, red, stat, w.pl == 0);
+    __syncthreads();
+    for (int c = t; c < C; c += 256) {      // thread c (< C) folds the pixel lanes of channel c
+        adain_channel_stats(adain_fold<T>(w, red, c), (double)npx, stat, C, c, gsum, gn_scale != nullptr);
+    }
+    __syncthreads();
+    if (gn_scale) adain_group_affine(gsum, gmr, C, npx, g, t, gn_gamma, gn_beta, gn_eps, gn_scale, gn_shift);
+    adain_apply<T>(w, stat, out + (size_t)g * S * S * 2 * C, 0, 1);
+}
+
 static int adain_launch(const void* prior, const void* feat, void* out, int32_t dtype, int32_t G, int32_t S, int32_t C,
                         int32_t feat_w, const int32_t* g_img, const int32_t* g_x1, const int32_t* g_y1, const int32_t* g_w,
                         const float* gamma, const float* beta, float eps, float* scale, float* shift, void* stream) {
     MNET_CHECK_ARG(prior && feat && out && g_img && g_x1 && g_y1 && g_w, "adain: null pointer");
     MNET_CHECK_ARG(G > 0 && S > 0 && C > 0 && feat_w >= S, "adain: bad geometry");
-    MNET_CHECK_ARG(dtype == MNET_F32 || dtype == MNET_F16 || is_split4(dtype), "adain: bad dtype");
-    const int N = dtype == MNET_F32 ? 4 : 8;
+    MNET_CHECK_ARG(is_storage(dtype), "adain: bad dtype");
+    const int N = chunk_n(dtype);
     MNET_CHECK_ALIGN(C % N == 0 && 256 % (C / N) == 0 && C % 32 == 0 && aligned16(prior) && aligned16(feat) && aligned16(out),
                      "adain: C=%d unsupported or unaligned", C);
     MNET_CHECK_ALIGN(!is_split4(dtype) || (aligned128(prior) && aligned128(feat) && aligned128(out)), "adain: split-half tensors must be 128-byte aligned");
@@ -495,25 +549,15 @@ static int adain_launch(const void* prior, const void* feat, void* out, int32_t 
                        (size_t)(2 * C / 32) * 2 * sizeof(float);
     // a workgroup can have 160 KiB of LDS: C = 2048 in an 8-wide storage asks for 164,864 bytes — refused here, before any HIP call, like adain_split's lds2
     MNET_CHECK_ARG(lds <= 160 * 1024, "adain: C=%d too large (%zu bytes of LDS per workgroup, 163840 at most)", C, lds);
-    static thread_local size_t lds_all[256][4] = {};                   // attribute raised once per (device, size) (not during graph capture replays)
-    size_t* lds_set = lds_all[DeviceOnce::dev()];
-    if (dtype == MNET_F16X2) {
-        if (lds > lds_set[2]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(adain_crop_kernel<hs>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); lds_set[2] = lds; }
-        hipLaunchKernelGGL(adain_crop_kernel<hs>, dim3(G), dim3(256), lds, st, (const hs*)prior, (const hs*)feat, (hs*)out, S, C, feat_w,
+    dispatch_storage(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        // per instantiation, per thread, per device: the attribute is raised when a larger size is asked for, never lowered (and not during graph capture replays)
+        static thread_local size_t lds_set[256] = {};
+        size_t& have = lds_set[DeviceOnce::dev()];
+        if (lds > have) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(adain_crop_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); have = lds; }
+        hipLaunchKernelGGL(adain_crop_kernel<T>, dim3(G), dim3(256), lds, st, (const T*)prior, (const T*)feat, (T*)out, S, C, feat_w,
                            g_img, g_x1, g_y1, g_w, gamma, beta, eps, scale, shift);
-    } else if (dtype == MNET_F16M) {
-        if (lds > lds_set[3]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(adain_crop_kernel<hm>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); lds_set[3] = lds; }
-        hipLaunchKernelGGL(adain_crop_kernel<hm>, dim3(G), dim3(256), lds, st, (const hm*)prior, (const hm*)feat, (hm*)out, S, C, feat_w,
-                           g_img, g_x1, g_y1, g_w, gamma, beta, eps, scale, shift);
-    } else if (dtype == MNET_F16) {
-        if (lds > lds_set[1]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(adain_crop_kernel<f16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); lds_set[1] = lds; }
-        hipLaunchKernelGGL(adain_crop_kernel<f16>, dim3(G), dim3(256), lds, st, (const f16*)prior, (const f16*)feat, (f16*)out, S, C, feat_w,
-                           g_img, g_x1, g_y1, g_w, gamma, beta, eps, scale, shift);
-    } else {
-        if (lds > lds_set[0]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(adain_crop_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); lds_set[0] = lds; }
-        hipLaunchKernelGGL(adain_crop_kernel<float>, dim3(G), dim3(256), lds, st, (const float*)prior, (const float*)feat, (float*)out, S, C, feat_w,
-                           g_img, g_x1, g_y1, g_w, gamma, beta, eps, scale, shift);
-    }
+    });
     MNET_LAUNCH_CHECK("adain_crop");
     return MNET_OK;
 }
@@ -537,62 +581,24 @@ extern "C" int mnet_adain_crop_concat_gn(const void* prior, const void* feat, vo
 // One workgroup per glyph walks its window as a chain of exposed load latencies (≈380 us for a 64x64x256 window): fine when a
 // thousand glyphs share the chip (batch 64: the kernel is HBM-bound), but a single strip has 16.  Here `slices` workgroups share
 // a glyph: (1) per-slice fp64 partial sums, (2) one workgroup per glyph folds them in slice order into the AdaIN statistics and
-// the GroupNorm affine, (3) `slices` workgroups write the output.  The arithmetic per element is the fused kernel's; only the
+// the GroupNorm affine, (3) `slices` workgroups write the output.  The arithmetic per element is the fused kernel's — the same functions; only the
 // association of the fp64 sums differs (slice-major instead of lane-major), i.e. results agree to fp64 rounding of the sums.
 template <typename T>
 __global__ void __launch_bounds__(256) adain_stats_kernel(const T* __restrict__ prior, const T* __restrict__ feat, int S, int C, int FW,
                                                           const int* __restrict__ g_img, const int* __restrict__ g_x1,
                                                           const int* __restrict__ g_y1, const int* __restrict__ g_w,
                                                           double* __restrict__ partial, float* __restrict__ stat_g, int slices) {
-    constexpr int N = Vec<T>::N;
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
     double* red = reinterpret_cast<double*>(dyn);                       // [256][N][4]
     const int g = blockIdx.y, sl = blockIdx.x, t = threadIdx.x;
-    const int cpp = C / N, plane = 256 / cpp;
-    const int ch = t % cpp, pl = t / cpp;
-    const int img = g_img[g], x1 = g_x1[g], y1 = g_y1[g], gw = g_w[g];
-    const T* pbase = prior + (size_t)g * S * S * C + (size_t)ch * N;
-    const T* fbase = feat + (size_t)img * S * FW * C + (size_t)ch * N;
-    const int npx = S * gw, per = (npx + slices - 1) / slices;
-    const int p_end = min(npx, (sl + 1) * per);
-    float pk[N], fk[N];                                                  // the pivots of adain_crop_kernel: the same for every slice of the glyph
-    unpackr<T>(ldraw<T>(pbase + (size_t)y1 * C), pk);
-    unpackr<T>(ldraw<T>(fbase + (size_t)x1 * C), fk);
-    if (sl == 0 && pl == 0) {                                            // handed to adain_finalize_kernel in the rows it overwrites with the means
-        float* st = stat_g + (size_t)g * 4 * C + (size_t)ch * N;
-#pragma unroll
-        for (int j = 0; j < N; ++j) { st[j] = pk[j]; st[2 * C + j] = fk[j]; }
-    }
-    double ps_[N], pss[N], fs_[N], fss[N];
-#pragma unroll
-    for (int j = 0; j < N; ++j) { ps_[j] = pss[j] = fs_[j] = fss[j] = 0.0; }
-    for (int p = sl * per + pl; p < p_end; p += plane) {
-        const int y = p / gw, x = p - y * gw;
-        float a[N], b[N];
-        unpackr<T>(ldraw<T>(pbase + ((size_t)y * S + (y1 + x)) * C), a);
-        unpackr<T>(ldraw<T>(fbase + ((size_t)y * FW + (x1 + x)) * C), b);
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-            const double da = (double)a[j] - (double)pk[j], db = (double)b[j] - (double)fk[j];     // exact
-            ps_[j] += da; pss[j] += da * da;
-            fs_[j] += db; fss[j] += db * db;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        double* r = red + ((size_t)t * N + j) * 4;
-        r[0] = ps_[j]; r[1] = pss[j]; r[2] = fs_[j]; r[3] = fss[j];
-    }
+    const AdainWin<T> w(prior, feat, S, C, FW, g_img, g_x1, g_y1, g_w, g, t);
+    // the pivots are the same for every slice of the glyph: slice 0 hands them to adain_finalize_kernel
+    adain_accumulate<T>(w, sl, slices, red, stat_g + (size_t)g * 4 * C, sl == 0 && w.pl == 0);
     __syncthreads();
     for (int c = t; c < C; c += 256) {
-        const int chn = c / N, j = c % N;
-        double a0 = 0, a1 = 0, b0 = 0, b1 = 0;
-        for (int q = 0; q < plane; ++q) {
-            const double* r = red + ((size_t)(q * cpp + chn) * N + j) * 4;
-            a0 += r[0]; a1 += r[1]; b0 += r[2]; b1 += r[3];
-        }
+        const AdainSums s = adain_fold<T>(w, red, c);
         double* o = partial + (((size_t)g * slices + sl) * C + c) * 4;
-        o[0] = a0; o[1] = a1; o[2] = b0; o[3] = b1;
+        o[0] = s.a0; o[1] = s.a1; o[2] = s.b0; o[3] = s.b1;
     }
 }
 
@@ -606,45 +612,17 @@ __global__ void __launch_bounds__(256) adain_finalize_kernel(const double* __res
     float* gmr = reinterpret_cast<float*>(gsum + 4 * C);                 // [2C/32][2]
     const int g = blockIdx.x, t = threadIdx.x;
     const int npx = S * g_w[g];
-    float* st = stat + (size_t)g * 4 * C;
     for (int c = t; c < C; c += 256) {
-        double a0 = 0, a1 = 0, b0 = 0, b1 = 0;
+        AdainSums s = {0, 0, 0, 0};
         for (int sl = 0; sl < slices; ++sl) {
             const double* r = partial + (((size_t)g * slices + sl) * C + c) * 4;
-            a0 += r[0]; a1 += r[1]; b0 += r[2]; b1 += r[3];
+            s.a0 += r[0]; s.a1 += r[1]; s.b0 += r[2]; s.b1 += r[3];
         }
-        const double cnt = (double)npx;
-        const double pd = a0 / cnt, fd = b0 / cnt;                      // the sums are of (value - pivot); adain_stats_kernel left the pivots in st
-        const double pm = (double)st[c] + pd, fm = (double)st[2 * C + c] + fd;
-        double pdev = a1 - cnt * pd * pd, fdev = b1 - cnt * fd * fd;
-        if (pdev < 0) pdev = 0; if (fdev < 0) fdev = 0;
-        const double pv = pdev / (cnt - 1.0), fv = fdev / (cnt - 1.0);
-        const float psd = sqrtf((float)pv + 1e-5f), fsd = sqrtf((float)fv + 1e-5f);
-        st[c] = (float)pm; st[C + c] = psd; st[2 * C + c] = (float)fm; st[3 * C + c] = fsd;
-        if (gn_scale) {
-            const double r = (double)fsd / (double)psd;
-            gsum[c] = cnt * fm;            gsum[2 * C + c] = r * r * pdev + cnt * fm * fm;
-            gsum[C + c] = cnt * fm;        gsum[3 * C + c] = fdev + cnt * fm * fm;
-        }
+        adain_channel_stats(s, (double)npx, stat + (size_t)g * 4 * C, C, c, gsum, gn_scale != nullptr);
     }
     if (!gn_scale) return;
     __syncthreads();
-    const int G2 = 2 * C / 32;
-    for (int gq = t; gq < G2; gq += 256) {
-        double s1 = 0.0, s2 = 0.0;
-        for (int k = 0; k < 32; ++k) { s1 += gsum[gq * 32 + k]; s2 += gsum[2 * C + gq * 32 + k]; }
-        const double cnt = (double)npx * 32.0;
-        const double mean = s1 / cnt;
-        double var = s2 / cnt - mean * mean;
-        if (var < 0.0) var = 0.0;
-        gmr[2 * gq] = (float)mean; gmr[2 * gq + 1] = (float)(1.0 / sqrt(var + (double)gn_eps));
-    }
-    __syncthreads();
-    for (int c = t; c < 2 * C; c += 256) {
-        const float ga = gn_gamma[c] * gmr[2 * (c / 32) + 1];
-        gn_scale[(size_t)g * 2 * C + c] = ga;
-        gn_shift[(size_t)g * 2 * C + c] = gn_beta[c] - gmr[2 * (c / 32)] * ga;
-    }
+    adain_group_affine(gsum, gmr, C, npx, g, t, gn_gamma, gn_beta, gn_eps, gn_scale, gn_shift);
 }
 
 template <typename T>
@@ -652,37 +630,13 @@ __global__ void __launch_bounds__(256) adain_apply_kernel(const T* __restrict__ 
                                                           int S, int C, int FW, const int* __restrict__ g_img,
                                                           const int* __restrict__ g_x1, const int* __restrict__ g_y1,
                                                           const int* __restrict__ g_w, const float* __restrict__ stat_g, int slices) {
-    constexpr int N = Vec<T>::N;
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
     float* stat = reinterpret_cast<float*>(dyn);                         // [4][C]
     const int g = blockIdx.y, sl = blockIdx.x, t = threadIdx.x;
-    const int cpp = C / N, plane = 256 / cpp;
-    const int ch = t % cpp, pl = t / cpp;
-    const int img = g_img[g], x1 = g_x1[g], y1 = g_y1[g], gw = g_w[g];
+    const AdainWin<T> w(prior, feat, S, C, FW, g_img, g_x1, g_y1, g_w, g, t);
     for (int i = t; i < 4 * C; i += 256) stat[i] = stat_g[(size_t)g * 4 * C + i];
     __syncthreads();
-    const T* pbase = prior + (size_t)g * S * S * C + (size_t)ch * N;
-    const T* fbase = feat + (size_t)img * S * FW * C + (size_t)ch * N;
-    T* obase = out + (size_t)g * S * S * 2 * C;
-    const int c0 = ch * N;
-    const int per = (S * S + slices - 1) / slices, p_end = min(S * S, (sl + 1) * per);
-    for (int p = sl * per + pl; p < p_end; p += plane) {
-        const int y = p / S, x = p - y * S;
-        Raw<T> oa = zero_raw<T>(), ob = zero_raw<T>();
-        if (x < gw) {
-            float a[N], o[N];
-            unpackr<T>(ldraw<T>(pbase + ((size_t)y * S + (y1 + x)) * C), a);
-            ob = ldraw<T>(fbase + ((size_t)y * FW + (x1 + x)) * C);
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-                const int c = c0 + j;
-                o[j] = (a[j] - stat[c]) / stat[C + c] * stat[3 * C + c] + stat[2 * C + c];
-            }
-            oa = packr<T>(o);
-        }
-        straw<T>(obase + (size_t)p * 2 * C + c0, oa);
-        straw<T>(obase + (size_t)p * 2 * C + C + c0, ob);
-    }
+    adain_apply<T>(w, stat, out + (size_t)g * S * S * 2 * C, sl, slices);
 }
 
 extern "C" int mnet_adain_crop_concat_split(const void* prior, const void* feat, void* out, int32_t dtype, int32_t G,
@@ -692,11 +646,11 @@ extern "C" int mnet_adain_crop_concat_split(const void* prior, const void* feat,
                                             double* partial, float* stat, int32_t slices, void* stream) {
     MNET_CHECK_ARG(prior && feat && out && g_img && g_x1 && g_y1 && g_w && partial && stat, "adain_split: null pointer");
     MNET_CHECK_ARG(G > 0 && G <= 65535 && S > 0 && C > 0 && feat_w >= S && slices > 0 && slices <= 1024, "adain_split: bad geometry");
-    MNET_CHECK_ARG(dtype == MNET_F32 || dtype == MNET_F16 || is_split4(dtype), "adain_split: bad dtype");
+    MNET_CHECK_ARG(is_storage(dtype), "adain_split: bad dtype");
     MNET_CHECK_ALIGN(!is_split4(dtype) || (aligned128(prior) && aligned128(feat) && aligned128(out)), "adain_split: split-half tensors must be 128-byte aligned");
     MNET_CHECK_ARG((gamma != nullptr) == (beta != nullptr) && (gamma != nullptr) == (scale != nullptr) && (gamma != nullptr) == (shift != nullptr),
                    "adain_split: gamma, beta, scale, shift go together");
-    const int N = dtype == MNET_F32 ? 4 : 8;
+    const int N = chunk_n(dtype);
     MNET_CHECK_ALIGN(C % N == 0 && 256 % (C / N) == 0 && C % 32 == 0 && aligned16(prior) && aligned16(feat) && aligned16(out),
                      "adain_split: C=%d unsupported or unaligned", C);
     const size_t lds1 = (size_t)256 * N * 4 * sizeof(double);
@@ -704,26 +658,19 @@ extern "C" int mnet_adain_crop_concat_split(const void* prior, const void* feat,
     const size_t lds3 = (size_t)4 * C * sizeof(float);
     MNET_CHECK_ARG(lds2 <= 65536 && lds3 <= 65536, "adain_split: C=%d too large", C);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    static thread_local DeviceOnce attr_once;
-    if (!attr_once.done()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(adain_stats_kernel<f16>), hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 8 * 4 * 8);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(adain_stats_kernel<hs>), hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 8 * 4 * 8);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(adain_stats_kernel<hm>), hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 8 * 4 * 8);
-        attr_once.mark();
-    }
-    if (dtype == MNET_F16) hipLaunchKernelGGL(adain_stats_kernel<f16>, dim3(slices, G), dim3(256), lds1, st, (const f16*)prior, (const f16*)feat, S, C, feat_w, g_img, g_x1, g_y1, g_w, partial, stat, slices);
-    else if (dtype == MNET_F16X2) hipLaunchKernelGGL(adain_stats_kernel<hs>, dim3(slices, G), dim3(256), lds1, st, (const hs*)prior, (const hs*)feat, S, C, feat_w, g_img, g_x1, g_y1, g_w, partial, stat, slices);
-    else if (dtype == MNET_F16M) hipLaunchKernelGGL(adain_stats_kernel<hm>, dim3(slices, G), dim3(256), lds1, st, (const hm*)prior, (const hm*)feat, S, C, feat_w, g_img, g_x1, g_y1, g_w, partial, stat, slices);
-    else hipLaunchKernelGGL(adain_stats_kernel<float>, dim3(slices, G), dim3(256), lds1, st, (const float*)prior, (const float*)feat, S, C, feat_w, g_img, g_x1, g_y1, g_w, partial, stat, slices);
-    MNET_LAUNCH_CHECK("adain_stats");
-    hipLaunchKernelGGL(adain_finalize_kernel, dim3(G), dim3(256), lds2, st, partial, slices, S, C, g_w, stat, gamma, beta, eps, scale, shift);
-    MNET_LAUNCH_CHECK("adain_finalize");
-    if (dtype == MNET_F16) hipLaunchKernelGGL(adain_apply_kernel<f16>, dim3(slices, G), dim3(256), lds3, st, (const f16*)prior, (const f16*)feat, (f16*)out, S, C, feat_w, g_img, g_x1, g_y1, g_w, stat, slices);
-    else if (dtype == MNET_F16X2) hipLaunchKernelGGL(adain_apply_kernel<hs>, dim3(slices, G), dim3(256), lds3, st, (const hs*)prior, (const hs*)feat, (hs*)out, S, C, feat_w, g_img, g_x1, g_y1, g_w, stat, slices);
-    else if (dtype == MNET_F16M) hipLaunchKernelGGL(adain_apply_kernel<hm>, dim3(slices, G), dim3(256), lds3, st, (const hm*)prior, (const hm*)feat, (hm*)out, S, C, feat_w, g_img, g_x1, g_y1, g_w, stat, slices);
-    else hipLaunchKernelGGL(adain_apply_kernel<float>, dim3(slices, G), dim3(256), lds3, st, (const float*)prior, (const float*)feat, (float*)out, S, C, feat_w, g_img, g_x1, g_y1, g_w, stat, slices);
-    MNET_LAUNCH_CHECK("adain_apply");
-    return MNET_OK;
+    return dispatch_storage(dtype, [&](auto tag) -> int {
+        using T = typename decltype(tag)::type;
+        const T *p = (const T*)prior, *f = (const T*)feat;
+        static thread_local DeviceOnce attr_once;      // per instantiation, per thread, per device: lds1 is a constant of T (64 KiB for the 8-wide storages)
+        if (!attr_once.done()) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(adain_stats_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1); attr_once.mark(); }
+        hipLaunchKernelGGL(adain_stats_kernel<T>, dim3(slices, G), dim3(256), lds1, st, p, f, S, C, feat_w, g_img, g_x1, g_y1, g_w, partial, stat, slices);
+        MNET_LAUNCH_CHECK("adain_stats");
+        hipLaunchKernelGGL(adain_finalize_kernel, dim3(G), dim3(256), lds2, st, partial, slices, S, C, g_w, stat, gamma, beta, eps, scale, shift);
+        MNET_LAUNCH_CHECK("adain_finalize");
+        hipLaunchKernelGGL(adain_apply_kernel<T>, dim3(slices, G), dim3(256), lds3, st, p, f, (T*)out, S, C, feat_w, g_img, g_x1, g_y1, g_w, stat, slices);
+        MNET_LAUNCH_CHECK("adain_apply");
+        return MNET_OK;
+    });
 }
 
 // ============================================================================ ordered glyph scatter
@@ -798,8 +745,8 @@ extern "C" int mnet_glyph_scatter_affine(const void* feat, const void* scale, co
                                          const int32_t* g_start, const int32_t* g_x1, const int32_t* g_w, void* stream) {
     MNET_CHECK_ARG(feat && scale && shift && out && g_start && g_x1 && g_w, "scatter: null pointer");
     MNET_CHECK_ARG(B > 0 && S > 0 && C > 0 && feat_w > 0, "scatter: bad geometry");
-    MNET_CHECK_ARG(dtype == MNET_F32 || dtype == MNET_F16 || is_split4(dtype), "scatter: bad dtype");
-    const int N = dtype == MNET_F32 ? 4 : 8;
+    MNET_CHECK_ARG(is_storage(dtype), "scatter: bad dtype");
+    const int N = chunk_n(dtype);
     MNET_CHECK_ALIGN(!is_split4(dtype) || (C % 32 == 0 && aligned128(feat) && aligned128(scale) && aligned128(shift) && aligned128(out)),
                      "scatter: split-half needs C %% 32 == 0, 128-byte aligned");
     MNET_CHECK_ALIGN(C % N == 0 && aligned16(feat) && aligned16(scale) && aligned16(shift) && aligned16(out),
@@ -809,10 +756,11 @@ extern "C" int mnet_glyph_scatter_affine(const void* feat, const void* scale, co
     const int runs = (S + MNET_SCATTER_RUN - 1) / MNET_SCATTER_RUN;
     MNET_CHECK_ARG(runs <= 65535, "scatter: S too large");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == MNET_F16) hipLaunchKernelGGL(glyph_scatter_kernel<f16>, dim3(blocks, B, runs), dim3(256), 0, st, (const f16*)feat, (const f16*)scale, (const f16*)shift, (f16*)out, S, C, feat_w, g_start, g_x1, g_w);
-    else if (dtype == MNET_F16X2) hipLaunchKernelGGL(glyph_scatter_kernel<hs>, dim3(blocks, B, runs), dim3(256), 0, st, (const hs*)feat, (const hs*)scale, (const hs*)shift, (hs*)out, S, C, feat_w, g_start, g_x1, g_w);
-    else if (dtype == MNET_F16M) hipLaunchKernelGGL(glyph_scatter_kernel<hm>, dim3(blocks, B, runs), dim3(256), 0, st, (const hm*)feat, (const hm*)scale, (const hm*)shift, (hm*)out, S, C, feat_w, g_start, g_x1, g_w);
-    else hipLaunchKernelGGL(glyph_scatter_kernel<float>, dim3(blocks, B, runs), dim3(256), 0, st, (const float*)feat, (const float*)scale, (const float*)shift, (float*)out, S, C, feat_w, g_start, g_x1, g_w);
+    dispatch_storage(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(glyph_scatter_kernel<T>, dim3(blocks, B, runs), dim3(256), 0, st, (const T*)feat, (const T*)scale, (const T*)shift, (T*)out, S, C, feat_w,
+                           g_start, g_x1, g_w);
+    });
     MNET_LAUNCH_CHECK("glyph_scatter");
     return MNET_OK;
 }
@@ -848,17 +796,17 @@ extern "C" int mnet_embed_gather_scaled(const float* emb, const int64_t* labels,
                                         int32_t nc, int32_t C, int32_t num_classes, void* stream) {
     MNET_CHECK_ARG(emb && labels && out && N_ > 0 && nc > 0 && C > 0 && num_classes > 0, "embed_gather: bad args");
     MNET_CHECK_ALIGN(aligned16(scale), "embed_gather: unaligned scale");
-    MNET_CHECK_ARG(dtype == MNET_F32 || dtype == MNET_F16 || is_split4(dtype), "embed_gather: bad dtype");
-    const int N = dtype == MNET_F32 ? 4 : 8;
+    MNET_CHECK_ARG(is_storage(dtype), "embed_gather: bad dtype");
+    const int N = chunk_n(dtype);
     MNET_CHECK_ALIGN(C % N == 0 && aligned16(out), "embed_gather: unaligned");
     MNET_CHECK_ALIGN(!is_split4(dtype) || (C % 32 == 0 && aligned128(out)), "embed_gather: split-half needs C %% 32 == 0, 128-byte aligned");
     const long long total = (long long)N_ * 16 * nc * (C / N);
     const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == MNET_F16) hipLaunchKernelGGL(embed_gather_kernel<f16>, dim3(blocks), dim3(256), 0, st, emb, labels, scale, (f16*)out, nc, C, total);
-    else if (dtype == MNET_F16X2) hipLaunchKernelGGL(embed_gather_kernel<hs>, dim3(blocks), dim3(256), 0, st, emb, labels, scale, (hs*)out, nc, C, total);
-    else if (dtype == MNET_F16M) hipLaunchKernelGGL(embed_gather_kernel<hm>, dim3(blocks), dim3(256), 0, st, emb, labels, scale, (hm*)out, nc, C, total);
-    else hipLaunchKernelGGL(embed_gather_kernel<float>, dim3(blocks), dim3(256), 0, st, emb, labels, scale, (float*)out, nc, C, total);
+    dispatch_storage(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(embed_gather_kernel<T>, dim3(blocks), dim3(256), 0, st, emb, labels, scale, (T*)out, nc, C, total);
+    });
     MNET_LAUNCH_CHECK("embed_gather");
     return MNET_OK;
 }
@@ -950,17 +898,9 @@ __global__ void __launch_bounds__(256) convert_kernel(const S* __restrict__ src,
     }
 }
 
-template <typename S>
-static void convert_from(const void* src, void* dst, int32_t dst_dtype, long long n8, int blocks, hipStream_t st) {
-    if (dst_dtype == MNET_F32) hipLaunchKernelGGL((convert_kernel<S, float>), dim3(blocks), dim3(256), 0, st, (const S*)src, (float*)dst, n8);
-    else if (dst_dtype == MNET_F16) hipLaunchKernelGGL((convert_kernel<S, f16>), dim3(blocks), dim3(256), 0, st, (const S*)src, (f16*)dst, n8);
-    else if (dst_dtype == MNET_F16M) hipLaunchKernelGGL((convert_kernel<S, hm>), dim3(blocks), dim3(256), 0, st, (const S*)src, (hm*)dst, n8);
-    else hipLaunchKernelGGL((convert_kernel<S, hs>), dim3(blocks), dim3(256), 0, st, (const S*)src, (hs*)dst, n8);
-}
-
 extern "C" int mnet_convert(const void* src, int32_t src_dtype, void* dst, int32_t dst_dtype, int64_t count, void* stream) {
     MNET_CHECK_ARG(src && dst && count > 0 && count % 8 == 0, "convert: bad args (count %% 8 == 0)");
-    MNET_CHECK_ARG(src_dtype >= MNET_F32 && src_dtype <= MNET_F16M && dst_dtype >= MNET_F32 && dst_dtype <= MNET_F16M, "convert: bad dtype");
+    MNET_CHECK_ARG(is_storage(src_dtype) && is_storage(dst_dtype), "convert: bad dtype");
     MNET_CHECK_ALIGN(aligned16(src) && aligned16(dst), "convert: unaligned pointer");
     MNET_CHECK_ALIGN((!is_split4(src_dtype) || aligned128(src)) && (!is_split4(dst_dtype) || aligned128(dst)) &&
                      ((!is_split4(src_dtype) && !is_split4(dst_dtype)) || count % 32 == 0),
@@ -968,10 +908,13 @@ extern "C" int mnet_convert(const void* src, int32_t src_dtype, void* dst, int32
     const long long n8 = count / 8;
     const int blocks = (int)((n8 + 255) / 256 < 16384 ? (n8 + 255) / 256 : 16384);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (src_dtype == MNET_F32) convert_from<float>(src, dst, dst_dtype, n8, blocks, st);
-    else if (src_dtype == MNET_F16) convert_from<f16>(src, dst, dst_dtype, n8, blocks, st);
-    else if (src_dtype == MNET_F16M) convert_from<hm>(src, dst, dst_dtype, n8, blocks, st);
-    else convert_from<hs>(src, dst, dst_dtype, n8, blocks, st);
+    dispatch_storage(src_dtype, [&](auto stag) {
+        dispatch_storage(dst_dtype, [&](auto dtag) {
+            using S = typename decltype(stag)::type;
+            using D = typename decltype(dtag)::type;
+            hipLaunchKernelGGL((convert_kernel<S, D>), dim3(blocks), dim3(256), 0, st, (const S*)src, (D*)dst, n8);
+        });
+    });
     MNET_LAUNCH_CHECK("convert");
     return MNET_OK;
 }
@@ -1066,18 +1009,15 @@ static void affine_act_launch(const void* x, void* y, int n, int c, long long pe
 extern "C" int mnet_affine_act_nhwc(const void* x, void* y, int32_t dtype, int32_t n, int32_t hw, int32_t c,
                                     const float* scale, const float* shift, int32_t swish, void* stream) {
     MNET_CHECK_ARG(x && y && scale && n > 0 && hw > 0 && c > 0 && n <= 65535, "affine_act: bad args");
-    MNET_CHECK_ARG(dtype == MNET_F32 || dtype == MNET_F16 || is_split4(dtype), "affine_act: bad dtype");
-    const int N = dtype == MNET_F32 ? 4 : 8;
+    MNET_CHECK_ARG(is_storage(dtype), "affine_act: bad dtype");
+    const int N = chunk_n(dtype);
     MNET_CHECK_ALIGN(!is_split4(dtype) || (c % 32 == 0 && aligned128(x) && aligned128(y)), "affine_act: split-half needs c %% 32 == 0, 128-byte aligned");
     MNET_CHECK_ALIGN(c % N == 0 && 256 % (c / N) == 0 && aligned16(x) && aligned16(y) && aligned16(scale) && aligned16(shift),
                      "affine_act: c=%d unsupported or unaligned", c);
     const long long per = (long long)hw * (c / N);
     MNET_CHECK_ARG(per < (1ll << 31), "affine_act: image too large");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == MNET_F16) affine_act_launch<f16>(x, y, n, c, per, scale, shift, swish, st);
-    else if (dtype == MNET_F16X2) affine_act_launch<hs>(x, y, n, c, per, scale, shift, swish, st);
-    else if (dtype == MNET_F16M) affine_act_launch<hm>(x, y, n, c, per, scale, shift, swish, st);
-    else affine_act_launch<float>(x, y, n, c, per, scale, shift, swish, st);
+    dispatch_storage(dtype, [&](auto tag) { affine_act_launch<typename decltype(tag)::type>(x, y, n, c, per, scale, shift, swish, st); });
     MNET_LAUNCH_CHECK("affine_act");
     return MNET_OK;
 }
@@ -1103,16 +1043,14 @@ __global__ void __launch_bounds__(256) sr_postprocess_kernel(const T* __restrict
 extern "C" int mnet_sr_postprocess(const void* src, int32_t src_dtype, void* dst, int32_t dst_u8, int64_t npix, int32_t c_ld,
                                    void* stream) {
     MNET_CHECK_ARG(src && dst && npix > 0 && c_ld >= 3, "sr_postprocess: bad args");
-    MNET_CHECK_ARG(src_dtype == MNET_F32 || src_dtype == MNET_F16, "sr_postprocess: bad dtype");
+    MNET_CHECK_ARG(is_f16_f32(src_dtype), "sr_postprocess: bad dtype");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int grid = (int)((npix + 255) / 256 < 65536 ? (npix + 255) / 256 : 65536);
-    if (src_dtype == MNET_F16) {
-        if (dst_u8) hipLaunchKernelGGL((sr_postprocess_kernel<f16, unsigned char>), dim3(grid), dim3(256), 0, st, (const f16*)src, (unsigned char*)dst, (long long)npix, c_ld);
-        else hipLaunchKernelGGL((sr_postprocess_kernel<f16, float>), dim3(grid), dim3(256), 0, st, (const f16*)src, (float*)dst, (long long)npix, c_ld);
-    } else {
-        if (dst_u8) hipLaunchKernelGGL((sr_postprocess_kernel<float, unsigned char>), dim3(grid), dim3(256), 0, st, (const float*)src, (unsigned char*)dst, (long long)npix, c_ld);
-        else hipLaunchKernelGGL((sr_postprocess_kernel<float, float>), dim3(grid), dim3(256), 0, st, (const float*)src, (float*)dst, (long long)npix, c_ld);
-    }
+    dispatch_f16_f32(src_dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        if (dst_u8) hipLaunchKernelGGL((sr_postprocess_kernel<T, unsigned char>), dim3(grid), dim3(256), 0, st, (const T*)src, (unsigned char*)dst, (long long)npix, c_ld);
+        else hipLaunchKernelGGL((sr_postprocess_kernel<T, float>), dim3(grid), dim3(256), 0, st, (const T*)src, (float*)dst, (long long)npix, c_ld);
+    });
     MNET_LAUNCH_CHECK("sr_postprocess");
     return MNET_OK;
 }
@@ -1140,14 +1078,16 @@ __global__ void __launch_bounds__(256) nonfinite_flag_kernel(const T* __restrict
 
 extern "C" int mnet_nonfinite_flag(const void* x, int32_t dtype, int64_t n, int32_t* flag, void* stream) {
     MNET_CHECK_ARG(x && flag && n > 0, "nonfinite_flag: bad args");
-    MNET_CHECK_ARG(dtype == MNET_F32 || dtype == MNET_F16, "nonfinite_flag: MNET_F32 or MNET_F16 expected");
+    MNET_CHECK_ARG(is_f16_f32(dtype), "nonfinite_flag: MNET_F32 or MNET_F16 expected");
     MNET_CHECK_ALIGN(aligned16(x), "nonfinite_flag: x must be 16-byte aligned");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (hipMemsetAsync(flag, 0, sizeof(int32_t), st) != hipSuccess) return mnet_fail(MNET_E_LAUNCH, "nonfinite_flag: hipMemsetAsync failed");
-    const long long nv = n / (dtype == MNET_F32 ? 4 : 8);
+    const long long nv = n / chunk_n(dtype);
     const int grid = (int)((nv + 255) / 256 < 4096 ? (nv + 255) / 256 > 0 ? (nv + 255) / 256 : 1 : 4096);
-    if (dtype == MNET_F16) hipLaunchKernelGGL(nonfinite_flag_kernel<f16>, dim3(grid), dim3(256), 0, st, (const f16*)x, (long long)n, flag);
-    else hipLaunchKernelGGL(nonfinite_flag_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)x, (long long)n, flag);
+    dispatch_f16_f32(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(nonfinite_flag_kernel<T>, dim3(grid), dim3(256), 0, st, (const T*)x, (long long)n, flag);
+    });
     MNET_LAUNCH_CHECK("nonfinite_flag");
     return MNET_OK;
 }
@@ -1261,7 +1201,7 @@ __global__ void __launch_bounds__(256) torgb_kernel(const T* __restrict__ x, con
 extern "C" int mnet_torgb(const void* x, int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c, const float* wgt, const float* style,
                           const float* scale_b, const float* bias, const float* skip, float* out, void* stream) {
     MNET_CHECK_ARG(x && wgt && style && bias && out && n > 0 && h > 0 && w > 0 && n <= 65535, "torgb: bad args");
-    MNET_CHECK_ARG(dtype == MNET_F32 || dtype == MNET_F16 || is_split4(dtype), "torgb: bad dtype");
+    MNET_CHECK_ARG(is_storage(dtype), "torgb: bad dtype");
     MNET_CHECK_ARG(c >= 64 && c <= 512 && (c & (c - 1)) == 0, "torgb: c=%d (supported: 64, 128, 256, 512)", c);
     MNET_CHECK_ARG(!skip || (h % 2 == 0 && w % 2 == 0), "torgb: a skip image needs even h, w");
     MNET_CHECK_ALIGN(aligned16(x) && aligned16(skip) && aligned16(out) && (!is_split4(dtype) || aligned128(x)), "torgb: unaligned pointer");
@@ -1272,10 +1212,10 @@ extern "C" int mnet_torgb(const void* x, int32_t dtype, int32_t n, int32_t h, in
     const long long wgs = (groups + trips - 1) / trips;
     const int gx = (int)(wgs < 1024 ? wgs : 1024);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == MNET_F16) hipLaunchKernelGGL(torgb_kernel<f16>, dim3(gx, n), dim3(256), 0, st, (const f16*)x, wgt, style, scale_b, bias, skip, out, h, w, c);
-    else if (dtype == MNET_F16X2) hipLaunchKernelGGL(torgb_kernel<hs>, dim3(gx, n), dim3(256), 0, st, (const hs*)x, wgt, style, scale_b, bias, skip, out, h, w, c);
-    else if (dtype == MNET_F16M) hipLaunchKernelGGL(torgb_kernel<hm>, dim3(gx, n), dim3(256), 0, st, (const hm*)x, wgt, style, scale_b, bias, skip, out, h, w, c);
-    else hipLaunchKernelGGL(torgb_kernel<float>, dim3(gx, n), dim3(256), 0, st, (const float*)x, wgt, style, scale_b, bias, skip, out, h, w, c);
+    dispatch_storage(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(torgb_kernel<T>, dim3(gx, n), dim3(256), 0, st, (const T*)x, wgt, style, scale_b, bias, skip, out, h, w, c);
+    });
     MNET_LAUNCH_CHECK("torgb");
     return MNET_OK;
 }
@@ -1434,30 +1374,31 @@ __global__ void __launch_bounds__(256) conv3x3_rgb_kernel(const T* __restrict__ 
 extern "C" int mnet_conv3x3_rgb(const void* x, int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t cin, const void* wgt,
                                 const float* bias, int32_t act, void* y_nhwc, float* y_nchw, void* stream) {
     MNET_CHECK_ARG(x && wgt && bias && (y_nhwc || y_nchw) && n > 0 && h > 0 && w > 0 && n <= 65535, "conv3x3_rgb: bad args");
-    MNET_CHECK_ARG(dtype == MNET_F32 || dtype == MNET_F16 || is_split4(dtype), "conv3x3_rgb: bad dtype");
+    MNET_CHECK_ARG(is_storage(dtype), "conv3x3_rgb: bad dtype");
     MNET_CHECK_ARG(cin == 64, "conv3x3_rgb: cin=%d (supported: 64)", cin);
     MNET_CHECK_ALIGN(!is_split4(dtype) || aligned128(x), "conv3x3_rgb: split-half input must be 128-byte aligned");
     MNET_CHECK_ARG(act == MNET_ACT_NONE || act == MNET_ACT_TANH, "conv3x3_rgb: act %d", act);
     MNET_CHECK_ALIGN(aligned16(x) && aligned16(y_nhwc) && aligned16(wgt), "conv3x3_rgb: unaligned pointer");
     const int tiles = ((h + 7) / 8) * ((w + 31) / 32);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == MNET_F16) {
-        const int lds = 10 * 34 * 64 * 2;
-        hipLaunchKernelGGL((conv3x3_rgb_kernel<f16, 64>), dim3(tiles, n), dim3(256), lds, st, (const f16*)x, wgt, bias, (f16*)y_nhwc, y_nchw, h, w, act);
-    } else {
-        const int lds = 10 * 34 * 64 * 4;
-        static thread_local DeviceOnce attr_once;
-        if (!attr_once.done()) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_rgb_kernel<float, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_rgb_kernel<float, 64, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_rgb_kernel<float, 64, true, hm>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e != hipSuccess) return mnet_fail(MNET_E_LAUNCH, "hipFuncSetAttribute(conv3x3_rgb): %s", hipGetErrorString(e));
-            attr_once.mark();
+    return dispatch_storage(dtype, [&](auto tag) -> int {
+        using T = typename decltype(tag)::type;
+        if constexpr (__is_same(T, f16)) {
+            const int lds = 10 * 34 * 64 * 2;
+            hipLaunchKernelGGL((conv3x3_rgb_kernel<f16, 64>), dim3(tiles, n), dim3(256), lds, st, (const f16*)x, wgt, bias, (f16*)y_nhwc, y_nchw, h, w, act);
+        } else {                        // fp32 arithmetic and outputs; a blocked storage is converted while it is staged, half a patch at a time
+            constexpr bool SPLIT = is_split4_type<T>;
+            const auto kern = conv3x3_rgb_kernel<float, 64, SPLIT, std::conditional_t<SPLIT, T, hs>>;
+            const int lds = 10 * 34 * 64 * 4;
+            static thread_local DeviceOnce attr_once;      // per instantiation, per thread, per device
+            if (!attr_once.done()) {
+                const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+                if (e != hipSuccess) return mnet_fail(MNET_E_LAUNCH, "hipFuncSetAttribute(conv3x3_rgb): %s", hipGetErrorString(e));
+                attr_once.mark();
+            }
+            hipLaunchKernelGGL(kern, dim3(tiles, n), dim3(256), SPLIT ? 10 * 34 * 32 * 4 : lds, st, (const float*)x, wgt, bias, (float*)y_nhwc, y_nchw, h, w, act);
         }
-        if (dtype == MNET_F16X2) hipLaunchKernelGGL((conv3x3_rgb_kernel<float, 64, true>), dim3(tiles, n), dim3(256), 10 * 34 * 32 * 4, st, (const float*)x, wgt, bias, (float*)y_nhwc, y_nchw, h, w, act);
-        else if (dtype == MNET_F16M) hipLaunchKernelGGL((conv3x3_rgb_kernel<float, 64, true, hm>), dim3(tiles, n), dim3(256), 10 * 34 * 32 * 4, st, (const float*)x, wgt, bias, (float*)y_nhwc, y_nchw, h, w, act);
-        else hipLaunchKernelGGL((conv3x3_rgb_kernel<float, 64>), dim3(tiles, n), dim3(256), lds, st, (const float*)x, wgt, bias, (float*)y_nhwc, y_nchw, h, w, act);
-    }
-    MNET_LAUNCH_CHECK("conv3x3_rgb");
-    return MNET_OK;
+        MNET_LAUNCH_CHECK("conv3x3_rgb");
+        return MNET_OK;
+    });
 }

@@ -368,6 +368,26 @@ __device__ __forceinline__ void st_block32_hm(hm* px, int c, float v) {
 
 static inline bool aligned128(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 127u) == 0; }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// host: a runtime mnet_dtype as a C++ type.  `dispatch_storage(dtype, [&](auto tag) { using T = typename decltype(tag)::type; ... })` runs the
+// lambda with the element type of the storage (the caller has checked is_storage(dtype)) and hands back what it returns.
+static inline bool is_split4(int dt) { return dt == MNET_F16X2 || dt == MNET_F16M; }      // the two 4-byte blocked storages
+static inline bool is_storage(int dt) { return dt == MNET_F32 || dt == MNET_F16 || is_split4(dt); }
+static inline bool is_f16_f32(int dt) { return dt == MNET_F32 || dt == MNET_F16; }           // the plain element types
+static inline int chunk_n(int dt) { return dt == MNET_F32 ? 4 : 8; }                      // channels per 16-byte chunk: Vec<T>::N of the storage's type
+template <typename T> struct TypeTag { typedef T type; };
+template <typename T> constexpr bool is_split4_type = __is_same(T, hs) || __is_same(T, hm);
+template <typename F> static inline auto dispatch_storage(int dt, F&& f) {
+    if (dt == MNET_F16) return f(TypeTag<f16>{});
+    if (dt == MNET_F16X2) return f(TypeTag<hs>{});
+    if (dt == MNET_F16M) return f(TypeTag<hm>{});
+    return f(TypeTag<float>{});
+}
+template <typename F> static inline auto dispatch_f16_f32(int dt, F&& f) {                // the kernels that read plain elements only
+    if (dt == MNET_F16) return f(TypeTag<f16>{});
+    return f(TypeTag<float>{});
+}
+
 __device__ __forceinline__ float act_apply(float v, int act) {
     switch (act) {
         case MNET_ACT_RELU: return v < 0.f ? v * 0.f : v;         // (not fmaxf: a NaN must stay a NaN, like torch.relu; -inf becomes NaN, see act_apply_vec)

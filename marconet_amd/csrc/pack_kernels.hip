@@ -104,10 +104,10 @@ extern "C" int mnet_pack_weights(const float* w_oihw, int32_t cout, int32_t cin,
                                  double* workspace, void* stream) {
     MNET_CHECK_ARG(w_oihw && packed && cout > 0 && cin > 0 && kh > 0 && kw > 0, "pack_weights: bad args");
     MNET_CHECK_ARG(cout_pad >= cout && cin_pad >= cin, "pack_weights: padded sizes smaller than the tensor");
-    MNET_CHECK_ARG(dtype == MNET_F32 || dtype == MNET_F16 || dtype == MNET_F16X2 || dtype == MNET_F16M, "pack_weights: bad dtype");
+    MNET_CHECK_ARG(is_storage(dtype), "pack_weights: bad dtype");
     MNET_CHECK_ARG((sn_u == nullptr) == (sn_v == nullptr), "pack_weights: sn_u and sn_v go together");
     MNET_CHECK_ARG(!sn_u || workspace, "pack_weights: the spectral-norm fold needs a workspace of cout + 1 doubles");
-    MNET_CHECK_ALIGN((dtype != MNET_F16X2 && dtype != MNET_F16M) || (cin_pad % 32 == 0 && aligned128(packed)), "pack_weights: split-half needs cin_pad %% 32 == 0, 128-byte aligned");
+    MNET_CHECK_ALIGN(!is_split4(dtype) || (cin_pad % 32 == 0 && aligned128(packed)), "pack_weights: split-half needs cin_pad %% 32 == 0, 128-byte aligned");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     float* sigma = nullptr;
     if (sn_u) {
@@ -117,25 +117,21 @@ extern "C" int mnet_pack_weights(const float* w_oihw, int32_t cout, int32_t cin,
         hipLaunchKernelGGL(sn_fold_kernel, dim3(1), dim3(64), 0, st, workspace, cout, sigma);
         MNET_LAUNCH_CHECK("sn_fold");
     }
-    if (dtype == MNET_F16M) {           // `packed` holds cout_pad * kh * kw * cin_pad * 4 + cout_pad bytes
-        hipLaunchKernelGGL(pack_weights_mx_kernel, dim3(cout_pad), dim3(256), 0, st, w_oihw, (unsigned char*)packed, cout, cin, kh, kw, cout_pad,
-                           cin_pad, scale * MNET_SPLIT_WSCALE, sigma);
-        MNET_LAUNCH_CHECK("pack_weights_mx");
+    return dispatch_storage(dtype, [&](auto tag) -> int {
+        using T = typename decltype(tag)::type;
+        // the blocked storages hold MNET_SPLIT_WSCALE * W (exponent offset, undone by the conv epilogue)
+        const float ws = is_split4_type<T> ? scale * MNET_SPLIT_WSCALE : scale;
+        if constexpr (__is_same(T, hm)) {           // `packed` holds cout_pad * kh * kw * cin_pad * 4 + cout_pad bytes
+            hipLaunchKernelGGL(pack_weights_mx_kernel, dim3(cout_pad), dim3(256), 0, st, w_oihw, (unsigned char*)packed, cout, cin, kh, kw, cout_pad, cin_pad, ws, sigma);
+            MNET_LAUNCH_CHECK("pack_weights_mx");
+        } else {
+            const long long total = (long long)cout_pad * kh * kw * cin_pad;
+            const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+            hipLaunchKernelGGL(pack_weights_kernel<T>, dim3(blocks), dim3(256), 0, st, w_oihw, (T*)packed, cout, cin, kh, kw, cout_pad, cin_pad, ws, sigma, total);
+            MNET_LAUNCH_CHECK("pack_weights");
+        }
         return MNET_OK;
-    }
-    const long long total = (long long)cout_pad * kh * kw * cin_pad;
-    const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-    if (dtype == MNET_F16X2) {
-        // hi / lo of MNET_SPLIT_WSCALE * W (exponent offset, undone by the conv epilogue)
-        hipLaunchKernelGGL(pack_weights_kernel<hs>, dim3(blocks), dim3(256), 0, st, w_oihw, (hs*)packed, cout, cin, kh, kw, cout_pad, cin_pad,
-                           scale * MNET_SPLIT_WSCALE, sigma, total);
-    } else if (dtype == MNET_F16) {
-        hipLaunchKernelGGL(pack_weights_kernel<f16>, dim3(blocks), dim3(256), 0, st, w_oihw, (f16*)packed, cout, cin, kh, kw, cout_pad, cin_pad, scale, sigma, total);
-    } else {
-        hipLaunchKernelGGL(pack_weights_kernel<float>, dim3(blocks), dim3(256), 0, st, w_oihw, (float*)packed, cout, cin, kh, kw, cout_pad, cin_pad, scale, sigma, total);
-    }
-    MNET_LAUNCH_CHECK("pack_weights");
-    return MNET_OK;
+    });
 }
 
 // ---------------------------------------------------------------------------- demodulation table

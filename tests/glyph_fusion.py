@@ -30,7 +30,7 @@ BLOCKED_TOL = {SPLIT: 2e-6, MX: 2e-5}                     # tests/test_kernels_g
 
 
 def vec_n(storage):
-    """channels per 16-byte chunk — aux_kernels.hip adain_launch: `const int N = dtype == MNET_F32 ? 4 : 8;`"""
+    """channels per 16-byte chunk — aux_kernels.hip adain_launch: `const int N = chunk_n(dtype);`, common.h: `return dt == MNET_F32 ? 4 : 8;`"""
     return 4 if storage == F32 else 8
 
 

@@ -18,7 +18,7 @@ def _cdiv(a, b):
 
 
 def vec_n(dtype):
-    """channels per 16-byte chunk — aux_kernels.hip, every wrapper: `const int N = dtype == MNET_F32 ? 4 : 8;`"""
+    """channels per 16-byte chunk — aux_kernels.hip, every wrapper: `const int N = chunk_n(dtype);`, common.h: `return dt == MNET_F32 ? 4 : 8;`"""
     return 4 if dtype == F32 else 8
 
 
@@ -95,7 +95,7 @@ FLAG_CAP, CONVERT_CAP, SR_CAP, FBA_CAP = 4096, 16384, 65536, 16384
 
 
 def flag_launch(numel, dtype):
-    """-> (nv, grid, trips, tail) of mnet_nonfinite_flag: 16-byte vectors (aux_kernels.hip:1119 `n / (dtype == MNET_F32 ? 4 : 8)`), workgroups
+    """-> (nv, grid, trips, tail) of mnet_nonfinite_flag: 16-byte vectors (aux_kernels.hip:1119 `n / chunk_n(dtype)`), workgroups
     (:1120: ceil(nv / 256) clamped to [1, 4096]), trips of the grid-stride loop (:1100), elements of the scalar tail (:1109 `i = nv * N; i < n`)"""
     n = vec_n(dtype)
     nv = numel // n

@@ -120,7 +120,8 @@ def test_mirrored_constants_are_the_sources():
     assert re.search(r"#define MNET_SCATTER_RUN %d\b" % GF.SCATTER_RUN, hip)
     assert "ADAIN_SPLIT_BELOW = %d " % GF.DISPATCH_CASE[3] in ops and "G < ADAIN_SPLIT_BELOW" in ops
     launch = hip[hip.index("static int adain_launch"):hip.index('extern "C" int mnet_adain_crop_concat(')]
-    assert "const int N = dtype == MNET_F32 ? 4 : 8;" in launch
+    assert "const int N = chunk_n(dtype);" in launch                                           # ... which is the one definition in common.h:
+    assert "static inline int chunk_n(int dt) { return dt == MNET_F32 ? 4 : 8; }" in _src("marconet_amd", "csrc", "common.h")
     assert ("(size_t)256 * N * 4 * sizeof(double) + (size_t)4 * C * sizeof(float) + (size_t)4 * C * sizeof(double) +" in launch
             and "(size_t)(2 * C / 32) * 2 * sizeof(float);" in launch)                       # adain_lds_bytes
     assert "lds <= 160 * 1024" in launch
