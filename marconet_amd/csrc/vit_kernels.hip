@@ -181,16 +181,24 @@ extern "C" int mnet_attention(const float* qkv, float* out, int32_t B, int32_t N
 }
 
 // ---------------------------------------------------------------------------- argmax (first max index)
+// torch.argmax's order: NaN counts as the maximum, of equal candidates (two NaNs included) the lower index wins.  A lane without an
+// element keeps (-inf, 0x7fffffff), which loses against every real candidate by its index — a row of -inf gives 0, never the sentinel.
+__device__ __forceinline__ bool argmax_takes(float v, int i, float best, int bi) {
+    const bool vn = v != v, bn = best != best;
+    if (vn || bn) return vn && (!bn || i < bi);
+    return v > best || (v == best && i < bi);
+}
+
 __global__ void __launch_bounds__(256) argmax_kernel(const float* __restrict__ x, int64_t* __restrict__ idx, int rows, int D) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= rows) return;
     const float* xr = x + (size_t)row * D;
     float best = -INFINITY; int bi = 0x7fffffff;
-    for (int i = lane; i < D; i += 64) { const float v = xr[i]; if (v > best) { best = v; bi = i; } }
+    for (int i = lane; i < D; i += 64) { const float v = xr[i]; if (argmax_takes(v, i, best, bi)) { best = v; bi = i; } }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
-        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+        if (argmax_takes(ov, oi, best, bi)) { best = ov; bi = oi; }
     }
     if (lane == 0) idx[row] = bi;
 }

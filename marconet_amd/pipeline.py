@@ -285,7 +285,8 @@ ALPHABET_SIZE = 6735          # utils/alphabets.py: 6735 characters; class 6735 
 
 
 def clear_labels_batch(logits):
-    """test_w.py:34-40 for a whole batch: argmax over the 6736 classes (HIP kernel, first maximal index like torch.max),
+    """test_w.py:34-40 for a whole batch: argmax over the 6736 classes (HIP kernel, first maximal index like torch.max, a NaN
+    counting as the maximum as it does there),
     ONE device→host copy of the [B,64] indices, then the CTC-style collapse on the host (drop repeats, drop blanks).
     → list of B int64 tensors [n_b, 1] (CPU)."""
     B, T, C = logits.shape
