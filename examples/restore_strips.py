@@ -2,7 +2,7 @@
 """The reference's test_sr.py as ONE batch per call on the HIP path: a directory of low-quality text strips in, one panel PNG per strip out
 (preview | box marks | super-resolved strip | structure priors — the file test_sr.py:232 writes, under the same name).
 
-    python examples/restore_strips.py -i <strips dir> -o <out dir> [-m] [--precision fp16x2] [--batch 64]
+    python examples/restore_strips.py -i <strips dir> -o <out dir> [-m] [--precision fp16x2] [--batch 64] [--device-prep]
 
 Same flags as the script (-i / -o / -m, test_sr.py:236-241).  What differs, and why:
   * the YOLO character detector and the modelscope OCR (test_sr.py:55-56,86-96) are not part of this build (SURVEY.md §8f NEXT-4).  With
@@ -10,7 +10,9 @@ Same flags as the script (-i / -o / -m, test_sr.py:236-241).  What differs, and 
     come from the encoder itself (its class logits and its (left, right) predictions: MarconetPipeline.forward_blind's sources);
   * weights: the three checkpoints are looked for in ``$MARCONET_CKPT_DIR`` (the names of checkpoints/download_github.py); without them
     the seeded synthetic weights run — the panel then shows the plumbing, not a restoration;
-  * all strips of a batch go through the three networks in one call (the script: one strip at a time, :77).
+  * all strips of a batch go through the three networks in one call (the script: one strip at a time, :77);
+  * ``--device-prep`` (opt-in): the resize / canvas / normalise in front of the encoder and the 128-px preview (test_sr.py:98-115) run on the GPU
+    for the whole batch (MarconetPipeline.restore_images) instead of per strip in host numpy — the same panels, byte for byte.
 Needs the GPU (there is no CPU path in this package)."""
 import argparse
 import os
@@ -67,6 +69,19 @@ def blind_strips(pipe, paths, dev, max_glyphs=16):
     return out
 
 
+def device_strips(pipe, paths, manual, max_glyphs=16):
+    """--device-prep: the strips as loaded go to the device as they are; → (strips, results) in the form the loop below consumes"""
+    images = [lq_io.load_png(p) for p in paths]
+    texts = [lq_io.manual_text(p) for p in paths] if manual else None
+    res, strips = pipe.restore_images(images, texts=texts, with_prior=True, max_glyphs=max_glyphs, details=True)
+    for p, img, s in zip(paths, images, strips):
+        if s is None:
+            print("Warning!!! %s: wider than %d px at height 32: crop it into shorter segments" % (os.path.basename(p), lq_io.LQ_W))
+        else:
+            s["image"] = img
+    return strips, res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("-i", "--test_path", type=str, default="./Testsets/LQs")
@@ -74,6 +89,7 @@ def main():
     ap.add_argument("-m", "--manual", action="store_true")
     ap.add_argument("--precision", default="fp16x2", choices=["fp16x2", "fp16x3", "fp16", "fp32"])
     ap.add_argument("--batch", type=int, default=64, help="strips per call")
+    ap.add_argument("--device-prep", action="store_true", help="resize / normalise the strips on the GPU (MarconetPipeline.restore_images)")
     a = ap.parse_args()
     save_path = a.save_path or a.test_path.rstrip("/") + "_" + time.strftime("%m-%d_%H-%M", time.localtime()) + "_MARCONet"
     os.makedirs(save_path, exist_ok=True)
@@ -87,12 +103,15 @@ def main():
     for s0 in range(0, len(names), a.batch):
         chunk = names[s0:s0 + a.batch]
         paths = [os.path.join(a.test_path, f) for f in chunk]
-        strips = manual_strips(paths) if a.manual else blind_strips(pipe, paths, dev)
+        if a.device_prep:
+            strips, done = device_strips(pipe, paths, a.manual)
+        else:
+            strips = manual_strips(paths) if a.manual else blind_strips(pipe, paths, dev)
         live = [i for i, s in enumerate(strips) if s is not None and s["labels"].numel() > 0]
         for i, s in enumerate(strips):
             if s is not None and s["labels"].numel() == 0:
                 print("Warning!!! No character is detected in %s. Continue..." % chunk[i])          # test_sr.py:168-170
-        res = pipe.restore_strips([strips[i] for i in live], with_prior=True)
+        res = [done[i] for i in live] if a.device_prep else pipe.restore_strips([strips[i] for i in live], with_prior=True)
         for i, r in zip(live, res):
             s = strips[i]
             if r is None:                                                        # a character outside the alphabet (test_sr.py:181-190)
@@ -102,7 +121,7 @@ def main():
             n = int(s["labels"].shape[0])
             base = os.path.splitext(chunk[i])[0]
             out = os.path.join(save_path, "%s_%s.png" % (base, s["text"]))       # test_sr.py:232
-            lq_io.save_panel(out, lq_io.panel(s["image"], s["locs"][0], n, show_sr, prior128))
+            lq_io.save_panel(out, lq_io.panel(s["image"], s["locs"][0], n, show_sr, prior128, show=s.get("show")))
             print("Restoring %s. Using %s text: %s -> %s" % (chunk[i], "given" if a.manual else "predicted", s["text"], out))
 
 

@@ -350,6 +350,28 @@ int mnet_conv3x3_rgb(const void* x, int32_t dtype, int32_t n, int32_t h, int32_t
  * for the device→host copy and the multi-GPU all-gather (SURVEY.md §8f NEXT-1) */
 int mnet_sr_postprocess(const void* src, int32_t src_dtype, void* dst, int32_t dst_u8, int64_t npix, int32_t c_ld, void* stream);
 
+/* a17 on the device, the script's input pre-processing (test_sr.py:98-115; the input-side counterpart of mnet_sr_postprocess): a ragged batch of
+ * tightly packed uint8 RGB images [h][w][3] in ONE buffer → one launch that resizes every image to height dst_h with cv2's 8-bit INTER_CUBIC
+ * arithmetic (marconet_amd/lq_io.py::resize_cubic, bit for bit: fp64 sample positions, fp32 A = -0.75 weights rounded operation by operation,
+ * 11-bit integer taps, BORDER_REPLICATE, both passes in integers, clip((v + 2^21) >> 22, 0, 255)) and pastes it at the left of a canvas_w wide canvas:
+ *   MNET_LQ_FORM_F32_NCHW  dst fp32 [n][3][dst_h][canvas_w] = (u8 / 255 - 0.5) / 0.5 (ToTensor + Normalize, correctly rounded fp32: torch's values);
+ *                          columns >= dw are -1.0 (normalised black) — the encoder's LQ with dst_h = 32, canvas_w = 512
+ *   MNET_LQ_FORM_U8_HWC    dst uint8 [n][dst_h][canvas_w][3]; columns >= dw are 0 — the panel's preview (ShowLQ, test_sr.py:99) with dst_h = 128
+ * The WHOLE destination is written (no clearing by the caller).  `images`: a DEVICE table of n descriptors.  The caller computes per image only
+ * scalars: dw = the resized width (<= canvas_w; larger values are clamped) and scale = 1.0 / ((double)dst_h / h), which serves both axes as in the
+ * script (fx = fy).  Source indices are clamped into [0, h) x [0, w) of the image at `offset`: a table whose images lie inside src cannot take the
+ * kernel out of range.  MNET_E_ARG (nothing enqueued, checked before any HIP call) for a null pointer, n <= 0, dst_h < 1, canvas_w < 1, an unknown form. */
+typedef struct {
+    int64_t offset;             /* byte offset of the image's first pixel in src (any alignment)   */
+    int32_t h, w;               /* source size                                                      */
+    int32_t dw;                 /* resized width: columns [0, dw) carry the image, the rest the fill */
+    int32_t reserved;           /* 0                                                                */
+    double scale;               /* 1.0 / (dst_h / h): source step per destination pixel, both axes  */
+} mnet_lq_image;
+enum { MNET_LQ_FORM_F32_NCHW = 0, MNET_LQ_FORM_U8_HWC = 1 };
+int mnet_lq_from_u8(const uint8_t* src, const mnet_lq_image* images, int32_t n, int32_t dst_h, int32_t canvas_w, void* dst, int32_t form,
+                    void* stream);
+
 /* Finiteness guard of the half-range precision modes (the role `torch.isfinite(y).all()` would play after test_sr.py:197 — the
  * reference has no such check because its fp32 activations cannot overflow): *flag (int32, device) is set to 0 and then to 1 by any
  * thread that finds an element of x (n elements, MNET_F32 or MNET_F16) that is inf or NaN.  One streaming read of x, no atomics

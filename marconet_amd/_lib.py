@@ -40,6 +40,13 @@ class ConvDesc(ctypes.Structure):
     ]
 
 
+class LqImage(ctypes.Structure):
+    """mirror of ``mnet_lq_image`` (include/marconet_hip.h): one image of mnet_lq_from_u8's device table"""
+    _fields_ = [("offset", c_i64), ("h", c_int), ("w", c_int), ("dw", c_int), ("reserved", c_int), ("scale", c_double)]
+
+
+LQ_FORM_F32_NCHW, LQ_FORM_U8_HWC = 0, 1
+
 # name -> (restype, argtypes); every symbol include/marconet_hip.h declares
 SYMBOLS = {
     "mnet_last_error": (ctypes.c_char_p, []),
@@ -82,6 +89,7 @@ SYMBOLS = {
     "mnet_conv3x3_rgb": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "mnet_sr_postprocess": (c_int, [c_void_p, c_int, c_void_p, c_int, c_i64, c_int, c_void_p]),
     "mnet_nonfinite_flag": (c_int, [c_void_p, c_int, c_i64, c_void_p, c_void_p]),
+    "mnet_lq_from_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "mnet_pack_weights": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p,
                                   c_void_p, c_void_p]),
     "mnet_pack_wsq": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),

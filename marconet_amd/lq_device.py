@@ -1,0 +1,102 @@
+"""The input side of the script's driver glue on the GPU: what ``lq_io.lq_from_image`` / ``lq_io.show_lq`` do to a strip
+before ``modelEncoder(LQ)`` (test_sr.py:98-115) — for a whole batch of raw uint8 RGB arrays with one kernel launch per output
+(``mnet_lq_from_u8``), one host→device copy of the packed pixels and one of the descriptor table.  The host computes per image only scalars
+(sizes, the resized widths, the sampling step); there is no per-pixel host work.
+
+``lq_io`` stays the pure-host definition: the device path returns its bits (tests/test_lq_device_gpu.py) and raises its errors.
+"""
+import collections
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+from .lq_io import LQ_H, LQ_W, StripTooWide
+
+SHOW_H = 4 * LQ_H             # test_sr.py:99: ShowLQ, the strip at height 128
+
+Geometry = collections.namedtuple("Geometry", "h w dw scale show_w show_scale")
+Prepared = collections.namedtuple("Prepared", "lq content_w show_w index preview skipped")
+
+
+def _axis(h, w, dst_h):
+    """``resize_cubic(img, dst_h / h, dst_h / h)``'s output size and the table's sampling step: (dw, dh, scale) exactly as the host computes
+    them (Python floats; numpy's round half to even)"""
+    fx = dst_h / h
+    return int(np.rint(w * fx)), int(np.rint(h * fx)), 1.0 / fx
+
+
+def strip_geometry(img, preview=True):
+    """the scalars of one strip, with the host path's errors in the host path's order (``lq_io.lq_from_image``): TypeError for an array that is
+    not uint8 HxWxC, ValueError for an empty output or another channel count than 3, StripTooWide beyond 512 px at height 32"""
+    shape = np.shape(img)
+    if len(shape) != 3:
+        raise ValueError("uint8 RGB HxWx3 array expected, got shape %s" % (tuple(shape),))
+    if np.asarray(img).dtype != np.uint8:
+        raise TypeError("resize_cubic: uint8 HxWxC image expected")
+    h, w, c = (int(v) for v in shape)
+    if c != 3:
+        raise ValueError("uint8 RGB HxWx3 array expected, got %d channels" % c)
+    if h < 1 or w < 1:
+        raise ValueError("resize_cubic: empty output")
+    dw, dh, scale = _axis(h, w, LQ_H)
+    if dw <= 0 or dh <= 0:
+        raise ValueError("resize_cubic: empty output")
+    show_w, show_h, show_scale = _axis(h, w, SHOW_H)
+    if dw > LQ_W:
+        raise StripTooWide("strip is %d px wide at height 32 (limit %d): crop it into shorter segments" % (dw, LQ_W))
+    # the kernel resizes to a FIXED height: the host's own output height rint(h * (dst_h / h)) must be that height (it is for every h <= 4096)
+    if dh != LQ_H or (preview and (show_h != SHOW_H or show_w <= 0)):
+        raise ValueError("strip of height %d does not resize to height %d / %d" % (h, LQ_H, SHOW_H))
+    return Geometry(h, w, dw, scale, show_w, show_scale)
+
+
+def build_table(geoms, offsets, preview):
+    """→ numpy record array of ``mnet_lq_image`` [1 or 2, n]: row 0 the height-32 descriptors, row 1 (``preview``) the height-128 ones"""
+    n = len(geoms)
+    tab = np.zeros((2 if preview else 1, n), dtype=np.dtype(_lib.LqImage))
+    for k, (g, off) in enumerate(zip(geoms, offsets)):
+        tab[0, k] = (off, g.h, g.w, g.dw, 0, g.scale)
+        if preview:
+            tab[1, k] = (off, g.h, g.w, g.show_w, 0, g.show_scale)
+    return tab
+
+
+def prepare_strips(images, device, preview=False, skip_too_wide=False):
+    """images: list of uint8 RGB HxWx3 arrays → ``Prepared``:
+
+        lq         fp32 [B,3,32,512] on ``device`` — ``lq_io.lq_from_image(img)[0]`` of the B accepted images, bit for bit
+        content_w  their widths at height 32, ``show_w`` their widths at height 128 (lists of B ints)
+        index      positions of the accepted images in ``images``
+        preview    ``preview=True``: uint8 [B,128,max(show_w),3] on ``device`` — ``lq_io.show_lq(img)`` at columns < show_w[k], 0 beyond
+        skipped    ``skip_too_wide=True`` only: [(position, StripTooWide)] — the strips the script skips with a warning (test_sr.py:108-110)
+
+    Every error of the host path is raised as ``lq_io.lq_from_image`` raises it — StripTooWide included, before anything is copied or
+    launched; ``skip_too_wide=True`` (``MarconetPipeline.restore_images``) leaves such strips out of the batch instead, as the script does."""
+    device = torch.device(device)
+    geoms, index, skipped, flat, offsets, off = [], [], [], [], [], 0
+    for i, img in enumerate(images):
+        try:
+            g = strip_geometry(img, preview)
+        except StripTooWide as e:
+            if not skip_too_wide:
+                raise
+            skipped.append((i, e))
+            continue
+        geoms.append(g)
+        index.append(i)
+        offsets.append(off)
+        flat.append(np.ascontiguousarray(img).reshape(-1))
+        off += g.h * g.w * 3
+    B = len(geoms)
+    content_w, show_w = [g.dw for g in geoms], [g.show_w for g in geoms]
+    if not B:
+        return Prepared(torch.empty((0, 3, LQ_H, LQ_W), dtype=torch.float32, device=device), [], [], [],
+                        torch.empty((0, SHOW_H, 0, 3), dtype=torch.uint8, device=device) if preview else None, skipped)
+    src = torch.from_numpy(np.concatenate(flat)).to(device)                            # the one copy of the pixels
+    tab = build_table(geoms, offsets, preview)
+    table = torch.from_numpy(tab.view(np.uint8).reshape(tab.shape[0], B, tab.dtype.itemsize)).to(device)      # the one copy of the table
+    with ops.on_device(src):
+        lq = ops.lq_from_u8(src, table[0], LQ_H, LQ_W)
+        show = ops.lq_from_u8(src, table[1], SHOW_H, max(show_w), preview=True) if preview else None
+    return Prepared(lq, content_w, show_w, index, show, skipped)

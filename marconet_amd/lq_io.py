@@ -161,12 +161,13 @@ def draw_locs(show, locs, n, img_max_width=16 * 128):
     return out
 
 
-def panel(image, locs, n, show_sr, prior128):
+def panel(image, locs, n, show_sr, prior128, show=None):
     """test_sr.py:207-232: the array the script hands to ``cv2.imwrite`` — float [4·128, show_w, 3] in cv2's BGR order: the preview, the
     preview with the box marks (both flipped RGB→BGR), ``ShowSR`` (already BGR, cropped to the preview's width), and the row of
     structure images resized to the preview's size ×255 (NOT flipped: the script stacks that RGB array as it is, :212,232).
-    ``image``: the strip as loaded (uint8 RGB); ``show_sr`` / ``prior128``: ``MarconetPipeline.restore_strips(with_prior=True)``."""
-    show = show_lq(image)
+    ``image``: the strip as loaded (uint8 RGB); ``show_sr`` / ``prior128``: ``MarconetPipeline.restore_strips(with_prior=True)``;
+    ``show``: ``show_lq(image)`` where the caller has it already (``image`` is then not read)."""
+    show = show_lq(image) if show is None else np.asarray(show)
     prior = resize_linear(prior128, show.shape[1], show.shape[0]) * 255
     return np.vstack((show[:, :, ::-1], draw_locs(show, locs, n)[:, :, ::-1], np.asarray(show_sr)[:, :show.shape[1], :], prior))
 

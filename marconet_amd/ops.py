@@ -17,7 +17,7 @@ from .packing import MX_DTYPE, SPLIT_DTYPE, is_split, mx_weight_rows, new_tensor
 
 __all__ = ["conv2d", "linear", "nchw_to_nhwc", "nhwc_to_nchw", "upsample2x", "affine_act", "groupnorm_affine",
            "adain_crop_concat", "adain_crop_concat_gn", "glyph_scatter_affine", "layernorm", "token_mix", "attention", "pixelnorm",
-           "embed_gather", "demod", "argmax_rows", "convert", "fused_bias_act", "sr_postprocess", "conv3x3_rgb", "torgb", "stats",
+           "embed_gather", "demod", "argmax_rows", "convert", "fused_bias_act", "sr_postprocess", "lq_from_u8", "conv3x3_rgb", "torgb", "stats",
            "pack_weights", "pack_wsq", "gather_rows", "style_rows", "nonfinite_flag", "gn_partial_buffer", "can_emit_gn_partial", "groupnorm_affine_from_partial",
            "ACT_NONE", "ACT_RELU", "ACT_LRELU", "ACT_LRELU_SQRT2", "ACT_TANH", "ACT_GELU", "ACT_SIGMOID"]
 
@@ -553,6 +553,29 @@ def sr_postprocess(y_nhwc, u8=True):
     out = torch.empty((b, h, w, 3), dtype=torch.uint8 if u8 else torch.float32, device=y_nhwc.device)
     _lib.check(lib.mnet_sr_postprocess(_p(y_nhwc), _dt(y_nhwc), _p(out), 1 if u8 else 0, b * h * w, c_ld, _stream()),
                "mnet_sr_postprocess")
+    return out
+
+
+def lq_from_u8(src, table, dst_h, canvas_w, preview=False, out=None):
+    """mnet_lq_from_u8 (test_sr.py:98-115 on the device; the bits of lq_io.lq_from_image / lq_io.show_lq): ``src`` uint8 [bytes], a ragged batch
+    of tightly packed HxWx3 images; ``table`` uint8 [n, sizeof(mnet_lq_image)], the images' descriptors (``_lib.LqImage``), both on the device.
+    → fp32 [n,3,dst_h,canvas_w] (normalised, −1 beyond an image's width) or, ``preview=True``, uint8 [n,dst_h,canvas_w,3] (0 beyond it).
+    The kernel writes the whole of ``out``."""
+    lib = _lib.load()
+    _need_cuda(src, table, out)
+    if src.dtype != torch.uint8 or table.dtype != torch.uint8 or table.dim() != 2 or table.shape[1] != ctypes.sizeof(_lib.LqImage):
+        raise TypeError("lq_from_u8: uint8 pixels and a uint8 [n, %d] descriptor table expected" % ctypes.sizeof(_lib.LqImage))
+    if table.data_ptr() % 8:
+        raise ValueError("lq_from_u8: the descriptor table must be 8-byte aligned")
+    n = int(table.shape[0])
+    shape = (n, dst_h, canvas_w, 3) if preview else (n, 3, dst_h, canvas_w)
+    dtype = torch.uint8 if preview else torch.float32
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=src.device)
+    elif tuple(out.shape) != shape or out.dtype != dtype:
+        raise TypeError("lq_from_u8: out must be %s %s" % (dtype, list(shape)))
+    _lib.check(lib.mnet_lq_from_u8(_p(src), _p(table), n, dst_h, canvas_w, _p(out), _lib.LQ_FORM_U8_HWC if preview else _lib.LQ_FORM_F32_NCHW,
+                                   _stream()), "mnet_lq_from_u8")
     return out
 
 

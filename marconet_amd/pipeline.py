@@ -269,6 +269,49 @@ class MarconetPipeline:
         return out
 
     @torch.no_grad()
+    def restore_images(self, images, texts=None, boxes=None, with_prior=False, max_glyphs=16, details=False):
+        """``restore_strips`` from RAW strips: ``images`` is a list of uint8 RGB HxWx3 arrays (``lq_io.load_png``, a detector's crops), and the
+        script's input pre-processing (test_sr.py:98-115) runs on the device for the whole batch (``lq_device.prepare_strips``: one kernel
+        launch, one copy of the pixels) instead of per strip in host numpy.  → what ``restore_strips`` returns for
+        ``lq_io.strip_from_png`` of the same strips, the same bytes; ``None`` for a strip the script skips (wider than 512 px at height 32,
+        :108-110; no character, :168-170; a character outside the alphabet, :181-190).
+        ``texts`` (one string per image): labels through the alphabet and one evenly spaced box per character, or ``boxes[i]`` where given —
+        as ``lq_io.strip_from_png``, except that an empty text gives ``None`` (the script's skip, :168-170) where ``strip_from_png`` raises.  ``texts=None``: labels (at most ``max_glyphs``) and locations come from the encoder itself, as in
+        ``forward_blind``.
+        ``details=True`` → ``(results, strips)``: per image also the dict ``restore_strips`` consumed (lq on the device, labels, locs, text,
+        content_w, show_w) plus ``show``, the uint8 RGB preview [128, show_w, 3] (``lq_io.show_lq``, resized on the device); None where skipped."""
+        from . import lq_device, lq_io
+        dev = next(self.sr.parameters()).device
+        prep = lq_device.prepare_strips(images, dev, preview=details, skip_too_wide=True)
+        strips = [None] * len(images)
+        if prep.index:
+            if texts is None:
+                logits, locs_lr, _ = self.encoder(prep.lq)
+                lab_all = clear_labels_batch(logits)
+                locs_all = locs_from_left_right(locs_lr).float().cpu()
+            show = prep.preview.cpu().numpy() if details else None
+            for k, i in enumerate(prep.index):
+                h = int(images[i].shape[0])
+                if texts is None:
+                    labels = lab_all[k][:max_glyphs]
+                    n = int(labels.shape[0])
+                    locs, text = locs_all[k:k + 1, :2 * n].contiguous(), lq_io.text_from_labels(labels.flatten().tolist())
+                else:
+                    text = texts[i]
+                    n = len(text)
+                    bx = boxes[i] if boxes is not None and boxes[i] is not None else lq_io.evenly_spaced_boxes(n, int(images[i].shape[1]), h)
+                    labels = torch.tensor(lq_io.labels_from_text(text), dtype=torch.float32).type(torch.LongTensor).reshape(-1, 1)   # test_sr.py:179
+                    locs = lq_io.locs_from_boxes(bx, h)
+                strips[i] = dict(lq=prep.lq[k:k + 1], labels=labels, locs=locs, text=text, content_w=prep.content_w[k], show_w=prep.show_w[k])
+                if details:
+                    strips[i]["show"] = show[k, :, :prep.show_w[k], :]
+        live = [i for i, s in enumerate(strips) if s is not None and s["labels"].numel() > 0]
+        out = [None] * len(images)
+        for i, r in zip(live, self.restore_strips([strips[i] for i in live], with_prior=with_prior)):
+            out[i] = r
+        return (out, strips) if details else out
+
+    @torch.no_grad()
     def forward_blind(self, lq, max_glyphs=16):
         """Self-contained end-to-end pass (SURVEY.md §8f NEXT-2): labels and glyph locations come from the encoder itself
         instead of the YOLO + OCR front-end — labels = ``clear_labels(logits)`` (test_w.py:34-40), locs = the encoder's
