@@ -2,7 +2,7 @@
 """The reference's test_sr.py as ONE batch per call on the HIP path: a directory of low-quality text strips in, one panel PNG per strip out
 (preview | box marks | super-resolved strip | structure priors — the file test_sr.py:232 writes, under the same name).
 
-    python examples/restore_strips.py -i <strips dir> -o <out dir> [-m] [--precision fp16x2] [--batch 64] [--device-prep]
+    python examples/restore_strips.py -i <strips dir> -o <out dir> [-m] [--precision fp16x2] [--batch 64] [--device-prep | --device-panel]
 
 Same flags as the script (-i / -o / -m, test_sr.py:236-241).  What differs, and why:
   * the YOLO character detector and the modelscope OCR (test_sr.py:55-56,86-96) are not part of this build (SURVEY.md §8f NEXT-4).  With
@@ -12,7 +12,9 @@ Same flags as the script (-i / -o / -m, test_sr.py:236-241).  What differs, and 
     the seeded synthetic weights run — the panel then shows the plumbing, not a restoration;
   * all strips of a batch go through the three networks in one call (the script: one strip at a time, :77);
   * ``--device-prep`` (opt-in): the resize / canvas / normalise in front of the encoder and the 128-px preview (test_sr.py:98-115) run on the GPU
-    for the whole batch (MarconetPipeline.restore_images) instead of per strip in host numpy — the same panels, byte for byte.
+    for the whole batch (MarconetPipeline.restore_images) instead of per strip in host numpy — the same panels, byte for byte;
+  * ``--device-panel`` (opt-in, implies ``--device-prep``): the panel itself (test_sr.py:203-232) is composed on the GPU too
+    (MarconetPipeline.restore_panels: one launch and one device→host copy per batch) — the same files; only PNG decode / encode stay on the host.
 Needs the GPU (there is no CPU path in this package)."""
 import argparse
 import os
@@ -82,6 +84,25 @@ def device_strips(pipe, paths, manual, max_glyphs=16):
     return strips, res
 
 
+def device_panels(pipe, paths, names, manual, save_path, max_glyphs=16):
+    """--device-panel: PNG in → PNG out; the host only decodes, encodes and prints the script's messages"""
+    from PIL import Image
+    images = [lq_io.load_png(p) for p in paths]
+    texts = [lq_io.manual_text(p) for p in paths] if manual else None
+    panels, strips = pipe.restore_panels(images, texts=texts, max_glyphs=max_glyphs, details=True)
+    for name, panel, s in zip(names, panels, strips):
+        if s is None:                                                            # test_sr.py:108-110
+            print("Warning!!! %s: wider than %d px at height 32: crop it into shorter segments" % (name, lq_io.LQ_W))
+        elif s["labels"].numel() == 0:                                           # test_sr.py:168-170
+            print("Warning!!! No character is detected in %s. Continue..." % name)
+        elif panel is None:                                                      # test_sr.py:181-190
+            print("Error in %s (a character outside the alphabet). Continue..." % name)
+        else:
+            out = os.path.join(save_path, "%s_%s.png" % (os.path.splitext(name)[0], s["text"]))       # test_sr.py:232
+            Image.fromarray(panel).save(out)
+            print("Restoring %s. Using %s text: %s -> %s" % (name, "given" if manual else "predicted", s["text"], out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("-i", "--test_path", type=str, default="./Testsets/LQs")
@@ -90,6 +111,7 @@ def main():
     ap.add_argument("--precision", default="fp16x2", choices=["fp16x2", "fp16x3", "fp16", "fp32"])
     ap.add_argument("--batch", type=int, default=64, help="strips per call")
     ap.add_argument("--device-prep", action="store_true", help="resize / normalise the strips on the GPU (MarconetPipeline.restore_images)")
+    ap.add_argument("--device-panel", action="store_true", help="also compose the saved panel on the GPU (MarconetPipeline.restore_panels); implies --device-prep")
     a = ap.parse_args()
     save_path = a.save_path or a.test_path.rstrip("/") + "_" + time.strftime("%m-%d_%H-%M", time.localtime()) + "_MARCONet"
     os.makedirs(save_path, exist_ok=True)
@@ -103,6 +125,9 @@ def main():
     for s0 in range(0, len(names), a.batch):
         chunk = names[s0:s0 + a.batch]
         paths = [os.path.join(a.test_path, f) for f in chunk]
+        if a.device_panel:
+            device_panels(pipe, paths, chunk, a.manual, save_path)
+            continue
         if a.device_prep:
             strips, done = device_strips(pipe, paths, a.manual)
         else:

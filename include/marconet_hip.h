@@ -372,6 +372,31 @@ enum { MNET_LQ_FORM_F32_NCHW = 0, MNET_LQ_FORM_U8_HWC = 1 };
 int mnet_lq_from_u8(const uint8_t* src, const mnet_lq_image* images, int32_t n, int32_t dst_h, int32_t canvas_w, void* dst, int32_t form,
                     void* stream);
 
+/* a17 on the device, the output side (test_sr.py:203-232; the counterpart of mnet_lq_from_u8's preview form): ONE launch composes, for every strip of
+ * a batch, the panel the script saves — dst uint8 [n][512][out_w][3] in the FILE's order (RGB), the bytes of
+ * marconet_amd/lq_io.py::panel_rgb_u8(panel(...)): clip(rint(panel), 0, 255) flipped BGR → RGB.  Rows of strip k, columns < show_w (the rest is 0;
+ * the WHOLE destination is written):
+ *     0..127   preview[preview_index][y][x][:]                      (uint8 [.][128][preview_w][3] RGB: mnet_lq_from_u8, MNET_LQ_FORM_U8_HWC)
+ *   128..255   the same, with (255,0,0) in rows 128..191 where x lies in a glyph's interval [a,b) and (0,0,255) in rows 192..255 where it lies in
+ *              [r,t): marks int32 [.][4] = a,b,r,t per glyph, rows glyph0 .. glyph0 + n_glyphs - 1 (the script's slices, resolved by the caller)
+ *   256..383   sr_bgr[k][y][x][2-c]                                  (uint8 [n][128][sr_w][3] BGR: mnet_sr_postprocess)
+ *   384..511   the strip's n_glyphs structure images side by side (prior_nhwc4 fp32 [.][128][128][4], RGB in channels 0..2, 16-byte aligned),
+ *              p * 0.5 + 0.5, resized to show_w columns with cv2's INTER_LINEAR arithmetic (lq_io.resize_linear: fp64 sample position
+ *              (x + 0.5) * step - 0.5, two taps, border clamp, fp32 p0 (1 - t) + p1 t, every operation rounded separately), * 255, rounded half to
+ *              even and saturated; file channel c = image channel 2 - c (the script stacks this RGB row into its BGR array as it is)
+ * `strips`: a DEVICE table of n descriptors; the caller computes per strip only scalars (step = 128.0 * n_glyphs / show_w).  A descriptor with
+ * show_w outside [0, out_w], a negative index or n_glyphs outside [1, 65536] is written as fill and not followed; indices that lie inside the
+ * tensors cannot take the kernel out of range.  MNET_E_ARG (nothing enqueued, checked before any HIP call) for a null pointer, n <= 0, out_w < 1,
+ * preview_w < out_w, sr_w < 1; MNET_E_ALIGN for a misaligned prior_nhwc4 (16), strips (8) or marks (4). */
+typedef struct {
+    int32_t show_w;             /* the strip's width at height 128: columns [0, show_w) carry the panel, the rest is 0 */
+    int32_t preview_index;      /* the strip's image in `preview`                                                      */
+    int32_t glyph0, n_glyphs;   /* its structure images in `prior_nhwc4` and its rows in `marks`                       */
+    double step;                /* 128.0 * n_glyphs / show_w: source step per destination column of the last row block */
+} mnet_panel_strip;
+int mnet_panel_u8(const uint8_t* preview, int32_t preview_w, const uint8_t* sr_bgr, int32_t sr_w, const float* prior_nhwc4,
+                  const mnet_panel_strip* strips, const int32_t* marks, int32_t n, int32_t out_w, uint8_t* dst, void* stream);
+
 /* Finiteness guard of the half-range precision modes (the role `torch.isfinite(y).all()` would play after test_sr.py:197 — the
  * reference has no such check because its fp32 activations cannot overflow): *flag (int32, device) is set to 0 and then to 1 by any
  * thread that finds an element of x (n elements, MNET_F32 or MNET_F16) that is inf or NaN.  One streaming read of x, no atomics

@@ -47,6 +47,12 @@ class LqImage(ctypes.Structure):
 
 LQ_FORM_F32_NCHW, LQ_FORM_U8_HWC = 0, 1
 
+
+class PanelStrip(ctypes.Structure):
+    """mirror of ``mnet_panel_strip`` (include/marconet_hip.h): one strip of mnet_panel_u8's device table"""
+    _fields_ = [("show_w", c_int), ("preview_index", c_int), ("glyph0", c_int), ("n_glyphs", c_int), ("step", c_double)]
+
+
 # name -> (restype, argtypes); every symbol include/marconet_hip.h declares
 SYMBOLS = {
     "mnet_last_error": (ctypes.c_char_p, []),
@@ -90,6 +96,7 @@ SYMBOLS = {
     "mnet_sr_postprocess": (c_int, [c_void_p, c_int, c_void_p, c_int, c_i64, c_int, c_void_p]),
     "mnet_nonfinite_flag": (c_int, [c_void_p, c_int, c_i64, c_void_p, c_void_p]),
     "mnet_lq_from_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "mnet_panel_u8": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "mnet_pack_weights": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p,
                                   c_void_p, c_void_p]),
     "mnet_pack_wsq": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),

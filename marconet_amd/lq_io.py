@@ -172,12 +172,17 @@ def panel(image, locs, n, show_sr, prior128, show=None):
     return np.vstack((show[:, :, ::-1], draw_locs(show, locs, n)[:, :, ::-1], np.asarray(show_sr)[:, :show.shape[1], :], prior))
 
 
-def save_panel(path, bgr):
-    """``cv2.imwrite(path, bgr)`` for that array: saturate to uint8 with round-half-to-even (cv2's ``saturate_cast<uchar>``), BGR on
-    the way in → RGB file"""
-    from PIL import Image
+def panel_rgb_u8(bgr):
+    """what ``cv2.imwrite`` makes of that array before it encodes: saturate to uint8 with round-half-to-even (cv2's ``saturate_cast<uchar>``),
+    BGR on the way in → the file's RGB.  (``panel_device.compose_panels`` returns these bytes from the device.)"""
     u8 = np.clip(np.rint(np.asarray(bgr, dtype=np.float64)), 0, 255).astype(np.uint8)
-    Image.fromarray(np.ascontiguousarray(u8[:, :, ::-1])).save(path)
+    return np.ascontiguousarray(u8[:, :, ::-1])
+
+
+def save_panel(path, bgr):
+    """``cv2.imwrite(path, bgr)`` for that array (``panel_rgb_u8``, then the PNG encoder)"""
+    from PIL import Image
+    Image.fromarray(panel_rgb_u8(bgr)).save(path)
 
 
 def load_png(path):

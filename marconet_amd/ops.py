@@ -17,7 +17,7 @@ from .packing import MX_DTYPE, SPLIT_DTYPE, is_split, mx_weight_rows, new_tensor
 
 __all__ = ["conv2d", "linear", "nchw_to_nhwc", "nhwc_to_nchw", "upsample2x", "affine_act", "groupnorm_affine",
            "adain_crop_concat", "adain_crop_concat_gn", "glyph_scatter_affine", "layernorm", "token_mix", "attention", "pixelnorm",
-           "embed_gather", "demod", "argmax_rows", "convert", "fused_bias_act", "sr_postprocess", "lq_from_u8", "conv3x3_rgb", "torgb", "stats",
+           "embed_gather", "demod", "argmax_rows", "convert", "fused_bias_act", "sr_postprocess", "lq_from_u8", "panel_u8", "conv3x3_rgb", "torgb", "stats",
            "pack_weights", "pack_wsq", "gather_rows", "style_rows", "nonfinite_flag", "gn_partial_buffer", "can_emit_gn_partial", "groupnorm_affine_from_partial",
            "ACT_NONE", "ACT_RELU", "ACT_LRELU", "ACT_LRELU_SQRT2", "ACT_TANH", "ACT_GELU", "ACT_SIGMOID"]
 
@@ -576,6 +576,41 @@ def lq_from_u8(src, table, dst_h, canvas_w, preview=False, out=None):
         raise TypeError("lq_from_u8: out must be %s %s" % (dtype, list(shape)))
     _lib.check(lib.mnet_lq_from_u8(_p(src), _p(table), n, dst_h, canvas_w, _p(out), _lib.LQ_FORM_U8_HWC if preview else _lib.LQ_FORM_F32_NCHW,
                                    _stream()), "mnet_lq_from_u8")
+    return out
+
+
+def panel_u8(preview, sr_bgr, prior_nhwc4, strips, marks, out_w=None, out=None):
+    """mnet_panel_u8 (test_sr.py:203-232 on the device; the bytes of lq_io.panel_rgb_u8(lq_io.panel(...))): ``preview`` uint8 [P,128,preview_w,3]
+    RGB (``lq_from_u8(preview=True)``), ``sr_bgr`` uint8 [n,128,sr_w,3] (``sr_postprocess``), ``prior_nhwc4`` fp32 [G,128,128,4] (the generator's
+    structure images), ``strips`` uint8 [n, sizeof(mnet_panel_strip)] (``_lib.PanelStrip``), ``marks`` int32 [G,4] — all on the device.
+    → uint8 [n,512,out_w,3] RGB (``out_w`` defaults to preview_w), 0 at the columns beyond a strip's show_w.  The kernel writes the whole of ``out``."""
+    lib = _lib.load()
+    _need_cuda(preview, sr_bgr, prior_nhwc4, strips, marks, out)
+    if preview.dtype != torch.uint8 or preview.dim() != 4 or preview.shape[1] != 128 or preview.shape[3] != 3:
+        raise TypeError("panel_u8: preview must be uint8 [P,128,W,3]")
+    if sr_bgr.dtype != torch.uint8 or sr_bgr.dim() != 4 or sr_bgr.shape[1] != 128 or sr_bgr.shape[3] != 3:
+        raise TypeError("panel_u8: sr_bgr must be uint8 [n,128,W,3]")
+    if prior_nhwc4.dtype != torch.float32 or prior_nhwc4.dim() != 4 or tuple(prior_nhwc4.shape[1:]) != (128, 128, 4):
+        raise TypeError("panel_u8: prior_nhwc4 must be fp32 [G,128,128,4]")
+    if strips.dtype != torch.uint8 or strips.dim() != 2 or strips.shape[1] != ctypes.sizeof(_lib.PanelStrip):
+        raise TypeError("panel_u8: a uint8 [n, %d] descriptor table expected" % ctypes.sizeof(_lib.PanelStrip))
+    if marks.dtype != torch.int32 or marks.dim() != 2 or marks.shape[1] != 4:
+        raise TypeError("panel_u8: marks must be int32 [G,4]")
+    n = int(strips.shape[0])
+    if n < 1 or sr_bgr.shape[0] != n:
+        raise ValueError("panel_u8: one SR image per descriptor expected (%d descriptors, %d images)" % (n, sr_bgr.shape[0]))
+    if prior_nhwc4.data_ptr() % 16 or strips.data_ptr() % 8:
+        raise ValueError("panel_u8: prior_nhwc4 must be 16-byte aligned and the descriptor table 8-byte aligned")
+    out_w = int(preview.shape[2]) if out_w is None else int(out_w)
+    if out_w < 1 or out_w > preview.shape[2]:
+        raise ValueError("panel_u8: out_w %d outside [1, preview width %d]" % (out_w, preview.shape[2]))
+    shape = (n, 512, out_w, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=preview.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.uint8:
+        raise TypeError("panel_u8: out must be torch.uint8 %s" % list(shape))
+    _lib.check(lib.mnet_panel_u8(_p(preview), int(preview.shape[2]), _p(sr_bgr), int(sr_bgr.shape[2]), _p(prior_nhwc4), _p(strips), _p(marks), n, out_w,
+                                 _p(out), _stream()), "mnet_panel_u8")
     return out
 
 

@@ -280,16 +280,66 @@ class MarconetPipeline:
         ``forward_blind``.
         ``details=True`` → ``(results, strips)``: per image also the dict ``restore_strips`` consumed (lq on the device, labels, locs, text,
         content_w, show_w) plus ``show``, the uint8 RGB preview [128, show_w, 3] (``lq_io.show_lq``, resized on the device); None where skipped."""
+        _, strips = self._strips_from_images(images, texts, boxes, max_glyphs, preview=details, host_preview=details)
+        live = [i for i, s in enumerate(strips) if s is not None and s["labels"].numel() > 0]
+        out = [None] * len(images)
+        for i, r in zip(live, self.restore_strips([strips[i] for i in live], with_prior=with_prior)):
+            out[i] = r
+        return (out, strips) if details else out
+
+    @torch.no_grad()
+    def restore_panels(self, images, texts=None, boxes=None, max_glyphs=16, details=False):
+        """``restore_images`` up to the file the script saves (test_sr.py:203-232): per image the panel — preview | preview with box marks | SR |
+        structure images — as a uint8 RGB host array [512, show_w, 3], the bytes of ``lq_io.panel_rgb_u8(lq_io.panel(...))`` of what
+        ``restore_images(..., with_prior=True, details=True)`` returns (``Image.fromarray(panel).save(path)`` writes ``lq_io.save_panel``'s file);
+        ``None`` where ``restore_images`` gives ``None``.  ``images`` / ``texts`` / ``boxes`` / ``max_glyphs`` as there.
+        Nothing per pixel happens on the host: the preview, the uint8 SR output and the generator's structure images stay on the device, one
+        launch composes all panels (``panel_device.compose_panels``) and ONE device→host copy brings them back.
+        ``details=True`` → ``(panels, strips)``: per image also the dict of its inputs (``text`` for the file name), None where too wide."""
+        from . import panel_device
+        if not self.need_prior_image:
+            raise ValueError("restore_panels needs MarconetPipeline(need_prior_image=True): the 128-px level is what produces the panel's last row")
+        dev = next(self.sr.parameters()).device
+        prep, strips = self._strips_from_images(images, texts, boxes, max_glyphs, preview=True, host_preview=False)
+        n_cls = self.gan.TextGenerator.class_num
+        keep = [i for i, s in enumerate(strips) if s is not None and s["labels"].numel() > 0
+                and int(s["labels"].min()) >= 0 and int(s["labels"].max()) < n_cls]                  # restore_strips' decisions
+        out = [None] * len(images)
+        if keep:
+            rows = [prep.index.index(i) for i in keep]
+            labels = [strips[i]["labels"] for i in keep]
+            counts = [int(l.shape[0]) for l in labels]
+            show_w = [strips[i]["show_w"] for i in keep]
+            locs = torch.zeros((len(keep), 2 * max(counts)), dtype=torch.float32)
+            for k, i in enumerate(keep):
+                locs[k, :strips[i]["locs"].shape[1]] = strips[i]["locs"][0]
+            with ops.on_device(prep.lq):
+                lq = prep.lq.index_select(0, torch.tensor(rows, device=dev))
+                lab, img_of = self._host_prep(labels, counts, dev)
+                prior = torch.empty((sum(counts), 128, 128, 4), dtype=torch.float32, device=dev)
+                y, flag = self._core(lq, lab, img_of, counts, locs, None, False, "u8_bgr", prior_images=prior)
+                self._raise_if_not_finite(flag)
+                panels = panel_device.compose_panels(prep.preview, rows, show_w, y, prior, counts, [strips[i]["locs"][0] for i in keep])
+            panels = panels.cpu().numpy()                                                            # the one device→host copy
+            for k, i in enumerate(keep):
+                out[i] = panels[k, :, :show_w[k], :]
+        return (out, strips) if details else out
+
+    @torch.no_grad()
+    def _strips_from_images(self, images, texts, boxes, max_glyphs, preview, host_preview):
+        """the per-strip inputs of ``restore_images`` / ``restore_panels``: → (``lq_device.Prepared``, list with one dict per image — lq on the
+        device, labels, locs, text, content_w, show_w; ``host_preview``: also ``show``, the preview copied to the host — or None for a strip
+        wider than 512 px at height 32)"""
         from . import lq_device, lq_io
         dev = next(self.sr.parameters()).device
-        prep = lq_device.prepare_strips(images, dev, preview=details, skip_too_wide=True)
+        prep = lq_device.prepare_strips(images, dev, preview=preview, skip_too_wide=True)
         strips = [None] * len(images)
         if prep.index:
             if texts is None:
                 logits, locs_lr, _ = self.encoder(prep.lq)
                 lab_all = clear_labels_batch(logits)
                 locs_all = locs_from_left_right(locs_lr).float().cpu()
-            show = prep.preview.cpu().numpy() if details else None
+            show = prep.preview.cpu().numpy() if host_preview else None
             for k, i in enumerate(prep.index):
                 h = int(images[i].shape[0])
                 if texts is None:
@@ -303,13 +353,9 @@ class MarconetPipeline:
                     labels = torch.tensor(lq_io.labels_from_text(text), dtype=torch.float32).type(torch.LongTensor).reshape(-1, 1)   # test_sr.py:179
                     locs = lq_io.locs_from_boxes(bx, h)
                 strips[i] = dict(lq=prep.lq[k:k + 1], labels=labels, locs=locs, text=text, content_w=prep.content_w[k], show_w=prep.show_w[k])
-                if details:
+                if host_preview:
                     strips[i]["show"] = show[k, :, :prep.show_w[k], :]
-        live = [i for i, s in enumerate(strips) if s is not None and s["labels"].numel() > 0]
-        out = [None] * len(images)
-        for i, r in zip(live, self.restore_strips([strips[i] for i in live], with_prior=with_prior)):
-            out[i] = r
-        return (out, strips) if details else out
+        return prep, strips
 
     @torch.no_grad()
     def forward_blind(self, lq, max_glyphs=16):
