@@ -40,9 +40,22 @@ extern "C" {
  * fp8 MFMA (v_mfma_scale_f32_32x32x64_f8f6f4, twice the f16 rate): 2 MFMA units per product instead of 3, ~16 significant bits.
  *   activations  bytes 0-63 hi = f16(v) of channels 0..31 | 64-95 lo8 = e4m3((v - hi) * 2^11 / s), channel order 0-7,16-23,8-15,24-31 |
  *                byte 96 E: s = 2^(E-127) = 2^(floor(log2 max|hi|) - 7) | bytes 97-127 zero
+ *                The whole rule for E (max|hi| over the block's 32 HALVES, not over v: a maximum that rounds up into the next binade takes that binade's scale):
+ *                  max|hi| > 0:   E = max(floor(log2 max|hi|) + 120, 105).  The floor 105 (s = 2^-22, max|hi| < 2^-15) is for blocks of fp16 subnormals, whose
+ *                                 rounding error stops shrinking with the block: with it (v - hi) * 2^11 / s is at most 2^8, without it it leaves e4m3's range.
+ *                                 In a block of normal halves it is at most 2^7: no writer ever saturates, and no finite input gives a NaN byte (0x7f / 0xff).
+ *                  max|hi| == 0:  E = 0 — a true all-zero block, and a block of values below 2^-25 alike.  Its lo bytes are e4m3((v - hi) * 0): zero bytes that keep
+ *                                 the residual's sign (0x00, or 0x80 where v < 0), exactly as a residual that underflows e4m3 in any other block does; the
+ *                                 block decodes to its hi halves (+-0) exactly.
+ *                  e4m3 rounds to nearest even.  Decoding is fl32(hi + lo8 * 2^(E - 138)), ONE rounding, with a lo scale of 0 for E < 12.
+ *                  Every writer — streaming kernels, layout kernels, every conv epilogue — and the host packer (marconet_amd/mxfmt.py) produce these bytes for
+ *                  finite input (tests/storage_codec.py is the rule as code).  The bytes of a block that holds an inf or a NaN are not defined beyond: that element
+ *                  decodes non-finite, the other blocks of the pixel are untouched.
  *   conv weights bytes 0-63 hi = f16(256 W) | 64-79 lo8 of channels 0-7,16-23 | 80-95 hi8 = e4m3(hi / s) of the same | 96-111 lo8 of
  *                8-15,24-31 | 112-127 hi8 of the same; s per OUTPUT channel; after the cout*kh*kw*cin elements one byte per output
- *                channel (E8M0 of s * 2^-11), i.e. a packed weight tensor is cout*kh*kw*cin*4 + cout bytes (mnet_pack_weights). */
+ *                channel (E8M0 of s * 2^-11), i.e. a packed weight tensor is cout*kh*kw*cin*4 + cout bytes (mnet_pack_weights).  The row's exponent is
+ *                clamp(floor(log2 max|hi|) + 120, 11, 254) — no floor at 105: a row with 0 < max|hi| < 2^-15 is outside the format (256 W of a layer never is) —
+ *                and 11 (trailing byte 0, signed-zero lo bytes as above) for a row whose every hi is +-0, e.g. a padding row. */
 typedef enum { MNET_F32 = 0, MNET_F16 = 1, MNET_F16X2 = 2, MNET_F16M = 3 } mnet_dtype;
 
 typedef enum {

@@ -288,7 +288,8 @@ __device__ __forceinline__ int hm_e8_raw(float m) { return max(0, (int)((__built
 // Activation blocks: floored at 2^(-15 - 7) for a non-zero block (round 6).  Below 2^-14 the hi halves are fp16 SUBNORMALS: their rounding error stops shrinking with the
 // block (2^-25 at most), so lo * 2^11 / s grows as the block shrinks and leaves e4m3's range for max |hi| < 2^-15 — where v_cvt_pk_fp8_f32 / v_cvt_scalef32_pk_fp8_f32
 // return NaN (0x7f), not the saturated byte (measured: tests/test_round6_gpu.py).  With the floor the scaled residual is at most 2^8; nothing is lost: the
-// lo byte's resolution at the floor, 2^-36, is far below the hi half's own 2^-25.  An all-zero block keeps exponent byte 0 (lo bytes 0).
+// lo byte's resolution at the floor, 2^-36, is far below the hi half's own 2^-25.  A block whose every hi is +-0 (all zeros, or values below 2^-25) keeps exponent byte 0; its
+// lo bytes are e4m3((v - hi) * 0): zero bytes that keep the residual's sign (include/marconet_hip.h) — what both encoders below give without an instruction for it.
 __device__ __forceinline__ int hm_e8_of(float m) {
     const int e = (int)((__builtin_bit_cast(unsigned, m) >> 23) & 255u) - 7;
     return e > 0 ? max(e, 105) : 0;
@@ -310,7 +311,7 @@ __device__ __forceinline__ u32x2 hm_encode_lo(const float* o, const f16x8& h, in
 #if MNET_HM_FAST
     // (v - hi) / 2^(e8 - 138): the conversion divides by the power of two whose exponent field its scale operand carries — field e8 - 11.  hi is a
     // HALF: a block's largest |hi| is 0 or >= 2^-24, so e8 is 0 (an all-zero block) or >= 96 — the fields 1 ... 10, and the field 0 that e8 = 11
-    // would ask for, never occur; the all-zero block divides by 2^127: zero bytes (the reference form multiplies by 0 there)
+    // would ask for, never occur; the zero-hi block divides by 2^127: signed zero bytes, the same as the reference form's multiplication by 0
     const float sc = __builtin_bit_cast(float, (unsigned)(e8 >= 12 ? e8 - 11 : 254) << 23);
     const u32x4 hp = bitcast<u32x4>(h);
     u32x2 r;

@@ -45,6 +45,9 @@ __global__ void __launch_bounds__(256) pack_weights_kernel(const float* __restri
             v = w[(((size_t)o * cin + i) * kh + rr) * kw + s];
             if (sigma) v = v / sg;                     // W_orig / sigma first (the reference's weight, an fp32 division), then the layer's constant scale
             v *= scale;
+            // (opaque: the fp32 PRODUCT is what every storage rounds — the host packer's bytes.  hipcc folded it into the f16 conversion of the plain-half build,
+            //  v_fma_mixlo_f16 v * scale + 0: one rounding instead of two (another half on double-rounding ties) and a -0 product stored as +0)
+            asm volatile("" : "+v"(v));
         }
         st_elem<T>(dst + (id - i), i, v);              // dst + first element of this (o, r, s) row; st_elem handles the split layout
     }
@@ -65,7 +68,9 @@ __global__ void __launch_bounds__(256) pack_weights_mx_kernel(const float* __res
         if (o >= cout || i >= cin) return 0.f;
         float v = w[(((size_t)o * cin + i) * kh + tap / kw) * kw + tap % kw];
         if (sigma) v = v / sg;
-        return v * scale;
+        v *= scale;
+        asm volatile("" : "+v"(v));                  // (opaque, as in pack_weights_kernel: pass 1's (f16)value(k) became v_fma_mixlo_f16 — a row maximum rounded once, the stored hi twice)
+        return v;
     };
     float m = 0.f;
     for (int k = t; k < K; k += 256) m = fmaxf(m, fabsf((float)(f16)value(k)));

@@ -5,12 +5,17 @@ One logical element = 4 bytes, blocked per 32 channels exactly like the split-ha
 
   activations   bytes 0-63    hi = f16(v), channels 0..31
                 bytes 64-95   lo8 = e4m3(lo * 2^11 / s), lo = v - hi, channel order PERM (0-7, 16-23 | 8-15, 24-31)
-                byte  96      E = E8M0 exponent of the block scale s = 2^(E - 127) = 2^(max(floor(log2 max|hi|), -15) - 7); 0 for an all-zero block
+                byte  96      E = E8M0 exponent of the block scale s = 2^(E - 127) = 2^(max(floor(log2 max|hi|), -15) - 7): E = max(floor(log2 max|hi|) + 120, 105)
+                              for a block with a non-zero hi (the floor 105 holds the scaled residual of fp16-subnormal blocks inside e4m3: at most 2^8);
+                              E = 0 for a block whose every hi is +-0 — an all-zero block, and a block of values below 2^-25 alike: its lo bytes are
+                              e4m3((v - hi) * 0), zero bytes that keep the residual's sign (0x00, or 0x80 for v < 0), and it decodes to its hi halves exactly
                 bytes 97-127  zero
+                decode        fl32(hi + lo8 * 2^(E - 138)), one rounding; the lo scale is 0 for E < 12
   conv weights  bytes 0-63    hi = f16(256 W)
                 bytes 64-79 lo8 of channels 0-7,16-23 | 80-95 hi8 of the same | 96-111 lo8 of 8-15,24-31 | 112-127 hi8 of the same
                 (hi8 = e4m3(hi / s), lo8 = e4m3(lo * 2^11 / s), s per OUTPUT CHANNEL), followed after the cout * K rows by one byte per
-                output channel: E8M0 of s * 2^-11
+                output channel: E8M0 of s * 2^-11.  E = clamp(floor(log2 max|hi|) + 120, 11, 254) over the row, 11 (trailing byte 0, signed-zero lo
+                bytes) for a row whose every hi is +-0; there is no floor at 105: a row with 0 < max|hi| < 2^-15 is outside the format
 
 x*w = hi*hi on the f16 MFMA + (w_lo8*x_hi8 + w_hi8*x_lo8) on the block-scaled fp8 MFMA (x_hi8 is derived from hi in the kernel).
 """
@@ -49,7 +54,7 @@ def pack_act(x):
     lo = xb - hi.float()
     e8 = block_e8(hi.float())
     s = torch.pow(2.0, (e8 - 127).float())
-    lo8 = _e4m3(lo * 2048.0 / s)
+    lo8 = _e4m3(torch.where(e8 > 0, lo * 2048.0 / s, lo * 0.0))          # max|hi| == 0: zero bytes (signed), not the residual under s = 2^-127
     out = torch.zeros(xb.shape[:-1] + (128,), dtype=torch.uint8, device=x.device)
     out[..., 0:64] = hi.contiguous().view(torch.uint8)
     out[..., 64:96] = lo8[..., PERM].contiguous().view(torch.uint8)
@@ -79,7 +84,7 @@ def pack_weight(w):
     e8 = (_floor_log2(m) - 7 + 127).clamp(11, 254).to(torch.int32)          # per output channel
     s = torch.pow(2.0, (e8 - 127).float()).reshape(O, 1, 1, 1, 1)
     hi8 = _e4m3(hi.float() / s)
-    lo8 = _e4m3(lo * 2048.0 / s)
+    lo8 = _e4m3(torch.where(e8.reshape(O, 1, 1, 1, 1) > 11, lo * 2048.0 / s, lo * 0.0))      # an all-zero-hi row: zero bytes, as in pack_act
     rows = torch.zeros((O, KH, KW, I // 32, 128), dtype=torch.uint8, device=w.device)
     rows[..., 0:64] = hi.contiguous().view(torch.uint8)
     p0, p1 = PERM[:16], PERM[16:]

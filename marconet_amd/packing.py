@@ -128,9 +128,9 @@ def split_halves(t):
     if t.shape[-1] % 32 != 0:
         raise ValueError("split-half tensors need a multiple of 32 channels, got %d" % t.shape[-1])
     t = t.detach().float().contiguous()
-    if t.numel() and float(t.abs().max()) > 65000.0:
-        raise OverflowError("value %.3g does not fit the half range of the fp16x3 mode" % float(t.abs().max()))
     hi = t.to(torch.float16)
+    if not bool(torch.isfinite(hi).all()):          # the half range itself (|v| < 65520), like mxfmt.pack_weight and the check on the device packer's output
+        raise OverflowError("value %.3g does not fit the half range of the fp16x3 mode" % float(t.abs().max()))
     lo = (t - hi.float()).to(torch.float16)
     blk = t.shape[:-1] + (t.shape[-1] // 32, 32)
     both = torch.stack((hi.reshape(blk), lo.reshape(blk)), dim=-2).contiguous()          # [..., C/32, 2, 32] halves
