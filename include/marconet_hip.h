@@ -179,7 +179,18 @@ enum { MNET_CONV_ALGO_AUTO = 0, MNET_CONV_ALGO_REG_STAGED = 1, MNET_CONV_ALGO_LD
                                              * into its conv2 as extra K instead of a separate launch + a residual read.  wgt is the ordinary
                                              * [cout][kh][kw][c0+c1] tensor whose x1 part is only read at the centre tap; x1 is NHWC
                                              * [n,h,w,c1] like x0 (stride 1 launches).  LDS-DMA kernel only (MNET_E_ARG when the launch is
-                                             * not eligible for it); mnet_conv2d_flops still counts x1 at every tap. */ };
+                                             * not eligible for it); mnet_conv2d_flops still counts x1 at every tap. */,
+       MNET_CONV_ALGO_FLAG_SHUFFLE2 = 1024 /* OR-ed in: pixel-shuffle output mode — conv3x3(bilinear_x2(x)) in polyphase form.  The launch is the
+                                             * 3x3 / stride 1 / pad 1 conv on the LOW-res map [n,h,w,c0] with cout = 4 C output channels, phase-major
+                                             * (channel (2 py + px) C + c is phase (py,px) of channel c; wgt and bias packed accordingly), and y is
+                                             * the [n,2h,2w,C] tensor: channel block b of low-res pixel (i,j) is stored as block b % (C/32) of
+                                             * hi-res pixel (2i + py, 2j + px), (py,px) = b / (C/32).  gn_partial keeps its [n*h*w/32][cout/32][2]
+                                             * layout — which IS [n*2h*2w/32][C/32][2] of y — with the low-res border ring (i in {0,h-1} or j in
+                                             * {0,w-1}: the hi-res ring the caller rewrites, mnet_polyphase_ring_fix) left out of the sums.
+                                             * MNET_F16M, one source, C % 32 == 0, h, w >= 4, w % 32 == 0, no residual / scale vectors / valid_w,
+                                             * and only on the LDS-DMA builds that carry the mode (AUTO picks one; ids 10, 15, 16): MNET_E_ARG
+                                             * otherwise, nothing enqueued. */,
+       MNET_CONV_ALGO_FLAGS = 256 | 512 | 1024 };
 int mnet_conv2d_nhwc_ex(const mnet_conv_desc* d, int32_t algo, void* stream);
 
 /* split-K form of the skinny kernel for a "patchify" conv (filter == stride, no padding; fp32; <= 512 output pixels) — the
@@ -246,6 +257,16 @@ int mnet_groupnorm_affine(const void* x, int32_t dtype, int32_t n, int32_t h, in
  * order, count = h * min(valid_w[n], w) * 32 per group.  One wave per (image, group): no pass over the map. */
 int mnet_groupnorm_affine_from_partial(const float* partial, int32_t n, int32_t h, int32_t w, int32_t c, const int32_t* valid_w,
                                        const float* gamma, const float* beta, float eps, float* scale, float* shift, void* stream);
+
+/* Ring fix-up of a MNET_CONV_ALGO_FLAG_SHUFFLE2 convolution's output y [n,h2,w2,c] (MNET_F16M; h2 = 2h, w2 = 2w): hi-res rows and columns {0, 1, last two} are
+ * copied from the two-launch form (up-sample + conv) run on four thin strips — top / bottom [n,4,w2,c] (low-res rows 0..1 / h-2..h-1: their hi-res rows 0..1 / 2..3 are
+ * kept, all columns), left / right [n,h2,4,c] (low-res columns 0..1 / w-2..w-1: hi-res columns 0..1 / 2..3, rows 2..h2-3).  sums [n][c/32][2] (fp64) receives the sum and
+ * the sum of squares of the stored ring values per (image, 32-channel group), folded in a fixed order. */
+int mnet_polyphase_ring_fix(const void* top, const void* bottom, const void* left, const void* right, void* y, int32_t dtype,
+                            int32_t n, int32_t h2, int32_t w2, int32_t c, double* sums, void* stream);
+/* mnet_groupnorm_affine_from_partial for such an output [n,h,w,c] (hi-res): the main launch's partial sums (border ring left out) plus ring_sums */
+int mnet_groupnorm_affine_from_partial_ring(const float* partial, const double* ring_sums, int32_t n, int32_t h, int32_t w, int32_t c,
+                                            const float* gamma, const float* beta, float eps, float* scale, float* shift, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * per-glyph prior transform of TSPSRNet (networks.py:421-449 and :455-482)

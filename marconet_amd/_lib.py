@@ -14,6 +14,7 @@ MNET_F32, MNET_F16, MNET_F16X2, MNET_F16M = 0, 1, 2, 3
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_LRELU_SQRT2, ACT_TANH, ACT_GELU, ACT_SIGMOID = range(7)
 ALGO_AUTO, ALGO_REG_STAGED, ALGO_LDS_DMA, ALGO_SKINNY, ALGO_DMA_CFG0, ALGO_STRIP_CFG0, ALGO_DMA_CFG16, ALGO_FLAG_ONE_TILE = 0, 1, 2, 3, 16, 32, 64, 256
 ALGO_FLAG_X1_CENTER = 512     # x1 contributes through the filter's centre tap only (a 1x1 skip conv folded into the k-loop)
+ALGO_FLAG_SHUFFLE2 = 1024     # pixel-shuffle output mode: conv3x3(bilinear x2) in polyphase form (cout = 4 C phase-major, y = [n,2h,2w,C])
 
 c_int, c_void_p, c_float, c_double, c_i64 = ctypes.c_int32, ctypes.c_void_p, ctypes.c_float, ctypes.c_double, ctypes.c_int64
 
@@ -71,6 +72,8 @@ SYMBOLS = {
     "mnet_groupnorm_affine": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                       c_float, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "mnet_groupnorm_affine_from_partial": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    "mnet_polyphase_ring_fix": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "mnet_groupnorm_affine_from_partial_ring": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
     "mnet_adain_crop_concat": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mnet_adain_crop_concat_gn": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,

@@ -331,7 +331,8 @@ extern "C" int mnet_groupnorm_affine(const void* x, int32_t dtype, int32_t n, in
 // ---------------------------------------------------------------------------- the same affine from epilogue partial sums (round 5)
 // partial[(n * frags + f) * G + g] = (sum, sum of squares) of fragment f (32 consecutive pixels) x group g, written by the producing convolution's
 // epilogue (mnet_conv_desc.gn_partial).  One wave per (group, image): lane l folds fragments l, l + 64, ... in fp64, then a fixed butterfly.
-__global__ void __launch_bounds__(64) gn_finalize_frag_kernel(const float* __restrict__ partial, int frags, int H, int W, int C,
+// `ring` (or nullptr): fp64 [n][G][2] sums the fragments leave out — the hi-res ring of a polyphase convolution's output, summed by polyphase_ring_kernel.
+__global__ void __launch_bounds__(64) gn_finalize_frag_kernel(const float* __restrict__ partial, const double* __restrict__ ring, int frags, int H, int W, int C,
                                                               const int* __restrict__ valid_w, const float* __restrict__ gamma,
                                                               const float* __restrict__ beta, float eps, float* __restrict__ scale,
                                                               float* __restrict__ shift) {
@@ -340,6 +341,7 @@ __global__ void __launch_bounds__(64) gn_finalize_frag_kernel(const float* __res
     double S = 0.0, SS = 0.0;
     for (int f = lane; f < frags; f += 64) { const f32x2 v = pp[(size_t)f * G]; S += (double)v[0]; SS += (double)v[1]; }
     S = wave_sum_d(S); SS = wave_sum_d(SS);
+    if (ring) { S += ring[((size_t)n * G + g) * 2]; SS += ring[((size_t)n * G + g) * 2 + 1]; }
     const int vw = valid_w ? min(valid_w[n], W) : W;
     const MeanRstd m = gn_mean_rstd(S, SS, (double)H * vw * 32.0, eps);
     if (lane < 32) {
@@ -355,8 +357,92 @@ extern "C" int mnet_groupnorm_affine_from_partial(const float* partial, int32_t 
     MNET_CHECK_ARG(partial && gamma && beta && scale && shift, "groupnorm_from_partial: null pointer");
     MNET_CHECK_ARG(n > 0 && n <= 65535 && h > 0 && w > 0 && c > 0 && c % 32 == 0 && (h * w) % 32 == 0, "groupnorm_from_partial: bad geometry (c %% 32, h*w %% 32)");
     MNET_CHECK_ALIGN((reinterpret_cast<uintptr_t>(partial) & 7u) == 0, "groupnorm_from_partial: partial must be 8-byte aligned");
-    hipLaunchKernelGGL(gn_finalize_frag_kernel, dim3(c / 32, n), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), partial, h * w / 32, h, w, c,
+    hipLaunchKernelGGL(gn_finalize_frag_kernel, dim3(c / 32, n), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), partial, (const double*)nullptr, h * w / 32, h, w, c,
                        valid_w, gamma, beta, eps, scale, shift);
+    MNET_LAUNCH_CHECK("gn_finalize_frag");
+    return MNET_OK;
+}
+
+// ---------------------------------------------------------------------------- ring fix-up of a polyphase conv3x3(bilinear x2) (MNET_CONV_ALGO_FLAG_SHUFFLE2)
+// The polyphase form zero-pads at LOW resolution where conv(up(x)) clamps the up-sample and zero-pads at hi resolution: hi-res rows and columns {0, 1, last two} of y
+// differ.  The caller runs the two-launch form on four thin strips (low-res rows 0..1 / H-2..H-1, columns 0..1 / W-2..W-1) and this kernel copies their ring parts over y:
+//     top    [n,4,W2,c]: rows 0..1            → y rows 0..1           bottom [n,4,W2,c]: rows 2..3    → y rows H2-2..H2-1     (all columns: the corners)
+//     left   [n,H2,4,c]: columns 0..1         → y columns 0..1        right  [n,H2,4,c]: columns 2..3 → y columns W2-2..W2-1  (rows 2..H2-3)
+// and sums what it stores, in fp64, per (image, 32-channel group): sums[n][c/32][2], the part of the GroupNorm statistics the main launch's epilogue leaves out.
+// Grid (c/32, n); thread t takes ring pixels t, t + 256, ... of its group's 128-byte block; a fixed fold (butterfly per wave, then the four waves in order).
+__global__ void __launch_bounds__(256) polyphase_ring_kernel(const unsigned char* __restrict__ top, const unsigned char* __restrict__ bottom,
+                                                             const unsigned char* __restrict__ left, const unsigned char* __restrict__ right,
+                                                             unsigned char* __restrict__ y, int H2, int W2, int C, double* __restrict__ sums) {
+    __shared__ double red[4][2];
+    const int g = blockIdx.x, n = blockIdx.y, G = C / 32, t = threadIdx.x;
+    const size_t px = (size_t)C * 4;                                    // bytes per pixel (fp16+8: 128 per 32-channel block)
+    const int nrow = 4 * W2, R = nrow + 4 * (H2 - 4);
+    double S = 0.0, SS = 0.0;
+    for (int r = t; r < R; r += 256) {
+        const unsigned char* src;
+        int row, col;
+        if (r < nrow) {
+            const int bot = r >= 2 * W2, q = r - bot * 2 * W2, sr = q / W2;
+            col = q - sr * W2;
+            row = bot ? H2 - 2 + sr : sr;
+            src = (bot ? bottom : top) + (((size_t)n * 4 + (bot ? 2 + sr : sr)) * W2 + col) * px;
+        } else {
+            const int q = r - nrow, ci = q & 3;
+            row = 2 + (q >> 2);
+            col = ci < 2 ? ci : W2 - 4 + ci;
+            src = (ci < 2 ? left : right) + (((size_t)n * H2 + row) * 4 + ci) * px;
+        }
+        src += (size_t)g * 128;
+        unsigned char* dst = y + (((size_t)n * H2 + row) * W2 + col) * px + (size_t)g * 128;
+        u32x4 b[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) b[k] = ldg16(src + k * 16);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) stg16(dst + k * 16, b[k]);
+        const float sl = hm_lo_scale((int)(b[6][0] & 255u));
+        float a = 0.f, q2 = 0.f;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {                                   // lo bytes of chunk c: 8-byte slot hm_lo_slot(c) of the block's bytes 64..95
+            const int slot = hm_lo_slot(c);
+            float v[8];
+            hm_decode8(b[c], u32x2{b[4 + (slot >> 1)][2 * (slot & 1)], b[4 + (slot >> 1)][2 * (slot & 1) + 1]}, sl, v);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { a += v[j]; q2 = fmaf(v[j], v[j], q2); }
+        }
+        S += (double)a; SS += (double)q2;
+    }
+    S = wave_sum_d(S); SS = wave_sum_d(SS);
+    if ((t & 63) == 0) { red[t >> 6][0] = S; red[t >> 6][1] = SS; }
+    __syncthreads();
+    if (t == 0) {
+        double* o = sums + ((size_t)n * G + g) * 2;
+        o[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
+        o[1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
+    }
+}
+
+extern "C" int mnet_polyphase_ring_fix(const void* top, const void* bottom, const void* left, const void* right, void* y, int32_t dtype,
+                                       int32_t n, int32_t h2, int32_t w2, int32_t c, double* sums, void* stream) {
+    MNET_CHECK_ARG(top && bottom && left && right && y && sums, "polyphase_ring_fix: null pointer");
+    MNET_CHECK_ARG(dtype == MNET_F16M, "polyphase_ring_fix: MNET_F16M tensors only");
+    MNET_CHECK_ARG(n > 0 && n <= 65535 && h2 >= 8 && w2 >= 8 && h2 % 2 == 0 && w2 % 2 == 0 && c > 0 && c % 32 == 0, "polyphase_ring_fix: bad geometry (hi-res h, w even and >= 8, c %% 32)");
+    MNET_CHECK_ARG(4ll * w2 + 4ll * h2 < (1ll << 30), "polyphase_ring_fix: map too large");
+    MNET_CHECK_ALIGN(aligned128(top) && aligned128(bottom) && aligned128(left) && aligned128(right) && aligned128(y) && (reinterpret_cast<uintptr_t>(sums) & 7u) == 0,
+                     "polyphase_ring_fix: tensors must be 128-byte aligned, sums 8-byte aligned");
+    hipLaunchKernelGGL(polyphase_ring_kernel, dim3(c / 32, n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), (const unsigned char*)top, (const unsigned char*)bottom,
+                       (const unsigned char*)left, (const unsigned char*)right, (unsigned char*)y, h2, w2, c, sums);
+    MNET_LAUNCH_CHECK("polyphase_ring");
+    return MNET_OK;
+}
+
+// mnet_groupnorm_affine_from_partial of a polyphase convolution's output [n,h,w,c] (hi-res): the epilogue's partial sums (ring left out) + the ring's fp64 sums
+extern "C" int mnet_groupnorm_affine_from_partial_ring(const float* partial, const double* ring_sums, int32_t n, int32_t h, int32_t w, int32_t c,
+                                                       const float* gamma, const float* beta, float eps, float* scale, float* shift, void* stream) {
+    MNET_CHECK_ARG(partial && ring_sums && gamma && beta && scale && shift, "groupnorm_from_partial_ring: null pointer");
+    MNET_CHECK_ARG(n > 0 && n <= 65535 && h > 0 && w > 0 && c > 0 && c % 32 == 0 && (h * w) % 128 == 0, "groupnorm_from_partial_ring: bad geometry (c %% 32, h*w %% 128)");
+    MNET_CHECK_ALIGN((reinterpret_cast<uintptr_t>(partial) & 7u) == 0 && (reinterpret_cast<uintptr_t>(ring_sums) & 7u) == 0, "groupnorm_from_partial_ring: buffers must be 8-byte aligned");
+    hipLaunchKernelGGL(gn_finalize_frag_kernel, dim3(c / 32, n), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), partial, ring_sums, h * w / 32, h, w, c,
+                       (const int*)nullptr, gamma, beta, eps, scale, shift);
     MNET_LAUNCH_CHECK("gn_finalize_frag");
     return MNET_OK;
 }

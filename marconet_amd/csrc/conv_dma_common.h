@@ -96,7 +96,30 @@ struct AccArray {
     const f32x16 (&r)[FA][FB];
     __device__ __forceinline__ float get(int fa, int px, int q) const { return r[fa][px][q]; }
 };
-template <int BC, int BP, int WC, int WP, int FC, int FP, int XL = 64, bool GN = true, typename ACC>
+// MNET_CONV_ALGO_FLAG_SHUFFLE2 (SHUF builds of the fp16+8 epilogues): the launch is a conv with cout = 4 C output channels, phase-major, on the low-res map [N,H,W] and
+// y is the [N,2H,2W,C] tensor — channel block `blk` (of cout) of low-res pixel (n,i,j) is block blk % (C/32) of hi-res pixel (n, 2i + py, 2j + px), (py,px) = blk / (C/32).
+// A hi-res pixel is C * 4 = cout bytes.  The planner admits W % 32 == 0 only: a 32-pixel fragment (aligned to 32) lies in ONE low-res row, so the hi-res pixel index of
+// phase (0,0) of its pixel t is hib + 2 t with the wave-uniform hib = 4 pixb - 2 (pixb % W), and a phase adds (py * 2W + px) pixels.
+struct Shuf2Frag {
+    long long hib;          // hi-res pixel index of phase (0,0) of the fragment's first pixel
+    int ib, jb;             // low-res row / first column of the fragment
+};
+__device__ __forceinline__ Shuf2Frag shuf2_frag(const ConvArgs& p, int pixb) {
+    const int rem = pixb % p.howo, ib = rem / p.wo, jb = rem - ib * p.wo;
+    return {4ll * pixb - 2 * jb, ib, jb};
+}
+// byte offset of channel block `blk` (of cout) inside the fragment's hi-res window, relative to phase (0,0) of the fragment's first pixel
+__device__ __forceinline__ int shuf2_block_off(const ConvArgs& p, int blk) {
+    const int G = p.cout >> 7, ph = blk / G, g = blk - ph * G;
+    return ((ph >> 1) * 2 * p.wo + (ph & 1)) * p.cout + g * 128;
+}
+// the low-res border ring (i in {0, H-1} or j in {0, W-1}) is left out of the GroupNorm sums of a SHUFFLE2 launch: its hi-res pixels are rewritten by the ring fix-up
+__device__ __forceinline__ bool shuf2_interior(const ConvArgs& p, const Shuf2Frag& f, int t) {
+    const int j = f.jb + t;
+    return f.ib > 0 && f.ib < p.ho - 1 && j > 0 && j < p.wo - 1;
+}
+
+template <int BC, int BP, int WC, int WP, int FC, int FP, int XL = 64, bool GN = true, bool SHUF = false, typename ACC>
 __device__ __forceinline__ void dma_epilogue_mx_acc(const ConvArgs& p, const ACC& acc32, int co0, int pix0, int wc, int wp, int lane,
                                                     unsigned char* xpose = nullptr) {
     static_assert(XL == 64 || XL == 16, "scratch of 4 KiB or 1 KiB per wave");
@@ -112,10 +135,17 @@ __device__ __forceinline__ void dma_epilogue_mx_acc(const ConvArgs& p, const ACC
         const int pixb = pix0 + wp * (BP / WP) + px * 32;                   // first pixel of this wave's 32
         const int pix = pixb + (lane & 31);
         const int n_img = min(pix, last_pix) / p.howo;
+        Shuf2Frag sf = {0, 0, 0};
+        if constexpr (SHUF) sf = shuf2_frag(p, pixb);
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
             const int cob = co0 + wc * (BC / WC) + b * 64;                  // first channel of lane-half 0's block
             const int co = cob + h * 32;                                    // first channel of this lane's block
+            // SHUF: where block (cob >> 5) + hsel of the fragment's pixel t goes (the block's address is all that changes: the same 128-byte block stores)
+            const int sho0 = SHUF ? shuf2_block_off(p, cob >> 5) : 0, sho1 = SHUF ? shuf2_block_off(p, min((cob >> 5) + 1, (p.cout >> 5) - 1)) : 0;
+            auto shuf_addr = [&](int t, int hsel) __attribute__((always_inline)) -> unsigned char* {
+                return reinterpret_cast<unsigned char*>(p.y) + (size_t)(sf.hib + 2 * t) * p.cout + (hsel ? sho1 : sho0);
+            };
             float v[32];
 #pragma unroll
             for (int q = 0; q < 16; ++q) { v[q] = acc32.get(2 * b, px, q) * MNET_SPLIT_WSCALE_INV; v[16 + q] = acc32.get(2 * b + 1, px, q) * MNET_SPLIT_WSCALE_INV; }
@@ -181,6 +211,7 @@ __device__ __forceinline__ void dma_epilogue_mx_acc(const ConvArgs& p, const ACC
                         const int ow = p.wo_shift >= 0 ? (pix & (p.wo - 1)) : pix % p.wo;
                         ok = ok && ow < p.valid_w[n_img];
                     }
+                    if constexpr (SHUF) ok = ok && shuf2_interior(p, sf, lane & 31);
                     gs1 = ok ? gs1 : 0.f; gs2 = ok ? gs2 : 0.f;
 #pragma unroll
                     for (int o = 1; o < 32; o <<= 1) { gs1 += __shfl_xor(gs1, o, 64); gs2 += __shfl_xor(gs2, o, 64); }
@@ -203,6 +234,7 @@ __device__ __forceinline__ void dma_epilogue_mx_acc(const ConvArgs& p, const ACC
             u32x2 lo[4];
             if (!xpose) {
                 unsigned char* yb = reinterpret_cast<unsigned char*>(p.y) + (size_t)pix * p.cout * 4 + (co >> 5) * 128;
+                if constexpr (SHUF) yb = shuf_addr(lane & 31, h);
 #pragma unroll
                 for (int c = 0; c < 4; ++c) { stg16(yb + c * 16, bitcast<u32x4>(hh[c])); lo[c] = hm_encode_lo_ref(v + c * 8, hh[c], e8); }
                 // lo bytes in the order 0-7,16-23 | 8-15,24-31 (slot of chunk c = hm_lo_slot(c))
@@ -249,6 +281,9 @@ __device__ __forceinline__ void dma_epilogue_mx_acc(const ConvArgs& p, const ACC
                     for (int k = 0; k < 4; ++k) {
                         const unsigned P = (L >> 2) + 16u * k;
                         const int ppix = pixb + (int)(P & 31u), pco = cob + (int)(P >> 5) * 32;
+                        if constexpr (SHUF) {
+                            if (ppix < p.npix && pco < p.cout) stg16(shuf_addr((int)(P & 31u), (int)(P >> 5)) + half * 64 + j * 16, piece[k]);
+                        } else
                         if (ppix < p.npix && pco < p.cout)
                             stg16(reinterpret_cast<unsigned char*>(p.y) + (size_t)ppix * p.cout * 4 + (pco >> 5) * 128 + half * 64 + j * 16, piece[k]);
                     }
@@ -263,6 +298,9 @@ __device__ __forceinline__ void dma_epilogue_mx_acc(const ConvArgs& p, const ACC
                         const unsigned Pq = L >> 2, P = 16u * r + Pq;
                         const u32x4 piece = *reinterpret_cast<const u32x4*>(xpose + ((4u * Pq + (j ^ ((Pq >> 1) & 3u))) << 4));
                         const int ppix = pixb + (int)(P & 31u), pco = cob + (int)(P >> 5) * 32;
+                        if constexpr (SHUF) {
+                            if (ppix < p.npix && pco < p.cout) stg16(shuf_addr((int)(P & 31u), (int)(P >> 5)) + half * 64 + j * 16, piece);
+                        } else
                         if (ppix < p.npix && pco < p.cout)
                             stg16(reinterpret_cast<unsigned char*>(p.y) + (size_t)ppix * p.cout * 4 + (pco >> 5) * 128 + half * 64 + j * 16, piece);
                     }
@@ -273,10 +311,10 @@ __device__ __forceinline__ void dma_epilogue_mx_acc(const ConvArgs& p, const ACC
     }
 }
 
-template <int BC, int BP, int WC, int WP, int FC, int FP, int XL = 64, bool GN = true>
+template <int BC, int BP, int WC, int WP, int FC, int FP, int XL = 64, bool GN = true, bool SHUF = false>
 __device__ __forceinline__ void dma_epilogue_mx(const ConvArgs& p, const f32x16 (&acc32)[FC / 2][FP / 2], int co0, int pix0, int wc, int wp, int lane,
                                                 unsigned char* xpose = nullptr) {
-    dma_epilogue_mx_acc<BC, BP, WC, WP, FC, FP, XL, GN>(p, AccArray<FC / 2, FP / 2>{acc32}, co0, pix0, wc, wp, lane, xpose);
+    dma_epilogue_mx_acc<BC, BP, WC, WP, FC, FP, XL, GN, SHUF>(p, AccArray<FC / 2, FP / 2>{acc32}, co0, pix0, wc, wp, lane, xpose);
 }
 
 // Epilogue of one (cout tile co0, pixel tile pix0): identical math to conv_igemm.hip.  Every lane owns NG groups of 8

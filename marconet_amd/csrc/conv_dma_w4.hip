@@ -91,7 +91,11 @@ static_assert(FA * FB == NDMA, "one DMA piece behind each scaled MFMA");
 // ACC::block(fa, px) takes a block's 16 values out of the accumulator file where they are consumed.  `par`: this wave's parameter area (w4::PB bytes).
 // SC / RG: the launch has out_scale or post_scale / a residual or GroupNorm sums.  Four builds of the kernel (launch_conv_dma_w4 picks): a tile without them runs an
 // epilogue without their code, branches and kernel-argument reloads — measured on the bias + activation launches: 36 000 -> 29 000 cycles per tile (profiles/r6m_*).
-template <bool SC, bool RG, typename ACC, typename STAMP>
+// SHUF: the MNET_CONV_ALGO_FLAG_SHUFFLE2 output mode (conv_dma_common.h, Shuf2Frag) — builds of their own (conv_dma_w4_shuf.hip); only a block's address and the GroupNorm
+// sums' mask (the low-res border ring instead of valid_w) change.  Every store stays an unconditional raw buffer store: the descriptor's window runs from phase (0,0) of
+// the tile's first pixel to phase (1,1) of its last valid one (a 256-pixel run of low-res pixels and the second hi-res row of its phases: 32-bit offsets); a hi-res index is
+// not monotonic in the low-res pixel across phases, so a pixel >= npix gets the out-of-range offset explicitly.
+template <bool SC, bool RG, bool SHUF = false, typename ACC, typename STAMP>
 __device__ __forceinline__ void w4_epilogue(const ConvArgs& p_, const ACC& acc, int co0, int pix0, int wc, int wp, int lane, unsigned char* xpose, unsigned char* par, STAMP&& stamp) {
 #pragma clang fp contract(off)      // every product and sum rounded on its own, as in dma_epilogue_mx — whose runtime arms keep hipcc from fusing across them; in this straight-line
                                     // form it fused scale * acc + bias into an fma
@@ -121,6 +125,13 @@ __device__ __forceinline__ void w4_epilogue(const ConvArgs& p_, const ACC& acc, 
     //  dma_epilogue_mx, which skips the add, keeps it; +0 would store +0 there: other bytes)
     for (int b = 0; b < NB; ++b) par_f[b * 64 + lane] = p.bias ? p.bias[min(cob[b] + lane, p.cout - 1)] : -0.f;
     struct Step { float osc1, psc1; u32x4 rh[4], rl[2]; unsigned re8; int pixb, pix, n_img, vw; };
+    int sho[NB][2];                                                         // SHUF: byte offset of block (cob[b] >> 5) + hsel inside a fragment's hi-res window
+    long long hib0 = 0;                                                     // SHUF: hi-res pixel index of phase (0,0) of the tile's first pixel (the descriptor's base)
+    if constexpr (SHUF) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b) { sho[b][0] = shuf2_block_off(p, cob[b] >> 5); sho[b][1] = shuf2_block_off(p, min((cob[b] >> 5) + 1, (p.cout >> 5) - 1)); }
+        hib0 = shuf2_frag(p, pix0).hib;
+    }
     auto request = [&](int t, Step& S) __attribute__((always_inline)) {     // addresses + parameter loads of step t (no use of the values here)
         const int px = t / NB, b = t % NB;
         S.pixb = pix0 + wp * (BP / WP) + px * 32;                           // first pixel of this wave's 32
@@ -151,8 +162,15 @@ __device__ __forceinline__ void w4_epilogue(const ConvArgs& p_, const ACC& acc, 
     // after the next step's parameter loads path-dependent, and hipcc's s_waitcnt pass then waits with vmcnt(0) — for the stores — in front of every step (measured: 59
     // vmcnt(0) waits per epilogue, 90 000 cycles per tile)
     const int tile_px = min(BP, p.npix - pix0);
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<unsigned char*>(p.y) + (size_t)pix0 * p.cout * 4, 0,
-                                                                         __builtin_amdgcn_readfirstlane(tile_px * p.cout * 4), 0x00020000);
+    size_t ry_base = (size_t)pix0 * p.cout * 4;
+    int ry_bytes = tile_px * p.cout * 4;
+    if constexpr (SHUF) {
+        const Shuf2Frag fl = shuf2_frag(p, pix0 + tile_px - 1);              // (a one-pixel "fragment": phase (0,0) of the tile's last valid pixel)
+        ry_base = (size_t)hib0 * p.cout;
+        ry_bytes = (int)(fl.hib + 2 * p.wo + 2 - hib0) * p.cout;
+    }
+    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<unsigned char*>(p.y) + ry_base, 0,
+                                                                         __builtin_amdgcn_readfirstlane(ry_bytes), 0x00020000);
     const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc(gnp, 0, __builtin_amdgcn_readfirstlane(gnp ? (p.npix >> 5) * (p.cout >> 5) * 8 : 0), 0x00020000);
     Step cur;
     request(0, cur);
@@ -161,6 +179,8 @@ __device__ __forceinline__ void w4_epilogue(const ConvArgs& p_, const ACC& acc, 
     for (int t = 0; t < NS; ++t) {
         const int px = t / NB, b = t % NB;
         const int pixb = cur.pixb, pix = cur.pix;
+        Shuf2Frag sf = {0, 0, 0};
+        if constexpr (SHUF) sf = shuf2_frag(p, pixb);
         float* const stepbuf = par_f + NB * 64 + (t & 1) * 128;
         if constexpr (SC) { stepbuf[lane] = cur.osc1; stepbuf[64 + lane] = cur.psc1; }      // this step's scale windows → LDS (read back below, per half)
         typedef __attribute__((address_space(3))) const f32x4* lds_f32x4;
@@ -269,8 +289,13 @@ __device__ __forceinline__ void w4_epilogue(const ConvArgs& p_, const ACC& acc, 
                 const unsigned P = (L >> 2) + 16u * k;
                 const int ppix = pixb + (int)(P & 31u), pco = cob[b] + (int)(P >> 5) * 32;
                 // (pixels >= npix lie beyond the descriptor's num_records; a block beyond cout gets bit 31)
-                const unsigned off = (unsigned)((ppix - pix0) * p.cout * 4 + (pco >> 5) * 128 + half * 64) + j * 16u;
-                __builtin_amdgcn_raw_buffer_store_b128(piece[k], ry, (int)(pco < p.cout ? off : OOB), 0, 0);
+                unsigned off = (unsigned)((ppix - pix0) * p.cout * 4 + (pco >> 5) * 128 + half * 64) + j * 16u;
+                bool in = pco < p.cout;
+                if constexpr (SHUF) {
+                    off = (unsigned)((int)(sf.hib - hib0 + 2 * (int)(P & 31u)) * p.cout + ((P >> 5) ? sho[b][1] : sho[b][0]) + half * 64) + j * 16u;
+                    in = in && ppix < p.npix;
+                }
+                __builtin_amdgcn_raw_buffer_store_b128(piece[k], ry, (int)(in ? off : OOB), 0, 0);
             }
             stamp(10 + half);
         }
@@ -282,6 +307,7 @@ __device__ __forceinline__ void w4_epilogue(const ConvArgs& p_, const ACC& acc, 
                     const int ow = p.wo_shift >= 0 ? (pix & (p.wo - 1)) : pix % p.wo;
                     ok = ok && ow < cur.vw;
                 }
+                if constexpr (SHUF) ok = ok && shuf2_interior(p, sf, lane & 31);
                 gs1 = ok ? gs1 : 0.f; gs2 = ok ? gs2 : 0.f;
 #pragma unroll
                 for (int o = 1; o < 32; o <<= 1) { gs1 += __shfl_xor(gs1, o, 64); gs2 += __shfl_xor(gs2, o, 64); }
@@ -295,8 +321,8 @@ __device__ __forceinline__ void w4_epilogue(const ConvArgs& p_, const ACC& acc, 
     }
 }
 
-template <bool SC, bool RG>
-__global__ void __launch_bounds__(256, 1) conv_dma_w4_kernel(const ConvArgs p) {
+template <bool SC, bool RG, bool SHUF>
+__device__ __forceinline__ void conv_dma_w4_body(const ConvArgs& p) {
     using namespace w4;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -624,7 +650,7 @@ __global__ void __launch_bounds__(256, 1) conv_dma_w4_kernel(const ConvArgs p) {
         tile_coords(v, co0, pix0);
         mfma_drain();
         // (W4_STAMPS == 2: slots 7-12 = per tile: first request | per step, summed: arithmetic + encode | next step's requests | LDS round + stores 1 | 2 | GroupNorm fold)
-        w4_epilogue<SC, RG>(p, AccFile{acc}, co0, pix0, wc, wp, lane, xpose, smem + STAGES * STAGE + NW * XB + wave * PB,
+        w4_epilogue<SC, RG, SHUF>(p, AccFile{acc}, co0, pix0, wc, wp, lane, xpose, smem + STAGES * STAGE + NW * XB + wave * PB,
                           [&](int i) __attribute__((always_inline)) { if constexpr (W4_STAMPS == 2) ph_stamp(i); });
     };
 
@@ -693,20 +719,35 @@ __global__ void __launch_bounds__(256, 1) conv_dma_w4_kernel(const ConvArgs p) {
     }
 }
 
+#ifndef MNET_W4_SHUF_TU
+template <bool SC, bool RG>
+__global__ void __launch_bounds__(256, 1) conv_dma_w4_kernel(const ConvArgs p) { conv_dma_w4_body<SC, RG, false>(p); }
+#define W4_KERNEL(SC, RG) conv_dma_w4_kernel<SC, RG>
+#else
+// conv_dma_w4_shuf.hip: the builds with the MNET_CONV_ALGO_FLAG_SHUFFLE2 output mode (such a launch has no scale vectors and no residual: RG = it writes GroupNorm sums)
+template <bool SC, bool RG>
+__global__ void __launch_bounds__(256, 1) conv_dma_w4_shuf_kernel(const ConvArgs p) { static_assert(!SC, "SHUFFLE2: no scale vectors"); conv_dma_w4_body<SC, RG, true>(p); }
+#define W4_KERNEL(SC, RG) conv_dma_w4_shuf_kernel<SC, RG>
+#endif
+
 template <bool SC, bool RG>
 static int launch_w4(const ConvArgs& b, int grid, hipStream_t st) {
     static thread_local DeviceOnce attr_once;      // per instantiation, per thread, per device
     if (!attr_once.done()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_dma_w4_kernel<SC, RG>), hipFuncAttributeMaxDynamicSharedMemorySize, w4::LDS);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(W4_KERNEL(SC, RG)), hipFuncAttributeMaxDynamicSharedMemorySize, w4::LDS);
         if (e != hipSuccess) return mnet_fail(MNET_E_LAUNCH, "hipFuncSetAttribute(dma_w4): %s", hipGetErrorString(e));
         attr_once.mark();
     }
-    hipLaunchKernelGGL((conv_dma_w4_kernel<SC, RG>), dim3((unsigned)grid), dim3(w4::NW * 64), w4::LDS, st, b);
+    hipLaunchKernelGGL((W4_KERNEL(SC, RG)), dim3((unsigned)grid), dim3(w4::NW * 64), w4::LDS, st, b);
     MNET_LAUNCH_CHECK("conv_dma_w4_kernel");
     return MNET_OK;
 }
 
+#ifdef MNET_W4_SHUF_TU
+int launch_conv_dma_w4_shuf(const ConvArgs& a, hipStream_t st) {
+#else
 int launch_conv_dma_w4(const ConvArgs& a, hipStream_t st) {
+#endif
     ConvArgs b = a;
     auto log2_or_minus1 = [](int v) { return v > 0 && (v & (v - 1)) == 0 ? __builtin_ctz((unsigned)v) : -1; };
     b.howo_shift = log2_or_minus1(a.howo); b.wo_shift = log2_or_minus1(a.wo);
@@ -719,6 +760,11 @@ int launch_conv_dma_w4(const ConvArgs& a, hipStream_t st) {
     if (grid > lim && !a.one_tile_per_wg && !env_one_tile) grid = lim & ~7;
     // (a launch this tile is not built for never gets here: conv_resolve hands it to id 15)
     const bool sc = a.out_scale || a.post_scale, rg = a.res || a.gn_partial;
+#ifdef MNET_W4_SHUF_TU
+    if (sc || a.res) return mnet_fail(MNET_E_ARG, "conv: a MNET_CONV_ALGO_FLAG_SHUFFLE2 launch has no scale vectors and no residual");      // (conv_resolve refuses it first)
+    return rg ? launch_w4<false, true>(b, grid, st) : launch_w4<false, false>(b, grid, st);
+#else
     if (sc) return rg ? launch_w4<true, true>(b, grid, st) : launch_w4<true, false>(b, grid, st);
     return rg ? launch_w4<false, true>(b, grid, st) : launch_w4<false, false>(b, grid, st);
+#endif
 }

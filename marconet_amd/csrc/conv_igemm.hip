@@ -513,7 +513,8 @@ static int conv_prepare(const mnet_conv_desc* d, int32_t algo, ConvArgs& a) {
     static const int env_fetch_pad = [] { const char* e = getenv("MNET_MX_FETCH_PAD"); return e ? atoi(e) : 0; }();   // A/B knob, see ConvArgs
     a.mx_fetch_pad = env_fetch_pad;
     a.x1_center = (algo & MNET_CONV_ALGO_FLAG_X1_CENTER) ? 1 : 0;
-    algo &= ~(MNET_CONV_ALGO_FLAG_ONE_TILE | MNET_CONV_ALGO_FLAG_X1_CENTER);
+    a.shuffle2 = (algo & MNET_CONV_ALGO_FLAG_SHUFFLE2) ? 1 : 0;
+    algo &= ~MNET_CONV_ALGO_FLAGS;
     MNET_CHECK_ARG((algo >= 0 && algo <= 3) || (algo >= MNET_CONV_ALGO_DMA_CFG0 && algo < MNET_CONV_ALGO_DMA_CFG0 + 16) ||
                    (algo >= MNET_CONV_ALGO_STRIP_CFG0 && algo < MNET_CONV_ALGO_STRIP_CFG0 + 3) ||
                    (algo >= MNET_CONV_ALGO_DMA_CFG16 && algo < MNET_CONV_ALGO_DMA_CFG16 + 16), "conv: bad algo %d", algo);
@@ -567,6 +568,16 @@ static int conv_prepare(const mnet_conv_desc* d, int32_t algo, ConvArgs& a) {
     a.howo_shift = a.wo_shift = -1;      // "not a power of two" until an LDS-DMA launcher says otherwise (0 would read as a shift by 0)
     a.center_tap = (d->kh / 2) * d->kw + d->kw / 2;
     a.center_tpx = (d->kh / 2) * d->w + d->kw / 2;
+    if (a.shuffle2) {
+        // conv o bilinear x2 in polyphase form: cout = 4 C phase-major on the low-res map, y = [N,2H,2W,C].  The epilogues place whole 32-pixel fragments of one low-res
+        // row (W % 32 == 0) and the one-wave tile addresses a tile's hi-res window with 32-bit offsets.
+        MNET_CHECK_ARG(d->dtype == MNET_F16M && d->kh == 3 && d->kw == 3 && d->stride_h == 1 && d->stride_w == 1 && d->pad_h == 1 && d->pad_w == 1 && !d->x1,
+                       "conv: MNET_CONV_ALGO_FLAG_SHUFFLE2 needs an MNET_F16M 3x3 / stride 1 / pad 1 launch with one source");
+        MNET_CHECK_ARG(d->cout % 128 == 0 && d->h >= 4 && d->w >= 4 && d->w % 32 == 0, "conv: MNET_CONV_ALGO_FLAG_SHUFFLE2 needs cout = 4 C with C %% 32 == 0, H, W >= 4 and W %% 32 == 0");
+        MNET_CHECK_ARG(!d->residual && !d->out_scale && !d->post_scale && !d->valid_w && !d->in_scale,
+                       "conv: MNET_CONV_ALGO_FLAG_SHUFFLE2 takes no residual, no scale vectors and no valid_w");
+        MNET_CHECK_ARG((1024ll + 2ll * d->w + 2) * d->cout < 0x7fffffffLL, "conv: MNET_CONV_ALGO_FLAG_SHUFFLE2: map too wide");
+    }
     if (a.x1_center) {
         MNET_CHECK_ARG(d->x1 && d->c1 > 0 && (d->kh & 1) && (d->kw & 1) && d->stride_h == 1 && d->stride_w == 1 &&
                        d->pad_h == d->kh / 2 && d->pad_w == d->kw / 2 && d->dtype != MNET_F32,
@@ -674,6 +685,13 @@ static int conv_dma_pick(const ConvArgs& a) {
     return big ? 5 : 3;
 }
 
+// LDS-DMA id AUTO uses for a MNET_CONV_ALGO_FLAG_SHUFFLE2 launch (cout = 4 C >= 128).  Whether a layer can take the polyphase form must not depend on the batch, so
+// every id named here — and the id a hand-over leads to — has a build with the mode (conv_dma_launcher): the dominant tile for the big launches, the 128x128 tile
+// for everything else (same k order, same MFMA sequence per output: the same bytes).
+static int conv_shuffle_pick(const ConvArgs& a) {
+    return a.cout >= 256 && a.npix >= 256 * 256 ? knobs().mx_256 : 10;
+}
+
 // tile configuration the strip kernel would use for this launch (0: 256x256, 16 waves; 1: 64x512, 8 waves), or -1 when
 // the launch is not eligible: 3x3 / stride 1 / pad 1, one source tensor, whole-row (or whole-segment) tiles that never
 // straddle an image, and everything conv_dma_eligible already requires
@@ -729,8 +747,13 @@ static int dma_algo(int id) { return id < 16 ? MNET_CONV_ALGO_DMA_CFG0 + id : MN
 // the kernel `algo` asks for on this launch, before the hand-overs: MNET_CONV_ALGO_REG_STAGED, MNET_CONV_ALGO_SKINNY,
 // MNET_CONV_ALGO_DMA_CFG0 / 16 + id or MNET_CONV_ALGO_STRIP_CFG0 + id (negative: error)
 static int conv_request(const mnet_conv_desc* d, int32_t algo, const ConvArgs& a) {
-    algo &= ~(MNET_CONV_ALGO_FLAG_ONE_TILE | MNET_CONV_ALGO_FLAG_X1_CENTER);
+    algo &= ~MNET_CONV_ALGO_FLAGS;
     const bool dma_ok = conv_dma_eligible(a, d->dtype);
+    if (a.shuffle2) {           // only builds of the fp16+8 LDS-DMA tiles store in the pixel-shuffle mode (conv_dma_launcher knows which)
+        if (!dma_ok || algo == MNET_CONV_ALGO_REG_STAGED || algo == MNET_CONV_ALGO_SKINNY || (algo >= MNET_CONV_ALGO_STRIP_CFG0 && algo < MNET_CONV_ALGO_DMA_CFG16))
+            return mnet_fail(MNET_E_ARG, "conv: MNET_CONV_ALGO_FLAG_SHUFFLE2 needs a launch the LDS-DMA kernel takes");
+        return algo >= MNET_CONV_ALGO_DMA_CFG0 ? algo : dma_algo(conv_shuffle_pick(a));
+    }
     if (a.x1_center) {          // only the LDS-DMA kernels walk the second source at one tap
         if (!dma_ok || algo == MNET_CONV_ALGO_REG_STAGED || algo == MNET_CONV_ALGO_SKINNY || (algo >= MNET_CONV_ALGO_STRIP_CFG0 && algo < MNET_CONV_ALGO_DMA_CFG16))
             return mnet_fail(MNET_E_ARG, "conv: MNET_CONV_ALGO_FLAG_X1_CENTER needs a launch the LDS-DMA kernel takes");

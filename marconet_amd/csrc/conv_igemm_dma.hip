@@ -53,8 +53,14 @@
 // SGN (with SWP): the software-pipelined tile WITH the GroupNorm-sum block in its epilogue.  Only conv_dma_swp_gn.hip instantiates it — a translation unit of its own,
 //     compiled with `-mllvm -greedy-reverse-local-assignment=1`: with hipcc's default assignment order that block moves a spill of the slab loop onto its hot path (three
 //     formulations tried), with the reverse order the tile is clean (31 spilled registers, none hot: tools/isa_hot_scratch.py).  The flag is kept away from every other tile.
+// DBG = DMA_SHUF (-1): not a diagnostic — the production tile built with the MNET_CONV_ALGO_FLAG_SHUFFLE2 output mode of the fp16+8 epilogue (conv_dma_common.h).  A value
+// of this parameter, not a parameter of its own: the names of the production instantiations (DBG = 0), which tools and recorded profiles key on, stay what they were, and
+// their code does not know the mode.
+constexpr int DMA_SHUF = -1;
 template <int BC, int BP, int WC, int WP, int STAGES, int MF = 16, int DBG = 0, bool X3 = false, bool SPREAD = false, bool PIPE = false, bool MX = false, bool SWP = false, bool SGN = false>
 __global__ void __launch_bounds__(WC * WP * 64, WC * WP / 4) conv_dma_kernel(const ConvArgs p) {
+    constexpr bool SHUF = DBG == DMA_SHUF;
+    static_assert(!SHUF || MX, "SHUF: fp16+8 tiles only");
     constexpr int NW = WC * WP;                          // waves per workgroup (8 or 16)
     constexpr int FC = BC / WC / 16, FP = BP / WP / 16;
     constexpr int NWI = NW;                              // waves that issue DMA: all of them (an asymmetric form — the older wave of every SIMD issuing all
@@ -66,8 +72,8 @@ __global__ void __launch_bounds__(WC * WP * 64, WC * WP / 4) conv_dma_kernel(con
     static_assert(NW == 8 || NW == 16, "8 or 16 waves");
     static_assert(!MX || (X3 && MF == 32), "MX: 4-byte storage, 32x32 MFMAs");
     static_assert(!SGN || SWP, "SGN: software-pipelined tiles only");
-    static_assert(!SWP || (MX && NW == 8 && STAGES == 2 && (DBG == 0 || DBG == 6) && (FC / 2) * (FP / 2) <= 16 && NDMA <= 16), "SWP: fp16+8, 2 stages, <= 16 accumulator blocks per wave");
-    static_assert(!SPREAD || (STAGES == 2 && (MF == 16 || X3) && (DBG == 0 || DBG == 6)), "SPREAD: production 2-stage tiles only");
+    static_assert(!SWP || (MX && NW == 8 && STAGES == 2 && (DBG == 0 || DBG == 6 || SHUF) && (FC / 2) * (FP / 2) <= 16 && NDMA <= 16), "SWP: fp16+8, 2 stages, <= 16 accumulator blocks per wave");
+    static_assert(!SPREAD || (STAGES == 2 && (MF == 16 || X3) && (DBG == 0 || DBG == 6 || SHUF)), "SPREAD: production 2-stage tiles only");
     static_assert(WJ >= 1 && XJ >= 1 && WJ * 8 * NWI == BC && XJ * 8 * NWI == BP, "tile / wave-count mismatch");
     static_assert(STAGES == 2 || ((STAGES == 3 || STAGES == 4) && NDMA >= 4 && NDMA <= 6), "vmcnt immediates below cover 4-6 DMAs per slab, up to 3 slabs in flight");
     static_assert((BC / WC) % 64 == 0 && (BP / WP) % 32 == 0, "the channel permutation works on 64-channel blocks of a wave tile");
@@ -736,7 +742,7 @@ __global__ void __launch_bounds__(WC * WP * 64, WC * WP / 4) conv_dma_kernel(con
             if (c_kt == nk) {                                            // slab s-1 closed its tile: epilogue, then the next tile's scales and a clean accumulator
                 int co0, pix0;
                 tile_coords(c_v, co0, pix0);
-                dma_epilogue_mx<BC, BP, WC, WP, FC, FP, (XB == 1024 ? 16 : 64), SWP_GN>(p, acc32, co0, pix0, wc, wp, lane, xpose);
+                dma_epilogue_mx<BC, BP, WC, WP, FC, FP, (XB == 1024 ? 16 : 64), SWP_GN, SHUF>(p, acc32, co0, pix0, wc, wp, lane, xpose);
                 c_kt = 0; c_v += G;
                 if (p.tilesC > 1) load_scales(c_v);                      // (one channel tile: every tile has the same scales)
                 zero_acc();
@@ -753,7 +759,7 @@ __global__ void __launch_bounds__(WC * WP * 64, WC * WP / 4) conv_dma_kernel(con
         {
             int co0, pix0;
             tile_coords(c_v, co0, pix0);
-            dma_epilogue_mx<BC, BP, WC, WP, FC, FP, (XB == 1024 ? 16 : 64), SWP_GN>(p, acc32, co0, pix0, wc, wp, lane, xpose);
+            dma_epilogue_mx<BC, BP, WC, WP, FC, FP, (XB == 1024 ? 16 : 64), SWP_GN, SHUF>(p, acc32, co0, pix0, wc, wp, lane, xpose);
         }
         if constexpr (DBG == 6) {       // DIAGNOSTIC: phase sums of this wave over the first bytes of the output (32 bytes per wave)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -855,7 +861,7 @@ __global__ void __launch_bounds__(WC * WP * 64, WC * WP / 4) conv_dma_kernel(con
 
         int co0, pix0;
         tile_coords(c_v, co0, pix0);
-        if constexpr (MX) dma_epilogue_mx<BC, BP, WC, WP, FC, FP, (XB == 1024 ? 16 : 64)>(p, acc32, co0, pix0, wc, wp, lane, xpose);
+        if constexpr (MX) dma_epilogue_mx<BC, BP, WC, WP, FC, FP, (XB == 1024 ? 16 : 64), true, SHUF>(p, acc32, co0, pix0, wc, wp, lane, xpose);
         else dma_epilogue<BC, BP, WC, WP, MF, DBG, FC, FP, X3>(p, acc, acc32, co0, pix0, wc, wp, lane);
         drain = true;
 
@@ -911,8 +917,11 @@ static int launch_dma_cfg(const ConvArgs& a, hipStream_t st) {
 #ifdef MNET_DMA_SWP_GN_TU
 // conv_dma_swp_gn.hip: this translation unit holds ONE instantiation — the software-pipelined 256x256 fp16+8 tile with the GroupNorm-sum block
 int launch_dma_swp_gn(const ConvArgs& a, hipStream_t st) { return launch_dma_cfg<256, 256, 2, 4, 2, 32, 0, true, false, false, true, true, true>(a, st); }
+// ... and the same build with the SHUFFLE2 output mode (conv_final.3's polyphase launch)
+int launch_dma_swp_gn_shuf(const ConvArgs& a, hipStream_t st) { return launch_dma_cfg<256, 256, 2, 4, 2, 32, DMA_SHUF, true, false, false, true, true, true>(a, st); }
 #else
 int launch_dma_swp_gn(const ConvArgs& a, hipStream_t st);      // conv_dma_swp_gn.hip
+int launch_dma_swp_gn_shuf(const ConvArgs& a, hipStream_t st);
 
 // tile configurations (BC x BP, waves, LDS stages, MFMA shape); MNET_CONV_ALGO_DMA_CFG0 + id selects one explicitly.
 // Production ids 0-6 all use v_mfma_f32_16x16x32_f16 and walk k in the same order (64-channel slice outer, tap inner), so a
@@ -931,6 +940,17 @@ static DmaLaunchFn no_form(const char* fmt, int id) {
 
 DmaLaunchFn conv_dma_launcher(int id, const ConvArgs& a) {
     static const bool allow_diag = [] { const char* e = getenv("MNET_ALLOW_DIAGNOSTIC_KERNELS"); return e && atoi(e) != 0; }();
+    if (a.shuffle2) {   // MNET_CONV_ALGO_FLAG_SHUFFLE2: the builds that carry the output mode — every id conv_shuffle_pick (conv_igemm.hip) can name, at any batch
+        if (a.split != 2) return no_form("conv: MNET_CONV_ALGO_FLAG_SHUFFLE2 needs fp16+8 storage (LDS-DMA id %d)", id);
+        switch (id) {
+            case 10: return launch_dma_cfg<128, 128, 2, 4, 4, 32, DMA_SHUF, true, false, false, true>;
+            case 15:
+                if (a.gn_partial) return launch_dma_swp_gn_shuf;
+                return launch_dma_cfg<256, 256, 2, 4, 2, 32, DMA_SHUF, true, false, false, true, true>;
+            case 16: return launch_conv_dma_w4_shuf;
+            default: return no_form("conv: LDS-DMA tile configuration %d has no build with the MNET_CONV_ALGO_FLAG_SHUFFLE2 output mode", id);
+        }
+    }
     if (a.split == 2) { // fp16+8 (MNET_F16M) instantiations: the same tile shapes on 32x32 MFMAs
         switch (id) {
             case 0: return launch_dma_cfg<256, 256, 4, 4, 2, 32, 0, true, true, false, true>;

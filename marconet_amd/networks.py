@@ -15,15 +15,17 @@ import os
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import _lib, ops
 from .glyphs import GlyphTables
-from .packing import (PRECISIONS, SPLIT_DTYPE, PackCache, is_split, default_precision, equal_linear_scale, pack_conv_weight,
-                      pack_linear_weight, pack_vec, pack_wsq, padded_cout, rgb_pad, torch_dtype)
+from .packing import (MX_DTYPE, PRECISIONS, SPLIT_DTYPE, PackCache, is_split, default_precision, equal_linear_scale, pack_conv_weight,
+                      pack_linear_weight, pack_polyphase_conv_weight, pack_vec, pack_wsq, padded_cout, rgb_pad, torch_dtype)
 from .resnet import resnet45stride as resnet45
 from .textvit_arch import TextViT as TextEncoder
 
 _STYLE_NORM = not bool(int(os.environ.get("MNET_NO_STYLE_NORM", "0")))     # A/B knob (tests): style rows normalised by a power of two
 _FOLD_SKIP = not bool(int(os.environ.get("MNET_NO_FOLD_SKIP", "0")))       # A/B knob: ResTextBlockV2's 1x1 skip conv as extra K of its conv2
+_NO_POLYPHASE = os.environ.get("MNET_NO_POLYPHASE", "0") == "1"             # A/B knob: the SR up-convs keep up-sample + conv (no polyphase form)
+_POLYPHASE_CONV_UP = os.environ.get("MNET_POLYPHASE_CONV_UP", "0") == "1"    # A/B knob: conv_up.1 takes the polyphase form too (default: conv_final.3 only)
 _FUSE_IMG_CONVERT = os.environ.get("MNET_NO_FUSE_IMG_CONVERT", "0") != "1"   # image-only levels: the f16 conversion rides in the up-sample's store (A/B knob)
 _FUSE_CONV1_MOD = os.environ.get("MNET_NO_FUSE_CONV1_MOD", "0") != "1"      # conv1's style multiply in the SelectText gather (A/B knob)
 RGB_PAD = 8      # 3-channel tensors are carried with 8 channels (one 16-byte fp16 chunk); 32 in the split-half mode (rgb_pad)
@@ -529,8 +531,23 @@ class TSPSRNet(nn.Module, _Precision):
                      "conv_64_scale", "conv_64_shift"):
             sn(name + ".0", getattr(self, name)[0])
             sn(name + ".2", getattr(self, name)[2])
+        def poly(name, m, algo=0):
+            # conv ∘ bilinear×2 in polyphase form (fp16+8 storage): the four phases' combined weights beside the ordinary pack, which the ring strips
+            # and the two-launch fallback keep using; the bias once per phase.  `algo`: the tile the main launch is pinned to (0: the planner's choice)
+            if dtype != MX_DTYPE or m.weight_orig.shape[0] % 32 or m.weight_orig.shape[1] % 32:
+                return
+            wf = pack_conv_weight(m.weight_orig.detach(), torch.float32, cin_mult=1, cout_mult=1, sn=(m.weight_u, m.weight_v))      # [O][3][3][I], folded
+            pk[name]["poly"] = dict(w=pack_polyphase_conv_weight(wf.reshape(m.weight_orig.shape[0], 3, 3, m.weight_orig.shape[1]), dtype),
+                                    b=pk[name]["b"].repeat(4).contiguous(), algo=algo)
+
         sn("conv_up.1", self.conv_up[1]); res("conv_up.3", self.conv_up[3]); sn("conv_up.4", self.conv_up[4])
         sn("conv_final.0", self.conv_final[0]); sn("conv_final.3", self.conv_final[3])
+        # conv_up.1 (256 → 256 on a 64-row map) keeps up-sample + conv: its top / bottom ring strips are 8 of 64 hi-res rows — an eighth of the conv again — which
+        # cancels the saved up-sample pass (same-box breakdown); MNET_POLYPHASE_CONV_UP=1 switches it on for an A/B
+        if _POLYPHASE_CONV_UP:
+            poly("conv_up.1", self.conv_up[1])
+        # conv_final.3 in polyphase form is a 128 → 256 conv: the 8-wave software-pipelined 256x256 tile (its build with the GroupNorm-sum block)
+        poly("conv_final.3", self.conv_final[3], algo=_lib.ALGO_DMA_CFG0 + 15)
         res("conv_final.5", self.conv_final[5]); sn("conv_final.6", self.conv_final[6], cout_mult=rgb_pad(dtype))
         m6 = self.conv_final[6]                       # the same layer for the dedicated 64 → 3 kernel: [3][3][3][64], bias [3]
         rgb_dt = torch.float32 if is_split(dtype) else dtype          # (the split-half mode runs this 64 → 3 layer in fp32)
@@ -560,6 +577,19 @@ class TSPSRNet(nn.Module, _Precision):
             return y, ops.groupnorm_affine_from_partial(part, n, h, w, L["cout"], *pk[norm], 1e-6, valid_w)
         y = self._c(pk, name, x, act, x1=x1, valid_w=valid_w)
         return y, ops.groupnorm_affine(y, *pk[norm], 1e-6, valid_w)
+
+    def _upconv_gn(self, pk, name, x, norm, act=ops.ACT_NONE):
+        """conv ``name`` on bilinear×2 of ``x``, feeding GroupNorm ``norm`` → (y, (scale, shift)).  fp16+8 storage: the polyphase form (one conv on the
+        low-res map, stored pixel-shuffled, + the ring from the two-launch form on thin strips: ops.upconv3x3_polyphase) — the 4×-sized up-sampled
+        tensor is never written.  Taken when the planner accepts the main launch, which depends on the map shape and the storage only, never on the
+        batch; MNET_NO_POLYPHASE=1 (A/B) and every other storage keep up-sample + conv."""
+        L = pk[name]
+        P = L.get("poly")
+        if P is not None and not _NO_POLYPHASE and ops.polyphase_plan(x, L["cout"], act, algo=P["algo"]) >= 0:
+            n, h, w, _ = x.shape
+            y, part, ring = ops.upconv3x3_polyphase(x, P["w"], P["b"], L["w"], L["b"], L["cout"], act, algo=P["algo"])
+            return y, ops.groupnorm_affine_from_partial_ring(part, ring, n, 2 * h, 2 * w, L["cout"], *pk[norm], 1e-6)
+        return self._conv_gn(pk, name, ops.upsample2x(x), norm, act)
 
     def _two(self, pk, name, x, x1=None, valid_w=None):
         """Sequential(SNconv, LeakyReLU(0.2), SNconv)."""
@@ -667,7 +697,7 @@ class TSPSRNet(nn.Module, _Precision):
                 s32 = self._prior_transform(pk, "32", s32, p32, tab32)                           # :425-449
                 del p32
 
-            h, aff = self._conv_gn(pk, "conv_up.1", ops.upsample2x(s32), "conv_up.3.norm1", ops.ACT_LRELU)   # conv_up :359-365
+            h, aff = self._upconv_gn(pk, "conv_up.1", s32, "conv_up.3.norm1", ops.ACT_LRELU)   # conv_up :359-365
             del s32
             h = self._res_block(pk, "conv_up.3", h, norm1_affine=aff)
             s64 = self._c(pk, "conv_up.4", h)
@@ -679,7 +709,7 @@ class TSPSRNet(nn.Module, _Precision):
 
             h = self._c(pk, "conv_final.0", s64, ops.ACT_LRELU)                                  # conv_final :367-376
             del s64
-            h, aff = self._conv_gn(pk, "conv_final.3", ops.upsample2x(h), "conv_final.5.norm1", ops.ACT_LRELU)
+            h, aff = self._upconv_gn(pk, "conv_final.3", h, "conv_final.5.norm1", ops.ACT_LRELU)
             h = self._res_block(pk, "conv_final.5", h, norm1_affine=aff)
             if h.shape[3] == 64:                      # conv_final.6 + tanh through the dedicated 3-output kernel
                 wr, br = pk["conv_final.6.rgb"]

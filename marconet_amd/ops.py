@@ -19,6 +19,7 @@ __all__ = ["conv2d", "linear", "nchw_to_nhwc", "nhwc_to_nchw", "upsample2x", "af
            "adain_crop_concat", "adain_crop_concat_gn", "glyph_scatter_affine", "layernorm", "token_mix", "attention", "pixelnorm",
            "embed_gather", "demod", "argmax_rows", "convert", "fused_bias_act", "sr_postprocess", "lq_from_u8", "panel_u8", "conv3x3_rgb", "torgb", "stats",
            "pack_weights", "pack_wsq", "gather_rows", "style_rows", "nonfinite_flag", "gn_partial_buffer", "can_emit_gn_partial", "groupnorm_affine_from_partial",
+           "polyphase_plan", "upconv3x3_polyphase", "polyphase_ring_fix", "groupnorm_affine_from_partial_ring",
            "ACT_NONE", "ACT_RELU", "ACT_LRELU", "ACT_LRELU_SQRT2", "ACT_TANH", "ACT_GELU", "ACT_SIGMOID"]
 
 
@@ -168,12 +169,13 @@ def _conv_desc(x0, x1, cout, kh, kw, stride, pad, wgt, y, in_scale=None, in_shif
 @_plumbing
 def conv2d(x0, wgt, cout, kh=1, kw=1, stride=(1, 1), pad=(0, 0), x1=None, in_scale=None, in_shift=None,
            in_swish=False, valid_w=None, out_scale=None, bias=None, residual=None, res_mod=0, act=ACT_NONE,
-           post_scale=None, out=None, algo=0, splitk=0, x1_center=False, gn_partial=None):
+           post_scale=None, out=None, algo=0, splitk=0, x1_center=False, gn_partial=None, shuffle2=False):
     """mnet_conv2d_nhwc(_ex).  x0 [N,H,W,C0] (+ optional x1 [N,H,W,C1]); wgt packed [cout,kh,kw,C0+C1] same dtype.
     ``splitk`` > 0: mnet_conv2d_splitk with that many K-slices (fp32 filter == stride convs over <= 512 output pixels).
     ``x1_center``: x1 enters through the filter's centre tap only (MNET_CONV_ALGO_FLAG_X1_CENTER: a 1x1 skip conv as extra K).
     ``gn_partial``: fp32 [n*ho*wo/32, cout/32, 2] buffer (``gn_partial_buffer``) the epilogue fills with the GroupNorm partial sums of the output
-    (fp16+8 launches on the LDS-DMA / strip kernels only: MarconetHipError otherwise, nothing enqueued)."""
+    (fp16+8 launches on the LDS-DMA / strip kernels only: MarconetHipError otherwise, nothing enqueued).
+    ``shuffle2``: MNET_CONV_ALGO_FLAG_SHUFFLE2 — ``cout`` = 4 C phase-major and the output is the [N,2H,2W,C] tensor (see ``upconv3x3_polyphase``)."""
     lib = _lib.load()
     _need_cuda(x0, x1, wgt, in_scale, in_shift, valid_w, out_scale, bias, residual, post_scale, out)
     n, h, w, c0 = x0.shape
@@ -185,10 +187,13 @@ def conv2d(x0, wgt, cout, kh=1, kw=1, stride=(1, 1), pad=(0, 0), x1=None, in_sca
         raise RuntimeError("conv2d: weight dtype/shape mismatch (%s %s vs cout=%d k=%dx%d cin=%d)"
                            % (wgt.dtype, tuple(wgt.shape), cout, kh, kw, c0 + c1))
     ho, wo = _out_size(h, w, kh, kw, stride, pad)
+    oshape = (n, 2 * ho, 2 * wo, cout // 4) if shuffle2 else (n, ho, wo, cout)
+    if shuffle2:
+        algo |= _lib.ALGO_FLAG_SHUFFLE2
     if out is None:
-        out = new_tensor((n, ho, wo, cout), x0.dtype, x0.device)
-    elif tuple(out.shape) != (n, ho, wo, cout) or out.dtype != x0.dtype:
-        raise RuntimeError("conv2d: out is %s %s, expected %s %s" % (tuple(out.shape), out.dtype, (n, ho, wo, cout), x0.dtype))
+        out = new_tensor(oshape, x0.dtype, x0.device)
+    elif tuple(out.shape) != oshape or out.dtype != x0.dtype:
+        raise RuntimeError("conv2d: out is %s %s, expected %s %s" % (tuple(out.shape), out.dtype, oshape, x0.dtype))
     if gn_partial is not None:
         _need_cuda(gn_partial)
         if gn_partial.dtype != torch.float32 or gn_partial.numel() != (n * ho * wo // 32) * (cout // 32) * 2:
@@ -340,6 +345,64 @@ def conv_plan(x0, cout, kh=1, kw=1, stride=(1, 1), pad=(0, 0), x1=None, act=ACT_
         if k >= 0:
             _PLAN_CACHE[key] = k
     return k
+
+
+def polyphase_plan(x, c, act=ACT_NONE, gn_partial=True, algo=0):
+    """the planner's answer for the main launch of ``upconv3x3_polyphase(x, …)`` with ``c`` output channels (negative: refused — the caller keeps
+    the two-launch form).  It depends on the per-image map shape, the channel counts and the storage type, never on the batch."""
+    if x.dtype != MX_DTYPE:
+        return -1
+    return conv_plan(x, 4 * c, 3, 3, (1, 1), (1, 1), act=act, gn_partial=gn_partial, algo=algo | _lib.ALGO_FLAG_SHUFFLE2)
+
+
+@_plumbing
+def polyphase_ring_fix(top, bottom, left, right, y):
+    """mnet_polyphase_ring_fix: hi-res rows / columns {0, 1, last two} of ``y`` [N,2H,2W,C] from the strips' two-launch results (top / bottom [N,4,2W,C],
+    left / right [N,2H,4,C]) → fp64 [N, C/32, 2] sums of the stored ring values"""
+    lib = _lib.load()
+    _need_cuda(top, bottom, left, right, y)
+    n, h2, w2, c = y.shape
+    if tuple(top.shape) != (n, 4, w2, c) or tuple(bottom.shape) != (n, 4, w2, c) or tuple(left.shape) != (n, h2, 4, c) or tuple(right.shape) != (n, h2, 4, c):
+        raise RuntimeError("polyphase_ring_fix: strips %s %s %s %s do not fit y %s" % (tuple(top.shape), tuple(bottom.shape), tuple(left.shape), tuple(right.shape), tuple(y.shape)))
+    sums = torch.empty((n, c // 32, 2), dtype=torch.float64, device=y.device)
+    # (bytes: half of every strip is read, as much of y written)
+    stats.tail("polyphase_ring", (top, left, top, left), lambda: _lib.check(lib.mnet_polyphase_ring_fix(_p(top), _p(bottom), _p(left), _p(right), _p(y), _dt(y), n, h2, w2, c,
+                                                                                                      _p(sums), _stream()), "mnet_polyphase_ring_fix"))
+    return sums
+
+
+def groupnorm_affine_from_partial_ring(partial, ring_sums, n, h, w, c, gamma, beta, eps=1e-6):
+    """``groupnorm_affine_from_partial`` for a polyphase conv's output [n,h,w,c] (hi-res): masked partial sums + the ring's sums"""
+    lib = _lib.load()
+    _need_cuda(partial, ring_sums, gamma, beta)
+    scale = torch.empty((n, c), dtype=torch.float32, device=partial.device)
+    shift = torch.empty((n, c), dtype=torch.float32, device=partial.device)
+    _lib.check(lib.mnet_groupnorm_affine_from_partial_ring(_p(partial), _p(ring_sums), n, h, w, c, _p(gamma), _p(beta), eps, _p(scale), _p(shift), _stream()),
+               "mnet_groupnorm_affine_from_partial_ring")
+    return scale, shift
+
+
+@_plumbing
+def _strip_pair(x, dim):
+    """the first two and the last two rows (dim 1) / columns (dim 2) of NHWC ``x``, stacked along the batch: [2N,2,W,C] / [2N,H,2,C]"""
+    r = _raw(x)
+    k = r.shape[dim]
+    out = torch.cat([r.narrow(dim, 0, 2), r.narrow(dim, k - 2, 2)], dim=0)
+    return tag(out.view(x.dtype)) if is_split(x.dtype) else out
+
+
+def upconv3x3_polyphase(x, wgt_poly, bias_poly, wgt, bias, c, act=ACT_NONE, algo=0, out=None):
+    """conv3x3(bilinear_x2(x)) + bias + act without the up-sampled tensor: ONE conv on the low-res map with the four phases' combined weights
+    (``wgt_poly`` [4c,3,3,cin], ``bias_poly`` [4c]: packing.polyphase_conv_weight) stored pixel-shuffled, then the hi-res ring — rows and columns
+    {0, 1, last two}, where clamping the up-sample differs from zero-padding its phases — from the two-launch form on four thin strips with the
+    ordinary ``wgt`` / ``bias``.  → (y [N,2H,2W,c], partial, ring_sums) for ``groupnorm_affine_from_partial_ring``.  The caller has asked
+    ``polyphase_plan``; ``algo`` pins the main launch's tile."""
+    n, h, w, _ = x.shape
+    part = gn_partial_buffer(n, h, w, 4 * c, x.device)
+    y = conv2d(x, wgt_poly, 4 * c, 3, 3, (1, 1), (1, 1), bias=bias_poly, act=act, gn_partial=part, algo=algo, shuffle2=True, out=out)
+    tb = conv2d(upsample2x(_strip_pair(x, 1)), wgt, c, 3, 3, (1, 1), (1, 1), bias=bias, act=act)        # [2N,4,2W,c]
+    lr = conv2d(upsample2x(_strip_pair(x, 2)), wgt, c, 3, 3, (1, 1), (1, 1), bias=bias, act=act)        # [2N,2H,4,c]
+    return y, part, polyphase_ring_fix(tb[:n], tb[n:], lr[:n], lr[n:], y)
 
 
 def plan_is_lds_dma(k):

@@ -215,6 +215,44 @@ def pack_conv_weight(w, dtype, cin_mult=8, cout_mult=4, scale=1.0, sn=None):
     return w.permute(0, 2, 3, 1).contiguous().to(dtype)
 
 
+# conv3x3 ∘ bilinear×2 (align_corners=False) as four 3x3 convs on the low-res map, one per output phase: with up[2i] = ¼x[i-1] + ¾x[i] and
+# up[2i+1] = ¾x[i] + ¼x[i+1], hi-res tap r of phase p reads low-res tap a with weight POLYPHASE_TAPS[p][a][r] (rows: low-res tap, columns: hi-res tap)
+POLYPHASE_TAPS = (((0.75, 0.25, 0.0), (0.25, 0.75, 0.75), (0.0, 0.0, 0.25)),
+                  ((0.25, 0.0, 0.0), (0.75, 0.75, 0.25), (0.0, 0.25, 0.75)))
+
+
+def polyphase_weight(w):
+    """w [O,KH=3,KW=3,I] (any float dtype) → fp64 [4·O,3,3,I], phase-major (row (2·py + px)·O + o): the weights of the conv on the LOW-res map whose
+    pixel-shuffled output is conv3x3(bilinear_x2(x); w) — exactly, away from hi-res rows / columns {0, 1, last two} (there the up-sample clamps where
+    this form zero-pads: the ring the caller takes from the two-launch form).  W'[py,px] = A[py] ⊗ A[px] ∘ W, combined in fp64 with elementwise
+    operations only."""
+    o, kh, kw, i = w.shape
+    if (kh, kw) != (3, 3):
+        raise ValueError("polyphase_weight: 3x3 filters only (got %dx%d)" % (kh, kw))
+    w64 = w.detach().to("cpu", torch.float64)
+    out = torch.zeros((4, o, 3, 3, i), dtype=torch.float64)
+    for py in range(2):
+        for px in range(2):
+            for a in range(3):
+                for r in range(3):
+                    ca = POLYPHASE_TAPS[py][a][r]
+                    if ca == 0.0:
+                        continue
+                    for b in range(3):
+                        for q in range(3):
+                            cb = POLYPHASE_TAPS[px][b][q]
+                            if cb != 0.0:
+                                out[2 * py + px, :, a, b, :] += (ca * cb) * w64[:, r, q, :]
+    return out.reshape(4 * o, 3, 3, i)
+
+
+def pack_polyphase_conv_weight(w_folded, dtype):
+    """``w_folded`` fp32 [O,3,3,I] (spectral norm already folded: pack_conv_weight(…, torch.float32, cin_mult=1, cout_mult=1, sn=…)) → the packed
+    [4·O,3,3,I] weights of the polyphase form in ``dtype`` (O and I whole 32-channel blocks)"""
+    wp = polyphase_weight(w_folded).to(torch.float32).permute(0, 3, 1, 2).contiguous().to(w_folded.device)
+    return pack_conv_weight(wp, dtype)
+
+
 def mx_weight_rows(cout_pad, kh, kw, cin_pad):
     """rows of the [rows, kh, kw, cin_pad] tensor that holds packed fp16+8 conv weights: cout_pad weight rows + the rows that
     carry the cout_pad per-channel scale bytes right behind them (include/marconet_hip.h)"""
