@@ -3,6 +3,7 @@
 (preview | box marks | super-resolved strip | structure priors — the file test_sr.py:232 writes, under the same name).
 
     python examples/restore_strips.py -i <strips dir> -o <out dir> [-m] [--precision fp16x2] [--batch 64] [--device-prep | --device-panel]
+                                      [--calibrate [--calibrate-apply]]
 
 Same flags as the script (-i / -o / -m, test_sr.py:236-241).  What differs, and why:
   * the YOLO character detector and the modelscope OCR (test_sr.py:55-56,86-96) are not part of this build (SURVEY.md §8f NEXT-4).  With
@@ -15,6 +16,10 @@ Same flags as the script (-i / -o / -m, test_sr.py:236-241).  What differs, and 
     for the whole batch (MarconetPipeline.restore_images) instead of per strip in host numpy — the same panels, byte for byte;
   * ``--device-panel`` (opt-in, implies ``--device-prep``): the panel itself (test_sr.py:203-232) is composed on the GPU too
     (MarconetPipeline.restore_panels: one launch and one device→host copy per batch) — the same files; only PNG decode / encode stay on the host.
+  * ``--calibrate`` (opt-in; the first thing to run on real checkpoints): before anything is restored, the first batch's first 8 strips run in the chosen
+    mode and in the fp16x3 reference mode (fp32 for ``--precision fp16x3``) on the device and the report of ``MarconetPipeline.calibrate`` is printed — is the
+    mode inside half the 1e-3 parity bar on THESE weights, and at which stage does the deviation enter.  A failed check ends the program with status 2;
+    with ``--calibrate-apply`` the pipeline falls back to the reference mode instead and goes on.
 Needs the GPU (there is no CPU path in this package)."""
 import argparse
 import os
@@ -103,6 +108,19 @@ def device_panels(pipe, paths, names, manual, save_path, max_glyphs=16):
             print("Restoring %s. Using %s text: %s -> %s" % (name, "given" if manual else "predicted", s["text"], out))
 
 
+def calibrate_on(pipe, strips, dev, reference, apply):
+    """MarconetPipeline.calibrate on the strips of the first batch (the batch layout of MarconetPipeline.restore_strips) → the report, or None when the
+    batch holds no strip with a character of the alphabet"""
+    n_cls = pipe.gan.TextGenerator.class_num
+    keep = [s for s in strips if s is not None and s["labels"].numel() > 0 and int(s["labels"].min()) >= 0 and int(s["labels"].max()) < n_cls]
+    if not keep:
+        return None
+    locs = torch.zeros((len(keep), 2 * max(int(s["labels"].shape[0]) for s in keep)), dtype=torch.float32)
+    for k, s in enumerate(keep):
+        locs[k, :s["locs"].shape[1]] = s["locs"][0]
+    return pipe.calibrate(torch.cat([s["lq"] for s in keep]).to(dev), [s["labels"] for s in keep], locs, reference=reference, apply=apply)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("-i", "--test_path", type=str, default="./Testsets/LQs")
@@ -112,6 +130,8 @@ def main():
     ap.add_argument("--batch", type=int, default=64, help="strips per call")
     ap.add_argument("--device-prep", action="store_true", help="resize / normalise the strips on the GPU (MarconetPipeline.restore_images)")
     ap.add_argument("--device-panel", action="store_true", help="also compose the saved panel on the GPU (MarconetPipeline.restore_panels); implies --device-prep")
+    ap.add_argument("--calibrate", action="store_true", help="check the precision mode against a more accurate one on the first batch (MarconetPipeline.calibrate) and exit with status 2 if it fails")
+    ap.add_argument("--calibrate-apply", action="store_true", help="with --calibrate: fall back to the reference mode instead of exiting")
     a = ap.parse_args()
     save_path = a.save_path or a.test_path.rstrip("/") + "_" + time.strftime("%m-%d_%H-%M", time.localtime()) + "_MARCONet"
     os.makedirs(save_path, exist_ok=True)
@@ -125,6 +145,15 @@ def main():
     for s0 in range(0, len(names), a.batch):
         chunk = names[s0:s0 + a.batch]
         paths = [os.path.join(a.test_path, f) for f in chunk]
+        if a.calibrate and s0 == 0:
+            if a.precision == "fp32":
+                print("%28s : nothing to check, fp32 is the parity mode" % "Precision margin")
+            else:
+                report = calibrate_on(pipe, manual_strips(paths) if a.manual else blind_strips(pipe, paths, dev), dev,
+                                      "fp32" if a.precision == "fp16x3" else "fp16x3", a.calibrate_apply)
+                print(report if report is not None else "Precision margin: no strip with characters in the first batch, nothing checked")
+                if report is not None and not report.ok and not report.applied:
+                    raise SystemExit(2)
         if a.device_panel:
             device_panels(pipe, paths, chunk, a.manual, save_path)
             continue

@@ -20,6 +20,7 @@
 #ifndef MARCONET_HIP_H
 #define MARCONET_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -436,6 +437,41 @@ int mnet_panel_u8(const uint8_t* preview, int32_t preview_w, const uint8_t* sr_b
  * thread that finds an element of x (n elements, MNET_F32 or MNET_F16) that is inf or NaN.  One streaming read of x, no atomics
  * (every writer stores the same value), no synchronisation: the caller reads the flag back when it consumes the result. */
 int mnet_nonfinite_flag(const void* x, int32_t dtype, int64_t n, int32_t* flag, void* stream);
+
+/* Precision margin guard: how far a run in a throughput mode lies from a run of the same network in a more accurate mode — the role a
+ * `torch.abs(a - b).max()` (with its argmax, the norms and an isfinite count) after test_sr.py:197 would play if the script ran its forward
+ * twice; the reference has no such check because it has one arithmetic.  `mode` and `ref` hold the same logical tensor [n_groups][elems_per_group]
+ * (a group = one strip's map, one glyph's prior: pixel-major, channel-minor), each in its OWN storage; one record per group is written to `stats`.
+ * The values compared are what the storage's reader returns (split half: float(hi) + float(lo); fp16+8: fl32(hi + lo8 * 2^(E - 138))); the difference
+ * is one fp32 subtraction.  A pair with a non-finite element on either side is counted and left out of every maximum and sum: a NaN cannot hide a
+ * deviation elsewhere.
+ *   (mode, ref) storages: (F16 | F16M, F16X2), (F16 | F16M | F16X2 | F32, F32); anything else MNET_E_ARG.
+ *   elems_per_group % 32 == 0 (a group starts on a 32-channel block), n_groups >= 1; F32 / F16 bases 16-byte, blocked storages 128-byte, stats and
+ *   workspace 8-byte aligned (MNET_E_ALIGN).  Everything is checked before any HIP call.
+ * One streaming pass: every workgroup of a group's MNET_CMP_SLICES(elems_per_group) slices writes one partial record to `workspace`
+ * (MNET_CMP_WORKSPACE_BYTES), a second small launch folds a group's slices in slice order.  No atomics, no counters: the same bytes on every launch, and a
+ * group's record does not depend on the other groups of the launch. */
+typedef struct {
+    float max_abs_diff;         /* max |mode - ref| over the pairs with both elements finite (0 when there is none)          */
+    float max_abs_ref;          /* max |ref| over the same pairs                                                              */
+    float max_abs_mode;         /* max |mode| over the same pairs                                                             */
+    int32_t reserved;           /* 0                                                                                          */
+    int64_t argmax_index;       /* lowest element index inside the group (pixel * C + channel) that attains max_abs_diff; -1: no finite pair */
+    double sum_sq_diff;         /* sum (mode - ref)^2 and sum ref^2 over the same pairs, fp64                                 */
+    double sum_sq_ref;
+    int64_t nonfinite_mode;     /* elements of mode / of ref that are inf or NaN                                              */
+    int64_t nonfinite_ref;
+} mnet_cmp_stats;
+#define MNET_CMP_WG_ELEMS 2048          /* elements one workgroup takes per trip: 256 threads x 8 */
+#define MNET_CMP_MAX_SLICES 32          /* workgroups per group at most; beyond 32 * 2048 elements they make further trips */
+#define MNET_CMP_SLICES(elems_per_group) \
+    ((int64_t)(elems_per_group) <= MNET_CMP_WG_ELEMS ? 1 : \
+     ((int64_t)(elems_per_group) + MNET_CMP_WG_ELEMS - 1) / MNET_CMP_WG_ELEMS >= MNET_CMP_MAX_SLICES ? MNET_CMP_MAX_SLICES : \
+     (int)(((int64_t)(elems_per_group) + MNET_CMP_WG_ELEMS - 1) / MNET_CMP_WG_ELEMS))
+#define MNET_CMP_WORKSPACE_BYTES(n_groups, elems_per_group) \
+    ((size_t)(n_groups) * (size_t)MNET_CMP_SLICES(elems_per_group) * sizeof(mnet_cmp_stats))
+int mnet_compare_stats(const void* mode, int32_t mode_dtype, const void* ref, int32_t ref_dtype, int32_t n_groups, int64_t elems_per_group,
+                       mnet_cmp_stats* stats, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * One-time weight packing on the device: from the checkpoint's tensors to the layouts above, without PyTorch

@@ -54,6 +54,35 @@ class PanelStrip(ctypes.Structure):
     _fields_ = [("show_w", c_int), ("preview_index", c_int), ("glyph0", c_int), ("n_glyphs", c_int), ("step", c_double)]
 
 
+class CmpStats(ctypes.Structure):
+    """mirror of ``mnet_cmp_stats`` (include/marconet_hip.h): one group's record of mnet_compare_stats"""
+    _fields_ = [("max_abs_diff", c_float), ("max_abs_ref", c_float), ("max_abs_mode", c_float), ("reserved", c_int),
+                ("argmax_index", c_i64), ("sum_sq_diff", c_double), ("sum_sq_ref", c_double),
+                ("nonfinite_mode", c_i64), ("nonfinite_ref", c_i64)]
+
+
+CMP_WG_ELEMS, CMP_MAX_SLICES = 2048, 32      # MNET_CMP_WG_ELEMS, MNET_CMP_MAX_SLICES
+
+
+def cmp_slices(elems_per_group):
+    """MNET_CMP_SLICES: workgroups (= partial records) per group"""
+    return max(1, min(CMP_MAX_SLICES, -(-int(elems_per_group) // CMP_WG_ELEMS)))
+
+
+def cmp_workspace_bytes(n_groups, elems_per_group):
+    """MNET_CMP_WORKSPACE_BYTES"""
+    return int(n_groups) * cmp_slices(elems_per_group) * ctypes.sizeof(CmpStats)
+
+
+def cmp_records(raw):
+    """bytes / uint8 array (a host copy of ops.compare_stats' result) → list of CmpStats, one per group"""
+    raw = bytes(memoryview(raw).cast("B")) if not isinstance(raw, (bytes, bytearray)) else bytes(raw)
+    n = ctypes.sizeof(CmpStats)
+    if len(raw) % n:
+        raise ValueError("cmp_records: %d bytes are no whole number of %d-byte records" % (len(raw), n))
+    return [CmpStats.from_buffer_copy(raw, k) for k in range(0, len(raw), n)]
+
+
 # name -> (restype, argtypes); every symbol include/marconet_hip.h declares
 SYMBOLS = {
     "mnet_last_error": (ctypes.c_char_p, []),
@@ -98,6 +127,7 @@ SYMBOLS = {
     "mnet_conv3x3_rgb": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "mnet_sr_postprocess": (c_int, [c_void_p, c_int, c_void_p, c_int, c_i64, c_int, c_void_p]),
     "mnet_nonfinite_flag": (c_int, [c_void_p, c_int, c_i64, c_void_p, c_void_p]),
+    "mnet_compare_stats": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_i64, c_void_p, c_void_p, c_void_p]),
     "mnet_lq_from_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "mnet_panel_u8": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "mnet_pack_weights": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p,

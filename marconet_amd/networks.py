@@ -69,9 +69,10 @@ class TextContextEncoderV2(nn.Module, _Precision):
         self.resnet.precision = self.resnet_precision(precision)
         return self
 
-    def forward(self, lq):
+    def forward(self, lq, *, precision=None):
+        """``precision``: the mode of this call only (None: ``self.precision``); nothing is written to the module"""
         with torch.no_grad(), ops.on_device(lq):
-            rp = self.resnet_precision(self.precision)
+            rp = self.resnet_precision(self.precision if precision is None else precision)
             dtype = torch_dtype(rp)
             x = ops.nchw_to_nhwc(lq.contiguous().float(), dtype, c_ld=rgb_pad(dtype))
             feat = self.resnet.forward_nhwc(x, rp)
@@ -487,10 +488,11 @@ class TSPSRNet(nn.Module, _Precision):
         self.scale_branch_precision = None
         self._cache = PackCache()
 
-    def _scale_branch_pack(self):
-        """packed weights the conv_*_scale branches run with, or None when they follow the module's precision mode"""
+    def _scale_branch_pack(self, override=None):
+        """packed weights the conv_*_scale branches run with, or None when they follow the module's precision mode — always under a per-call
+        ``precision=`` override (``override``): a run in another mode carries no per-layer plan"""
         want = self.scale_branch_precision
-        if want is None or want == self.precision or self.precision == "fp32":
+        if override is not None or want is None or want == self.precision or self.precision == "fp32":
             return None
         return self._cache.get(self, want, self._build), torch_dtype(want)
 
@@ -622,8 +624,8 @@ class TSPSRNet(nn.Module, _Precision):
             skip = ops.conv2d(x, co["w"], co["b"].numel(), bias=co["b"])
         return self._c(pk, name + ".conv2", h, valid_w=valid_w, residual=skip)
 
-    def _prior_transform(self, pk, tag, feat, prior, tab):
-        """All glyphs of the batch at one scale (networks.py:421-449 / :455-482)."""
+    def _prior_transform(self, pk, tag, feat, prior, tab, override=None):
+        """All glyphs of the batch at one scale (networks.py:421-449 / :455-482).  ``override``: forward_packed's per-call precision."""
         if tab.G == 0:
             return feat
         # AdaIN + crop + cat, and norm1's GroupNorm affine of the result in closed form from the AdaIN statistics
@@ -631,7 +633,7 @@ class TSPSRNet(nn.Module, _Precision):
                                                *pk["conv_%s_fuse.0.norm1" % tag], 1e-6)
         fused = self._res_block(pk, "conv_%s_fuse.0" % tag, cat, valid_w=tab.g_w, norm1_affine=(s1, h1))
         del cat
-        sb = self._scale_branch_pack()
+        sb = self._scale_branch_pack(override)
         if sb is None:
             sc = self._two(pk, "conv_%s_scale" % tag, fused, valid_w=tab.g_w)
         else:                                                    # precision plan: this branch in another storage / arithmetic (see __init__)
@@ -672,14 +674,20 @@ class TSPSRNet(nn.Module, _Precision):
             p64 = self._gather_priors(priors64, dtype, 256, 64) if sum(counts64) else None
             return self.forward_packed(lq, p64, p32, counts64, counts32, locs, nchw_out=True)
 
-    def forward_packed(self, lq, p64, p32, counts64, counts32, locs, nchw_out=False, tables=None):
+    def forward_packed(self, lq, p64, p32, counts64, counts32, locs, nchw_out=False, tables=None, precision=None, taps=None):
         """batched entry: ``p64`` NHWC [ΣN,64,64,256] / ``p32`` NHWC [ΣN,32,32,512] hold the glyph priors of all
         images back to back (``counts*[b]`` glyphs for image b).  Returns NHWC [B,128,2048,8] (RGB in channels 0-2), or —
         ``nchw_out`` — the reference's fp32 NCHW [B,3,128,2048] written by the last conv itself.  ``tables``: prebuilt
-        (GlyphTables@32, GlyphTables@64) instead of ``locs`` (the HIP-graph path keeps them at fixed device addresses)."""
+        (GlyphTables@32, GlyphTables@64) instead of ``locs`` (the HIP-graph path keeps them at fixed device addresses).
+        ``precision``: the mode of this call only (None: ``self.precision``; the priors must be in its storage); with it ``scale_branch_precision`` is
+        ignored.  ``taps``: a dict that receives REFERENCES to ``prior64`` / ``prior32`` as given, the fused maps ``feat32_fused`` / ``feat64_fused``
+        (the outputs of the two prior transforms) and ``sr`` (what this returns) — MarconetPipeline.calibrate compares them between two modes."""
         with torch.no_grad(), ops.on_device(lq):
-            pk = self._cache.get(self, self.precision, self._build)
-            dtype = torch_dtype(self.precision)
+            mode = self.precision if precision is None else precision
+            pk = self._cache.get(self, mode, self._build)
+            dtype = torch_dtype(mode)
+            if taps is not None:
+                taps["prior64"], taps["prior32"] = p64, p32
             x = ops.nchw_to_nhwc(lq.contiguous().float(), dtype, c_ld=rgb_pad(dtype))
             f32 = self._c(pk, "conv_first_32.0", x, ops.ACT_LRELU)                               # :412
             f16 = self._c(pk, "conv_first_16.0", f32, ops.ACT_LRELU)                             # :413
@@ -694,8 +702,10 @@ class TSPSRNet(nn.Module, _Precision):
             if n32:
                 tab32 = tables[0] if tables is not None else GlyphTables(locs_host, counts32, s32.shape[2], 16, lq.device)
                 p32 = self._two(pk, "conv_32_to256", p32)                                        # :424
-                s32 = self._prior_transform(pk, "32", s32, p32, tab32)                           # :425-449
+                s32 = self._prior_transform(pk, "32", s32, p32, tab32, precision)                # :425-449
                 del p32
+            if taps is not None:
+                taps["feat32_fused"] = s32
 
             h, aff = self._upconv_gn(pk, "conv_up.1", s32, "conv_up.3.norm1", ops.ACT_LRELU)   # conv_up :359-365
             del s32
@@ -704,8 +714,10 @@ class TSPSRNet(nn.Module, _Precision):
             del h
             if n64:
                 tab64 = tables[1] if tables is not None else GlyphTables(locs_host, counts64, s64.shape[2], 32, lq.device)
-                s64 = self._prior_transform(pk, "64", s64, p64, tab64)                           # :455-482
+                s64 = self._prior_transform(pk, "64", s64, p64, tab64, precision)                # :455-482
                 del p64
+            if taps is not None:
+                taps["feat64_fused"] = s64
 
             h = self._c(pk, "conv_final.0", s64, ops.ACT_LRELU)                                  # conv_final :367-376
             del s64
@@ -714,6 +726,10 @@ class TSPSRNet(nn.Module, _Precision):
             if h.shape[3] == 64:                      # conv_final.6 + tanh through the dedicated 3-output kernel
                 wr, br = pk["conv_final.6.rgb"]
                 y_nhwc, y_nchw = ops.conv3x3_rgb(h, wr, br, ops.ACT_TANH, nhwc=not nchw_out, nchw=nchw_out)
-                return y_nchw if nchw_out else y_nhwc
-            y = self._c(pk, "conv_final.6", h, ops.ACT_TANH)
-            return ops.nhwc_to_nchw(y, c=3) if nchw_out else y
+                y = y_nchw if nchw_out else y_nhwc
+            else:
+                y = self._c(pk, "conv_final.6", h, ops.ACT_TANH)
+                y = ops.nhwc_to_nchw(y, c=3) if nchw_out else y
+            if taps is not None:
+                taps["sr"] = y
+            return y

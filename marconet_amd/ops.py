@@ -18,7 +18,7 @@ from .packing import MX_DTYPE, SPLIT_DTYPE, is_split, mx_weight_rows, new_tensor
 __all__ = ["conv2d", "linear", "nchw_to_nhwc", "nhwc_to_nchw", "upsample2x", "affine_act", "groupnorm_affine",
            "adain_crop_concat", "adain_crop_concat_gn", "glyph_scatter_affine", "layernorm", "token_mix", "attention", "pixelnorm",
            "embed_gather", "demod", "argmax_rows", "convert", "fused_bias_act", "sr_postprocess", "lq_from_u8", "panel_u8", "conv3x3_rgb", "torgb", "stats",
-           "pack_weights", "pack_wsq", "gather_rows", "style_rows", "nonfinite_flag", "gn_partial_buffer", "can_emit_gn_partial", "groupnorm_affine_from_partial",
+           "pack_weights", "pack_wsq", "gather_rows", "style_rows", "nonfinite_flag", "compare_stats", "gn_partial_buffer", "can_emit_gn_partial", "groupnorm_affine_from_partial",
            "polyphase_plan", "upconv3x3_polyphase", "polyphase_ring_fix", "groupnorm_affine_from_partial_ring",
            "ACT_NONE", "ACT_RELU", "ACT_LRELU", "ACT_LRELU_SQRT2", "ACT_TANH", "ACT_GELU", "ACT_SIGMOID"]
 
@@ -687,6 +687,26 @@ def nonfinite_flag(x, out=None):
         raise TypeError("nonfinite_flag: out must be one int32 element")
     _lib.check(lib.mnet_nonfinite_flag(_p(x), _dt(x), x.numel(), _p(flag), _stream()), "mnet_nonfinite_flag")
     return flag
+
+
+@_plumbing
+def compare_stats(a, b, groups=None):
+    """mnet_compare_stats: ``a`` (the mode's tensor) against ``b`` (the reference's) — the same logical shape, each in its own storage (fp32, fp16, or a
+    tagged split-half / fp16+8 tensor; the accepted pairs: include/marconet_hip.h).  ``groups``: how many equal leading parts get a record of their own
+    (None: ``a.shape[0]``; it must divide the element count into multiples of 32).  → uint8 [groups, sizeof(mnet_cmp_stats)] on the device, one
+    ``_lib.CmpStats`` per group (``_lib.cmp_records`` reads a host copy).  No synchronisation, no statistics booked: this is not a kernel of the forward."""
+    lib = _lib.load()
+    _need_cuda(a, b)
+    if tuple(a.shape) != tuple(b.shape):
+        raise ValueError("compare_stats: shapes differ (%s, %s)" % (tuple(a.shape), tuple(b.shape)))
+    groups = int(a.shape[0]) if groups is None else int(groups)
+    if groups < 1 or a.numel() == 0 or a.numel() % groups:
+        raise ValueError("compare_stats: %d elements do not split into %d groups" % (a.numel(), groups))
+    per = a.numel() // groups
+    out = torch.empty((groups, ctypes.sizeof(_lib.CmpStats)), dtype=torch.uint8, device=a.device)
+    ws = torch.empty((_lib.cmp_workspace_bytes(groups, per),), dtype=torch.uint8, device=a.device)
+    _lib.check(lib.mnet_compare_stats(_p(a), _dt(a), _p(b), _dt(b), groups, per, _p(out), _p(ws), _stream()), "mnet_compare_stats")
+    return out
 
 
 @_plumbing

@@ -101,44 +101,118 @@ class MarconetPipeline:
         return lab.to(dev).contiguous(), torch.repeat_interleave(torch.arange(len(counts)), torch.tensor(counts)).to(dev)
 
     @torch.no_grad()
-    def _core(self, lq, lab, img_of, counts, locs, tables, return_nhwc=False, output="nchw_f32", prior_images=None):
+    def _core(self, lq, lab, img_of, counts, locs, tables, return_nhwc=False, output="nchw_f32", prior_images=None, precision=None, taps=None):
         """the device-side part of forward_batch: nothing here touches host data (it can be captured in a HIP graph).
         ``prior_images`` (fp32 [ΣN,128,128,4] or None): filled with the generator's structure images, chunk by chunk.
+        ``precision``: all three nets run THIS call in that mode (None: as configured); no module's state is written, the SR net's per-layer plan
+        (``scale_branch_precision``) is off and an image nobody asked for is not computed.  ``taps``: a dict that receives references to ``style_w``,
+        the priors as the SR net reads them, its two fused maps and its output (TSPSRNet.forward_packed) — what ``calibrate`` compares.
         → (output, finiteness flag of the SR result: int32 [1] on the device, or None with the check off)"""
-        _, _, w = self.encoder(lq)                                    # test_sr.py:146
+        _, _, w = self.encoder(lq, precision=precision)               # test_sr.py:146
+        if taps is not None:
+            taps["style_w"] = w
+        gen_prec = self.precision if precision is None else precision
+        need_image = self.need_prior_image if precision is None else prior_images is not None
         tg = self.gan.TextGenerator
         if sum(counts):
             # w0.repeat(n,1) per image (test_sr.py:183): the generator gets the B distinct styles + the glyph→image index
             # the generator runs in chunks of glyphs (bounded working set for huge batches) and writes its two prior levels
             # straight into the all-glyph buffers TSPSRNet reads (no concatenation pass: 34 GB of copies per step at batch 256)
-            G, gdt = lab.shape[0], torch_dtype(self.precision)
+            G, gdt = lab.shape[0], torch_dtype(gen_prec)
             p64 = new_tensor((G, 64, 64, 256), gdt, lq.device)
             p32 = new_tensor((G, 32, 32, 512), gdt, lq.device)
             # a returned image is computed in the mode's arithmetic; a dropped one under ``prior_image_precision`` (see forward_batch)
             # (a RETURNED image in the fp16x2 mode: its image-only level in the three-product arithmetic, networks.returned_image_precision)
             img_prec = self._image_precision() if prior_images is None or self.prior_image_precision != "auto" else returned_image_precision(self.precision)
+            if precision is not None:
+                img_prec = None                                       # the override's own arithmetic
             for s in range(0, G, self.glyph_chunk):
                 e = min(G, s + self.glyph_chunk)
                 if _NO_STYLE_DEDUPE:
                     img = tg.forward_nhwc(w.index_select(0, img_of[s:e]).contiguous(), lab[s:e].contiguous(),
-                                          need_image=self.need_prior_image, p64_out=p64[s:e], p32_out=p32[s:e], image_precision=img_prec,
-                                          precision=self.precision)[0]
+                                          need_image=need_image, p64_out=p64[s:e], p32_out=p32[s:e], image_precision=img_prec,
+                                          precision=gen_prec)[0]
                 else:
-                    img = tg.forward_nhwc(w, lab[s:e].contiguous(), need_image=self.need_prior_image, style_index=img_of[s:e].contiguous(),
-                                          p64_out=p64[s:e], p32_out=p32[s:e], image_precision=img_prec, precision=self.precision)[0]
+                    img = tg.forward_nhwc(w, lab[s:e].contiguous(), need_image=need_image, style_index=img_of[s:e].contiguous(),
+                                          p64_out=p64[s:e], p32_out=p32[s:e], image_precision=img_prec, precision=gen_prec)[0]
                 if prior_images is not None:
                     prior_images[s:e].copy_(img)
-            sr_dtype = torch_dtype(self.sr.precision)                 # the three nets may run in different precision modes
+            sr_dtype = torch_dtype(self.sr.precision if precision is None else precision)     # the three nets may run in different precision modes
             p64, p32 = ops.convert(p64, sr_dtype), ops.convert(p32, sr_dtype)
         else:
             p64 = p32 = None
         nchw = output != "u8_bgr" and not return_nhwc
-        y = self.sr.forward_packed(lq, p64, p32, counts, counts, locs, nchw_out=nchw, tables=tables)   # test_sr.py:197
+        y = self.sr.forward_packed(lq, p64, p32, counts, counts, locs, nchw_out=nchw, tables=tables, precision=precision, taps=taps)   # test_sr.py:197
         flag = ops.nonfinite_flag(y) if self._checks() else None          # device-side flag (mnet_nonfinite_flag): no synchronisation here
         if output == "u8_bgr":                                           # test_sr.py:198-200 fused: [B,128,2048,3] uint8
             y = ops.sr_postprocess(y, u8=True)
         return y, flag
 
+    @torch.no_grad()
+    def calibrate(self, lq, labels, locs, *, reference="fp16x3", tol=5e-4, max_strips=8, apply=False):
+        """The precision margin guard — the first thing to run on real checkpoints: is the configured (fast) mode inside the parity bar on THESE
+        weights, and if not, where does the deviation enter?  Runs the first ``max_strips`` strips of the batch twice on the device — once exactly
+        as ``forward_batch`` would now (the per-module modes, ``scale_branch_precision`` and ``prior_image_precision`` included), once with all
+        three nets in ``reference`` ("fp16x3": for the fp16x2 / fp16 modes; "fp32": for any mode) — and compares the two runs stage by stage with
+        one ``ops.compare_stats`` launch each: the encoder's style vector, the generator's two priors as the SR net reads them, the SR net's two
+        fused feature maps and its output.  No CPU oracle, no host arithmetic on tensors; one device→host copy of the records at the end.
+        → ``precision_guard.PrecisionReport``.  ``ok`` means: no non-finite element in any stage and max |SR(mode) − SR(reference)| ≤ ``tol``.
+
+        Why 5e-4: |mode − truth| ≤ |mode − reference| + |reference − truth|.  The parity bar is 1e-3; the most fp16x3 has been seen to deviate from
+        the fp32 oracle is 3.2e-4 (measured on an ill-conditioned net with a planted ×1000 GroupNorm gain, 2.7e-4 in the emulation; 2.7e-5 on regular weights), so a passing check keeps
+        the mode inside 1e-3 for as long as the reference itself stays within 5e-4 of the truth.  ``reference="fp32"`` removes that assumption at
+        several times the cost.  ``first_stage_over`` names the first stage whose deviation relative to max(1, |reference|) exceeds ``tol`` —
+        diagnostic only.
+
+        ``apply=True`` and not ok: ``set_precision(reference)``, the SR net's ``scale_branch_precision`` cleared, ``report.applied = True`` — the
+        pipeline then computes what one constructed at the reference mode computes.  Otherwise no state of the pipeline or its modules changes.
+        Not covered: there is no ``precision="auto"``; ``GraphedForward`` (a captured graph keeps the mode it was captured in — calibrate first),
+        ``forward_sharded`` (calibrate on one rank and apply the same mode on all), the generator's returned structure image."""
+        from . import _lib, precision_guard as pg
+        modes = [self.precision] + [m.precision for m in (self.encoder, self.gan, self.sr)]
+        pg.check_reference(modes, reference)
+        n = min(int(lq.shape[0]), int(max_strips))
+        if n < 1:
+            raise ValueError("calibrate: at least one strip is needed")
+        labels = list(labels[:n])
+        counts = [int(l.shape[0]) for l in labels]
+        with ops.on_device(lq):
+            lq = lq[:n].contiguous()
+            locs = locs[:n]
+            lab, img_of = self._host_prep(labels, counts, lq.device)
+            runs = []
+            for prec in (None, reference):          # each run's buffers other than its taps are gone before the other starts
+                taps = {}
+                self._core(lq, lab, img_of, counts, locs, None, precision=prec, taps=taps)
+                runs.append(taps)
+            g2s = pg.glyph_to_strip(counts)
+            recs, plan = [], []
+            for name in pg.STAGES:
+                a, b = runs[0].get(name), runs[1].get(name)
+                if a is None or b is None:
+                    continue
+                groups = int(a.shape[0])
+                recs.append(ops.compare_stats(a.contiguous(), b.contiguous(), groups=groups))
+                plan.append((name, groups, a.numel() // groups, g2s if name.startswith("prior") else list(range(n))))
+            del runs, taps, a, b
+            host = torch.cat(recs).cpu().numpy()                      # the one device→host copy
+        report = pg.PrecisionReport(mode=self._mode_text(), reference=reference, tol=float(tol), strips=n)
+        at = 0
+        for name, groups, per, owner in plan:
+            setattr(report, name, pg.stage_from_records(name, _lib.cmp_records(host[at:at + groups].tobytes()), owner, n, per))
+            at += groups
+        if apply and not report.ok:
+            self.set_precision(reference)
+            self.sr.scale_branch_precision = None
+            report.applied = True
+        return report
+
+    def _mode_text(self):
+        parts = ["%s %s" % (k, m.precision) for k, m in (("encoder", self.encoder), ("gan", self.gan), ("sr", self.sr)) if m.precision != self.precision]
+        sb = getattr(self.sr, "scale_branch_precision", None)
+        if sb is not None:
+            parts.append("sr scale branches %s" % sb)
+        return self.precision + (" (%s)" % ", ".join(parts) if parts else "")
 
     def forward_mixed_widths(self, lq, content_widths, labels, locs, bucket=64):
         with torch.no_grad(), ops.on_device(lq):
