@@ -3,7 +3,7 @@
 (preview | box marks | super-resolved strip | structure priors — the file test_sr.py:232 writes, under the same name).
 
     python examples/restore_strips.py -i <strips dir> -o <out dir> [-m] [--precision fp16x2] [--batch 64] [--device-prep | --device-panel]
-                                      [--calibrate [--calibrate-apply]]
+                                      [--calibrate [--calibrate-apply]] [--long-lines]
 
 Same flags as the script (-i / -o / -m, test_sr.py:236-241).  What differs, and why:
   * the YOLO character detector and the modelscope OCR (test_sr.py:55-56,86-96) are not part of this build (SURVEY.md §8f NEXT-4).  With
@@ -20,12 +20,17 @@ Same flags as the script (-i / -o / -m, test_sr.py:236-241).  What differs, and 
     mode and in the fp16x3 reference mode (fp32 for ``--precision fp16x3``) on the device and the report of ``MarconetPipeline.calibrate`` is printed — is the
     mode inside half the 1e-3 parity bar on THESE weights, and at which stage does the deviation enter.  A failed check ends the program with status 2;
     with ``--calibrate-apply`` the pipeline falls back to the reference mode instead and goes on.
+  * ``--long-lines`` (opt-in, needs ``-m``): a strip the script skips for its width (more than 512 px at height 32, test_sr.py:108-110) is cut into
+    overlapping windows of whole characters, all windows are restored in one batch and joined on the GPU (MarconetPipeline.restore_lines); it is saved
+    under the script's file name as the super-resolved line ALONE (the four-row panel is bounded by the 2048-px SR canvas).  Everything else is
+    saved as before.
 Needs the GPU (there is no CPU path in this package)."""
 import argparse
 import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -108,6 +113,28 @@ def device_panels(pipe, paths, names, manual, save_path, max_glyphs=16):
             print("Restoring %s. Using %s text: %s -> %s" % (name, "given" if manual else "predicted", s["text"], out))
 
 
+def long_lines(pipe, paths, names, save_path):
+    """--long-lines: the strips of the chunk that are too wide go through restore_lines and are saved; → the positions of the others"""
+    from PIL import Image
+    from marconet_amd.long_lines import too_wide
+    wide = []
+    for i, p in enumerate(paths):
+        with Image.open(p) as im:
+            if too_wide(im.size[1], im.size[0]):
+                wide.append(i)
+    if wide:
+        texts = [lq_io.manual_text(paths[i]) for i in wide]
+        lines = pipe.restore_lines([lq_io.load_png(paths[i]) for i in wide], texts)
+        for i, text, line in zip(wide, texts, lines):
+            if line is None:                                                     # test_sr.py:168-170, :181-190
+                print("Error in %s (no character, or a character outside the alphabet). Continue..." % names[i])
+                continue
+            out = os.path.join(save_path, "%s_%s.png" % (os.path.splitext(names[i])[0], text))       # test_sr.py:232
+            Image.fromarray(np.ascontiguousarray(line[:, :, ::-1])).save(out)    # BGR → RGB
+            print("Restoring %s as a long line of %d px. Using given text: %s -> %s" % (names[i], line.shape[1], text, out))
+    return [i for i in range(len(paths)) if i not in wide]
+
+
 def calibrate_on(pipe, strips, dev, reference, apply):
     """MarconetPipeline.calibrate on the strips of the first batch (the batch layout of MarconetPipeline.restore_strips) → the report, or None when the
     batch holds no strip with a character of the alphabet"""
@@ -132,7 +159,10 @@ def main():
     ap.add_argument("--device-panel", action="store_true", help="also compose the saved panel on the GPU (MarconetPipeline.restore_panels); implies --device-prep")
     ap.add_argument("--calibrate", action="store_true", help="check the precision mode against a more accurate one on the first batch (MarconetPipeline.calibrate) and exit with status 2 if it fails")
     ap.add_argument("--calibrate-apply", action="store_true", help="with --calibrate: fall back to the reference mode instead of exiting")
+    ap.add_argument("--long-lines", action="store_true", help="with -m: restore strips wider than 512 px at height 32 window by window and join them (MarconetPipeline.restore_lines)")
     a = ap.parse_args()
+    if a.long_lines and not a.manual:
+        ap.error("--long-lines needs -m: a window is a run of whole characters, and windows cut without the text would cut characters in half")
     save_path = a.save_path or a.test_path.rstrip("/") + "_" + time.strftime("%m-%d_%H-%M", time.localtime()) + "_MARCONet"
     os.makedirs(save_path, exist_ok=True)
     if not torch.cuda.is_available():
@@ -145,6 +175,11 @@ def main():
     for s0 in range(0, len(names), a.batch):
         chunk = names[s0:s0 + a.batch]
         paths = [os.path.join(a.test_path, f) for f in chunk]
+        if a.long_lines:
+            rest = long_lines(pipe, paths, chunk, save_path)
+            chunk, paths = [chunk[i] for i in rest], [paths[i] for i in rest]
+            if not chunk:
+                continue
         if a.calibrate and s0 == 0:
             if a.precision == "fp32":
                 print("%28s : nothing to check, fp32 is the parity mode" % "Precision margin")

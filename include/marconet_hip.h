@@ -432,6 +432,33 @@ typedef struct {
 int mnet_panel_u8(const uint8_t* preview, int32_t preview_w, const uint8_t* sr_bgr, int32_t sr_w, const float* prior_nhwc4,
                   const mnet_panel_strip* strips, const int32_t* marks, int32_t n, int32_t out_w, uint8_t* dst, void* stream);
 
+/* Long text lines (no counterpart in the script: test_sr.py:108-110 refuses a strip wider than 512 px at height 32 and tells its user to crop it):
+ * ONE launch joins, for every line of a batch, the restored windows of the line — dst uint8 [n_lines][rows][out_w][3] in sr's channel order, the
+ * bytes of marconet_amd/long_lines.py::stitch_host.  sr uint8 [n_sr][rows][sr_w][3] (mnet_sr_postprocess: rows = 128, sr_w = 2048 in the product).
+ * Line l owns windows[win0 .. win0 + n_win - 1]; window w shows columns [0, show_w) of sr[sr_index] at columns [offset, offset + show_w) of its line.
+ * Column x < the line's out_w (the rest is 0; the WHOLE destination is written):
+ *     in one window           sr[sr_index][y][x - offset][:]
+ *     in windows k and k + 1  per channel (a (2 D - 2 t - 1) + b (2 t + 1) + D) / (2 D) in integers (csrc/stitch_blend.h), a from window k, b from
+ *                             window k + 1, over the overlap [A, B) = [offset_{k+1}, offset_k + show_w_k): D = B - A, t = x - A
+ * `lines`, `windows`: DEVICE tables.  A line is written as fill and not followed if a window of it has sr_index outside [0, n_sr), show_w outside
+ * [1, sr_w] or a negative offset, if its offsets do not increase strictly, if a column of it lies in three windows or in none, or if n_win is outside
+ * [1, 65536], win0 negative or its out_w outside [0, out_w]; the lines next to it are not affected.  Indices that lie inside the tensors cannot take
+ * the kernel out of range.  MNET_E_ARG (nothing enqueued, checked before any HIP call) for a null pointer, n_lines <= 0, rows < 1, sr_w < 1 (or
+ * beyond 2^22, the range of the blend's 32-bit arithmetic), out_w < 1, n_sr < 1; MNET_E_ALIGN for a table that is not 4-byte aligned. */
+typedef struct {
+    int32_t out_w;              /* the line's width: columns [0, out_w) carry the joined line, the rest is 0 */
+    int32_t win0, n_win;        /* its windows in `windows`                                                 */
+    int32_t reserved;           /* 0                                                                        */
+} mnet_stitch_line;
+typedef struct {
+    int32_t sr_index;           /* the window's image in `sr`                                               */
+    int32_t offset;             /* its first column in the line                                             */
+    int32_t show_w;             /* its width: columns [0, show_w) of the image are shown                    */
+    int32_t reserved;           /* 0                                                                        */
+} mnet_stitch_window;
+int mnet_stitch_u8(const uint8_t* sr, int32_t n_sr, int32_t rows, int32_t sr_w, const mnet_stitch_line* lines, const mnet_stitch_window* windows,
+                   int32_t n_lines, int32_t out_w, uint8_t* dst, void* stream);
+
 /* Finiteness guard of the half-range precision modes (the role `torch.isfinite(y).all()` would play after test_sr.py:197 — the
  * reference has no such check because its fp32 activations cannot overflow): *flag (int32, device) is set to 0 and then to 1 by any
  * thread that finds an element of x (n elements, MNET_F32 or MNET_F16) that is inf or NaN.  One streaming read of x, no atomics

@@ -54,6 +54,16 @@ class PanelStrip(ctypes.Structure):
     _fields_ = [("show_w", c_int), ("preview_index", c_int), ("glyph0", c_int), ("n_glyphs", c_int), ("step", c_double)]
 
 
+class StitchLine(ctypes.Structure):
+    """mirror of ``mnet_stitch_line`` (include/marconet_hip.h): one line of mnet_stitch_u8's device table"""
+    _fields_ = [("out_w", c_int), ("win0", c_int), ("n_win", c_int), ("reserved", c_int)]
+
+
+class StitchWindow(ctypes.Structure):
+    """mirror of ``mnet_stitch_window`` (include/marconet_hip.h): one restored window of a line"""
+    _fields_ = [("sr_index", c_int), ("offset", c_int), ("show_w", c_int), ("reserved", c_int)]
+
+
 class CmpStats(ctypes.Structure):
     """mirror of ``mnet_cmp_stats`` (include/marconet_hip.h): one group's record of mnet_compare_stats"""
     _fields_ = [("max_abs_diff", c_float), ("max_abs_ref", c_float), ("max_abs_mode", c_float), ("reserved", c_int),
@@ -130,6 +140,7 @@ SYMBOLS = {
     "mnet_compare_stats": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_i64, c_void_p, c_void_p, c_void_p]),
     "mnet_lq_from_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "mnet_panel_u8": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "mnet_stitch_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "mnet_pack_weights": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p,
                                   c_void_p, c_void_p]),
     "mnet_pack_wsq": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),

@@ -677,6 +677,34 @@ def panel_u8(preview, sr_bgr, prior_nhwc4, strips, marks, out_w=None, out=None):
     return out
 
 
+def stitch_u8(sr, lines, windows, out_w, out=None):
+    """mnet_stitch_u8 (the bytes of long_lines.stitch_host): ``sr`` uint8 [n_sr,rows,sr_w,3] (``sr_postprocess``), ``lines`` uint8
+    [L, sizeof(mnet_stitch_line)] (``_lib.StitchLine``), ``windows`` uint8 [W, sizeof(mnet_stitch_window)] (``_lib.StitchWindow``) — all on the
+    device; every line's (win0, n_win) must lie inside ``windows``.  → uint8 [L,rows,out_w,3] in sr's channel order, 0 at the columns beyond a
+    line's width and over a line whose descriptors cannot be followed.  The kernel writes the whole of ``out``."""
+    lib = _lib.load()
+    _need_cuda(sr, lines, windows, out)
+    if sr.dtype != torch.uint8 or sr.dim() != 4 or sr.shape[3] != 3:
+        raise TypeError("stitch_u8: sr must be uint8 [n,rows,W,3]")
+    if lines.dtype != torch.uint8 or lines.dim() != 2 or lines.shape[1] != ctypes.sizeof(_lib.StitchLine):
+        raise TypeError("stitch_u8: a uint8 [L, %d] line table expected" % ctypes.sizeof(_lib.StitchLine))
+    if windows.dtype != torch.uint8 or windows.dim() != 2 or windows.shape[1] != ctypes.sizeof(_lib.StitchWindow):
+        raise TypeError("stitch_u8: a uint8 [W, %d] window table expected" % ctypes.sizeof(_lib.StitchWindow))
+    n_lines, out_w = int(lines.shape[0]), int(out_w)
+    if n_lines < 1 or windows.shape[0] < 1 or out_w < 1 or sr.numel() == 0:
+        raise ValueError("stitch_u8: empty batch (%d lines, %d windows, out_w %d, sr %s)" % (n_lines, windows.shape[0], out_w, list(sr.shape)))
+    if lines.data_ptr() % 4 or windows.data_ptr() % 4:
+        raise ValueError("stitch_u8: the tables must be 4-byte aligned")
+    shape = (n_lines, int(sr.shape[1]), out_w, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=sr.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.uint8:
+        raise TypeError("stitch_u8: out must be torch.uint8 %s" % list(shape))
+    _lib.check(lib.mnet_stitch_u8(_p(sr), int(sr.shape[0]), int(sr.shape[1]), int(sr.shape[2]), _p(lines), _p(windows), n_lines, out_w, _p(out),
+                                  _stream()), "mnet_stitch_u8")
+    return out
+
+
 def nonfinite_flag(x, out=None):
     """mnet_nonfinite_flag: int32 [1] device tensor (``out``: a one-element int32 view to write into), 1 iff the fp32 / fp16 tensor
     ``x`` holds an inf or NaN (no synchronisation here)"""

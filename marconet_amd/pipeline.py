@@ -8,6 +8,7 @@ loop (test_sr.py:77-197) by one pass over a whole batch —
 with one all-gather of the SR outputs.  Images are independent, so there is no other
 collective and no weight traffic.
 """
+import numpy as np
 import torch
 
 from . import ops
@@ -398,6 +399,59 @@ class MarconetPipeline:
             for k, i in enumerate(keep):
                 out[i] = panels[k, :, :show_w[k], :]
         return (out, strips) if details else out
+
+    @torch.no_grad()
+    def restore_lines(self, images, texts, boxes=None, max_glyphs=16, overlap_glyphs=2, details=False):
+        """Whole text lines, however wide: what the script tells its user to do by hand for a strip wider than 512 px at height 32 ("crop it into
+        shorter segments", test_sr.py:108-110) and the joining it leaves to them.  ``images``: uint8 RGB HxWx3 arrays; ``texts[i]``: the line's
+        characters; ``boxes[i]``: its character boxes in source pixels, or evenly spaced ones.  Per line ``long_lines.plan_windows`` cuts windows of
+        at most ``max_glyphs`` whole characters, consecutive ones sharing ``overlap_glyphs``; the crops are taken on the host, each with its slice
+        of the text and its boxes shifted into the crop, and ALL windows of ALL lines are restored as one batch exactly as ``restore_images``
+        restores strips (``lq_device.prepare_strips``, the same labels and locs, one forward, the finiteness check).  One launch then joins every
+        line on the device (``long_lines.compose_lines``: the bytes of ``long_lines.stitch_host``) and ONE device→host copy brings them back.
+        → per image a uint8 BGR array [128, out_w, 3] (a line that fits one window: ``restore_images``' own bytes); ``None`` for a line with no
+        character or with a character outside the alphabet — ``restore_strips``' decisions, applied to the line as a whole.
+        ``texts`` is required: windows cut without character boxes would cut characters in half.  ``details=True`` → ``(lines, plans)``."""
+        from . import long_lines, lq_device, lq_io
+        if texts is None:
+            raise ValueError("restore_lines needs texts: a window is a run of whole characters, and windows cut blind would cut characters in half "
+                             "(restore_images(texts=None) reads a strip of at most 512 px at height 32 without them)")
+        if len(texts) != len(images):
+            raise ValueError("restore_lines: one text per image expected (%d images, %d texts)" % (len(images), len(texts)))
+        dev = next(self.sr.parameters()).device
+        n_cls = self.gan.TextGenerator.class_num
+        plans, crops, labels, locs_rows = [None] * len(images), [], [], []
+        for i, (img, text) in enumerate(zip(images, texts)):
+            lab = lq_io.labels_from_text(text)
+            if not lab or min(lab) < 0 or max(lab) >= n_cls:                    # test_sr.py:168-170, :181-190
+                continue
+            h, w = int(img.shape[0]), int(img.shape[1])
+            bx = boxes[i] if boxes is not None and boxes[i] is not None else lq_io.evenly_spaced_boxes(len(text), w, h)
+            try:
+                plans[i] = long_lines.plan_windows(h, w, bx, max_glyphs, overlap_glyphs)
+            except ValueError as e:
+                raise ValueError("restore_lines: image %d: %s" % (i, e)) from None
+            for p in plans[i]:
+                crops.append(np.ascontiguousarray(img[:, p.c0:p.c1]))
+                labels.append(torch.tensor(lab[p.g0:p.g1], dtype=torch.float32).type(torch.LongTensor).reshape(-1, 1))   # test_sr.py:179
+                locs_rows.append(lq_io.locs_from_boxes([[b[0] - p.c0, b[1], b[2] - p.c0, b[3]] for b in bx[p.g0:p.g1]], h))
+        out = [None] * len(images)
+        live = [i for i, p in enumerate(plans) if p is not None]
+        if live:
+            prep = lq_device.prepare_strips(crops, dev)
+            counts = [int(l.shape[0]) for l in labels]
+            locs = torch.zeros((len(crops), 2 * max(counts)), dtype=torch.float32)
+            for k, row in enumerate(locs_rows):
+                locs[k, :row.shape[1]] = row[0]
+            with ops.on_device(prep.lq):
+                lab, img_of = self._host_prep(labels, counts, dev)
+                y, flag = self._core(prep.lq, lab, img_of, counts, locs, None, False, "u8_bgr")
+                self._raise_if_not_finite(flag)
+                joined = long_lines.compose_lines(y, [plans[i] for i in live])
+            joined = joined.cpu().numpy()                                        # the one device→host copy
+            for l, i in enumerate(live):
+                out[i] = joined[l, :, :long_lines.plan_out_w(plans[i]), :]
+        return (out, plans) if details else out
 
     @torch.no_grad()
     def _strips_from_images(self, images, texts, boxes, max_glyphs, preview, host_preview):
