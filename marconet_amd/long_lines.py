@@ -11,7 +11,6 @@ itself is restored does not change; a line that fits one window gives ``restore_
 import collections
 
 import numpy as np
-import torch
 
 from . import _lib, lq_device, ops
 from .lq_io import StripTooWide
@@ -185,8 +184,6 @@ def compose_lines(sr_u8, plans):
             raise ValueError("compose_lines: the plan of line %d cannot be followed (a window wider than the %d-px SR image, or a column in three "
                              "windows or in none)" % (l, sr_u8.shape[2]))
     lines, wins = build_tables(plans)
-    dev = sr_u8.device
-    lines_d = torch.from_numpy(lines.view(np.uint8).reshape(len(lines), lines.dtype.itemsize)).to(dev)      # the one copy of the line table
-    wins_d = torch.from_numpy(wins.view(np.uint8).reshape(len(wins), wins.dtype.itemsize)).to(dev)          # the one copy of the window table
+    lines_d, wins_d = ops.table_to_device(lines, sr_u8.device), ops.table_to_device(wins, sr_u8.device)      # one copy of each table
     with ops.on_device(sr_u8):
         return ops.stitch_u8(sr_u8, lines_d, wins_d, out_w=max(plan_out_w(p) for p in plans))

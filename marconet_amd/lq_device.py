@@ -94,8 +94,7 @@ def prepare_strips(images, device, preview=False, skip_too_wide=False):
         return Prepared(torch.empty((0, 3, LQ_H, LQ_W), dtype=torch.float32, device=device), [], [], [],
                         torch.empty((0, SHOW_H, 0, 3), dtype=torch.uint8, device=device) if preview else None, skipped)
     src = torch.from_numpy(np.concatenate(flat)).to(device)                            # the one copy of the pixels
-    tab = build_table(geoms, offsets, preview)
-    table = torch.from_numpy(tab.view(np.uint8).reshape(tab.shape[0], B, tab.dtype.itemsize)).to(device)      # the one copy of the table
+    table = ops.table_to_device(build_table(geoms, offsets, preview), device)           # the one copy of the table (both rows)
     with ops.on_device(src):
         lq = ops.lq_from_u8(src, table[0], LQ_H, LQ_W)
         show = ops.lq_from_u8(src, table[1], SHOW_H, max(show_w), preview=True) if preview else None

@@ -39,6 +39,12 @@ def labels_from_text(text):
     return [a.find(t) for t in text]
 
 
+def label_tensor(text):
+    """a text (or a list of alphabet indices) → the script's label tensor, int64 [n, 1], by way of float32 as test_sr.py:179 makes it"""
+    idx = labels_from_text(text) if isinstance(text, str) else list(text)
+    return torch.tensor(idx, dtype=torch.float32).type(torch.LongTensor).reshape(-1, 1)
+
+
 def text_from_labels(labels):
     """test_sr.py:31-35"""
     a = alphabet()
@@ -221,5 +227,4 @@ def strip_from_png(path, text=None, boxes=None):
         raise ValueError("no character given for %s (test_sr.py:168-170 skips such strips)" % path)
     boxes = evenly_spaced_boxes(len(text), w, h) if boxes is None else boxes
     lq, lq_w, show_w = lq_from_image(img)
-    labels = torch.tensor(labels_from_text(text), dtype=torch.float32).type(torch.LongTensor).unsqueeze(1)   # test_sr.py:179
-    return dict(lq=lq, labels=labels, locs=locs_from_boxes(boxes, h), text=text, content_w=lq_w, show_w=show_w, image=img)
+    return dict(lq=lq, labels=label_tensor(text), locs=locs_from_boxes(boxes, h), text=text, content_w=lq_w, show_w=show_w, image=img)

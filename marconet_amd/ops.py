@@ -8,6 +8,7 @@ import ctypes
 import functools
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -619,6 +620,30 @@ def sr_postprocess(y_nhwc, u8=True):
     return out
 
 
+def table_to_device(records, device):
+    """numpy record array [..., n] whose dtype is that of a ``_lib`` structure (``np.dtype(_lib.LqImage)``, ...) → uint8 [..., n, sizeof(struct)] on
+    ``device``, the form the descriptor-table kernels take: ONE host→device copy of the whole table"""
+    records = np.ascontiguousarray(records)
+    return torch.from_numpy(records.view(np.uint8).reshape(records.shape + (records.dtype.itemsize,))).to(device)
+
+
+def _check_table(who, what, table, struct, align):
+    """a descriptor table on the device: uint8 [n, sizeof(struct)] (TypeError), its rows aligned as the kernel reads them (ValueError)"""
+    if table.dtype != torch.uint8 or table.dim() != 2 or table.shape[1] != ctypes.sizeof(struct):
+        raise TypeError("%s: a uint8 [n, %d] %s expected" % (who, ctypes.sizeof(struct), what))
+    if table.data_ptr() % align:
+        raise ValueError("%s: the %s must be %d-byte aligned" % (who, what, align))
+
+
+def _out(who, out, shape, dtype, device):
+    """``out`` as given when it has exactly this shape and dtype (TypeError otherwise); None → a new tensor"""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype:
+        raise TypeError("%s: out must be %s %s" % (who, dtype, list(shape)))
+    return out
+
+
 def lq_from_u8(src, table, dst_h, canvas_w, preview=False, out=None):
     """mnet_lq_from_u8 (test_sr.py:98-115 on the device; the bits of lq_io.lq_from_image / lq_io.show_lq): ``src`` uint8 [bytes], a ragged batch
     of tightly packed HxWx3 images; ``table`` uint8 [n, sizeof(mnet_lq_image)], the images' descriptors (``_lib.LqImage``), both on the device.
@@ -626,17 +651,11 @@ def lq_from_u8(src, table, dst_h, canvas_w, preview=False, out=None):
     The kernel writes the whole of ``out``."""
     lib = _lib.load()
     _need_cuda(src, table, out)
-    if src.dtype != torch.uint8 or table.dtype != torch.uint8 or table.dim() != 2 or table.shape[1] != ctypes.sizeof(_lib.LqImage):
-        raise TypeError("lq_from_u8: uint8 pixels and a uint8 [n, %d] descriptor table expected" % ctypes.sizeof(_lib.LqImage))
-    if table.data_ptr() % 8:
-        raise ValueError("lq_from_u8: the descriptor table must be 8-byte aligned")
+    if src.dtype != torch.uint8:
+        raise TypeError("lq_from_u8: uint8 pixels expected")
+    _check_table("lq_from_u8", "descriptor table", table, _lib.LqImage, 8)
     n = int(table.shape[0])
-    shape = (n, dst_h, canvas_w, 3) if preview else (n, 3, dst_h, canvas_w)
-    dtype = torch.uint8 if preview else torch.float32
-    if out is None:
-        out = torch.empty(shape, dtype=dtype, device=src.device)
-    elif tuple(out.shape) != shape or out.dtype != dtype:
-        raise TypeError("lq_from_u8: out must be %s %s" % (dtype, list(shape)))
+    out = _out("lq_from_u8", out, (n, dst_h, canvas_w, 3) if preview else (n, 3, dst_h, canvas_w), torch.uint8 if preview else torch.float32, src.device)
     _lib.check(lib.mnet_lq_from_u8(_p(src), _p(table), n, dst_h, canvas_w, _p(out), _lib.LQ_FORM_U8_HWC if preview else _lib.LQ_FORM_F32_NCHW,
                                    _stream()), "mnet_lq_from_u8")
     return out
@@ -655,23 +674,18 @@ def panel_u8(preview, sr_bgr, prior_nhwc4, strips, marks, out_w=None, out=None):
         raise TypeError("panel_u8: sr_bgr must be uint8 [n,128,W,3]")
     if prior_nhwc4.dtype != torch.float32 or prior_nhwc4.dim() != 4 or tuple(prior_nhwc4.shape[1:]) != (128, 128, 4):
         raise TypeError("panel_u8: prior_nhwc4 must be fp32 [G,128,128,4]")
-    if strips.dtype != torch.uint8 or strips.dim() != 2 or strips.shape[1] != ctypes.sizeof(_lib.PanelStrip):
-        raise TypeError("panel_u8: a uint8 [n, %d] descriptor table expected" % ctypes.sizeof(_lib.PanelStrip))
     if marks.dtype != torch.int32 or marks.dim() != 2 or marks.shape[1] != 4:
         raise TypeError("panel_u8: marks must be int32 [G,4]")
+    _check_table("panel_u8", "descriptor table", strips, _lib.PanelStrip, 8)
     n = int(strips.shape[0])
     if n < 1 or sr_bgr.shape[0] != n:
         raise ValueError("panel_u8: one SR image per descriptor expected (%d descriptors, %d images)" % (n, sr_bgr.shape[0]))
-    if prior_nhwc4.data_ptr() % 16 or strips.data_ptr() % 8:
-        raise ValueError("panel_u8: prior_nhwc4 must be 16-byte aligned and the descriptor table 8-byte aligned")
+    if prior_nhwc4.data_ptr() % 16:
+        raise ValueError("panel_u8: prior_nhwc4 must be 16-byte aligned")
     out_w = int(preview.shape[2]) if out_w is None else int(out_w)
     if out_w < 1 or out_w > preview.shape[2]:
         raise ValueError("panel_u8: out_w %d outside [1, preview width %d]" % (out_w, preview.shape[2]))
-    shape = (n, 512, out_w, 3)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=preview.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.uint8:
-        raise TypeError("panel_u8: out must be torch.uint8 %s" % list(shape))
+    out = _out("panel_u8", out, (n, 512, out_w, 3), torch.uint8, preview.device)
     _lib.check(lib.mnet_panel_u8(_p(preview), int(preview.shape[2]), _p(sr_bgr), int(sr_bgr.shape[2]), _p(prior_nhwc4), _p(strips), _p(marks), n, out_w,
                                  _p(out), _stream()), "mnet_panel_u8")
     return out
@@ -686,20 +700,12 @@ def stitch_u8(sr, lines, windows, out_w, out=None):
     _need_cuda(sr, lines, windows, out)
     if sr.dtype != torch.uint8 or sr.dim() != 4 or sr.shape[3] != 3:
         raise TypeError("stitch_u8: sr must be uint8 [n,rows,W,3]")
-    if lines.dtype != torch.uint8 or lines.dim() != 2 or lines.shape[1] != ctypes.sizeof(_lib.StitchLine):
-        raise TypeError("stitch_u8: a uint8 [L, %d] line table expected" % ctypes.sizeof(_lib.StitchLine))
-    if windows.dtype != torch.uint8 or windows.dim() != 2 or windows.shape[1] != ctypes.sizeof(_lib.StitchWindow):
-        raise TypeError("stitch_u8: a uint8 [W, %d] window table expected" % ctypes.sizeof(_lib.StitchWindow))
+    _check_table("stitch_u8", "line table", lines, _lib.StitchLine, 4)
+    _check_table("stitch_u8", "window table", windows, _lib.StitchWindow, 4)
     n_lines, out_w = int(lines.shape[0]), int(out_w)
     if n_lines < 1 or windows.shape[0] < 1 or out_w < 1 or sr.numel() == 0:
         raise ValueError("stitch_u8: empty batch (%d lines, %d windows, out_w %d, sr %s)" % (n_lines, windows.shape[0], out_w, list(sr.shape)))
-    if lines.data_ptr() % 4 or windows.data_ptr() % 4:
-        raise ValueError("stitch_u8: the tables must be 4-byte aligned")
-    shape = (n_lines, int(sr.shape[1]), out_w, 3)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=sr.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.uint8:
-        raise TypeError("stitch_u8: out must be torch.uint8 %s" % list(shape))
+    out = _out("stitch_u8", out, (n_lines, int(sr.shape[1]), out_w, 3), torch.uint8, sr.device)
     _lib.check(lib.mnet_stitch_u8(_p(sr), int(sr.shape[0]), int(sr.shape[1]), int(sr.shape[2]), _p(lines), _p(windows), n_lines, out_w, _p(out),
                                   _stream()), "mnet_stitch_u8")
     return out

@@ -71,7 +71,7 @@ def compose_panels(preview, preview_index, show_w, sr_u8, prior_nhwc4, counts, l
         raise ValueError("compose_panels: %d structure images for %d characters" % (prior_nhwc4.shape[0], sum(int(c) for c in counts)))
     tab, marks = build_tables(preview_index, show_w, counts, locs)
     dev = preview.device
-    strips_d = torch.from_numpy(tab.view(np.uint8).reshape(n, tab.dtype.itemsize)).to(dev)      # the one copy of the descriptor table
+    strips_d = ops.table_to_device(tab, dev)                                                     # the one copy of the descriptor table
     marks_d = torch.from_numpy(marks).to(dev)                                                    # the one copy of the marks table
     with ops.on_device(preview):
         return ops.panel_u8(preview, sr_u8, prior_nhwc4, strips_d, marks_d, out_w=max(int(w) for w in show_w))

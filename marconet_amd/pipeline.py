@@ -17,10 +17,6 @@ from .networks import returned_image_precision
 from .packing import default_precision, new_tensor, torch_dtype
 
 
-import os as _os
-_NO_STYLE_DEDUPE = bool(int(_os.environ.get("MNET_NO_STYLE_DEDUPE", "0")))      # A/B knob
-
-
 class MarconetPipeline:
     def __init__(self, encoder, gan, sr, precision=None, glyph_chunk=1024, need_prior_image=True, check_finite=None,
                  prior_image_precision="auto"):
@@ -71,8 +67,8 @@ class MarconetPipeline:
         fp16x3 (see the comment there); the SR output is the same bits either way."""
         dev = lq.device
         counts = [int(l.shape[0]) for l in labels]
-        if return_prior and not self.need_prior_image:
-            raise ValueError("return_prior=True needs MarconetPipeline(need_prior_image=True): the 128-px level is what produces the image")
+        if return_prior:
+            self._require_prior_image("return_prior=True")
         with ops.on_device(lq):
             lab, img_of = self._host_prep(labels, counts, dev)
             prior = torch.empty((sum(counts), 128, 128, 4), dtype=torch.float32, device=dev) if return_prior else None
@@ -84,10 +80,12 @@ class MarconetPipeline:
         """half-range modes (fp16 / fp16x3 / fp16x2 store |activation| < 65504): an overflow turns into NaN on its way through the
         GroupNorm statistics of the following layers (and the last layer writes an infinite pre-activation as NaN instead of
         tanh's +-1), so the SR result carries it; one flag is read back per batch."""
-        # flag: int32 flags written by mnet_nonfinite_flag (1 = inf / NaN found; None: check off) — ONE device→host copy, tested on the host
-        if flag is not None and any(flag.cpu().tolist()):
-            raise FloatingPointError("marconet_amd: non-finite SR output in %s mode (activations beyond the fp16 range 65504?) — use "
-                                     "precision='fp32' for these weights" % self.precision)
+        if flag is not None:                      # None: check off
+            raise_if_flagged(flag, self.precision)
+
+    def _require_prior_image(self, what):
+        if not self.need_prior_image:
+            raise ValueError("%s needs MarconetPipeline(need_prior_image=True): the 128-px level is what produces the structure images" % what)
 
     def _host_prep(self, labels, counts, dev):
         """labels (host or device) → validated device tensors (labels [ΣN,1], glyph→image index [ΣN])"""
@@ -129,13 +127,8 @@ class MarconetPipeline:
                 img_prec = None                                       # the override's own arithmetic
             for s in range(0, G, self.glyph_chunk):
                 e = min(G, s + self.glyph_chunk)
-                if _NO_STYLE_DEDUPE:
-                    img = tg.forward_nhwc(w.index_select(0, img_of[s:e]).contiguous(), lab[s:e].contiguous(),
-                                          need_image=need_image, p64_out=p64[s:e], p32_out=p32[s:e], image_precision=img_prec,
-                                          precision=gen_prec)[0]
-                else:
-                    img = tg.forward_nhwc(w, lab[s:e].contiguous(), need_image=need_image, style_index=img_of[s:e].contiguous(),
-                                          p64_out=p64[s:e], p32_out=p32[s:e], image_precision=img_prec, precision=gen_prec)[0]
+                img = tg.forward_nhwc(w, lab[s:e].contiguous(), need_image=need_image, style_index=img_of[s:e].contiguous(),
+                                      p64_out=p64[s:e], p32_out=p32[s:e], image_precision=img_prec, precision=gen_prec)[0]
                 if prior_images is not None:
                     prior_images[s:e].copy_(img)
             sr_dtype = torch_dtype(self.sr.precision if precision is None else precision)     # the three nets may run in different precision modes
@@ -307,6 +300,46 @@ class MarconetPipeline:
             raise RuntimeError("forward_sharded(force_collective=True) needs an initialised process group")
         return all_gather_outputs(y, B, group, force=force_collective)
 
+    def _kept(self, strips):
+        """positions of the strips the script would restore (a strip that is None was too wide: ``_strips_from_images``)"""
+        n_cls = self.gan.TextGenerator.class_num
+        return [i for i, s in enumerate(strips) if s is not None and not script_skips(s["labels"], n_cls)]
+
+    @torch.no_grad()
+    def _restore_batch(self, lq, labels, locs_rows, with_prior=False):
+        """The front end every restore entry point shares.  ``lq`` [n,3,32,512] on the device, the kept strips' label tensors and their
+        ``preds_locs`` rows → (the script's post-processed image, uint8 BGR [n,128,2048,3] (test_sr.py:198-200); ``with_prior``: the generator's
+        structure images, fp32 NHWC4 [ΣN,128,128,4] in strip order, else None) — both still on the device, the finiteness check done."""
+        if with_prior:
+            self._require_prior_image("with_prior=True")
+        counts = [int(l.shape[0]) for l in labels]
+        locs = padded_locs(locs_rows)
+        with ops.on_device(lq):
+            lab, img_of = self._host_prep(labels, counts, lq.device)
+            prior = torch.empty((sum(counts), 128, 128, 4), dtype=torch.float32, device=lq.device) if with_prior else None
+            y, flag = self._core(lq, lab, img_of, counts, locs, None, False, "u8_bgr", prior_images=prior)
+            self._raise_if_not_finite(flag)
+        return y, prior
+
+    def _show_sr(self, lq, strips, keep, with_prior):
+        """``restore_strips``' result for ``strips``, of which the strips ``keep`` are restored; ``lq``: their rows, on the device"""
+        out = [None] * len(strips)
+        if not keep:
+            return out
+        kept = [strips[i] for i in keep]
+        y, prior = self._restore_batch(lq, [s["labels"] for s in kept], [s["locs"] for s in kept], with_prior)
+        y = y.cpu().numpy()
+        if with_prior:
+            prior = (prior[..., :3] * 0.5 + 0.5).cpu().numpy()                              # test_sr.py:208, on the NHWC images
+        g = 0
+        for k, (i, s) in enumerate(zip(keep, kept)):
+            out[i] = y[k, :, :s["show_w"], :]
+            if with_prior:
+                n = int(s["labels"].shape[0])
+                out[i] = (out[i], prior[g:g + n].transpose(1, 0, 2, 3).reshape(128, 128 * n, 3))   # hstack of the n images (:209-211)
+                g += n
+        return out
+
     @torch.no_grad()
     def restore_strips(self, strips, with_prior=False):
         """The body of test_sr.py's ``for img_name`` loop (:77-201) for a list of strips prepared by ``lq_io.strip_from_png``
@@ -316,32 +349,11 @@ class MarconetPipeline:
         raises, test_sr.py:181-190; no character at all, :168-170).
         ``with_prior=True`` → list of ``(ShowSR, prior128)``: ``prior128`` = the strip's structure images side by side, float32 RGB
         [128, 128·n, 3] = ``np.hstack`` of ``prior_cha * 0.5 + 0.5`` (test_sr.py:208-211) — the array the script hands to ``cv2.resize``
-        for the panel's last row (:212; cv2 is not part of this build, the resize stays with the caller)."""
-        dev = next(self.sr.parameters()).device
-        n_cls = self.gan.TextGenerator.class_num
-        keep = [i for i, s in enumerate(strips)
-                if s["labels"].numel() > 0 and int(s["labels"].min()) >= 0 and int(s["labels"].max()) < n_cls]
-        out = [None] * len(strips)
-        if not keep:
-            return out
-        m = max(int(strips[i]["labels"].shape[0]) for i in keep)
-        locs = torch.zeros((len(keep), 2 * m), dtype=torch.float32)
-        for k, i in enumerate(keep):
-            locs[k, :strips[i]["locs"].shape[1]] = strips[i]["locs"][0]
-        lq = torch.cat([strips[i]["lq"] for i in keep]).to(dev)
-        y = self.forward_batch(lq, [strips[i]["labels"] for i in keep], locs, output="u8_bgr", return_prior=with_prior)
-        if with_prior:
-            y, prior = y
-            prior = (prior * 0.5 + 0.5).permute(0, 2, 3, 1).cpu().numpy()            # test_sr.py:208
-        y = y.cpu().numpy()
-        g = 0
-        for k, i in enumerate(keep):
-            out[i] = y[k, :, :strips[i]["show_w"], :]
-            if with_prior:
-                n = int(strips[i]["labels"].shape[0])
-                out[i] = (out[i], prior[g:g + n].transpose(1, 0, 2, 3).reshape(128, 128 * n, 3))   # hstack of the n images (:209-211)
-                g += n
-        return out
+        for the panel's last row (:212; cv2 is not part of this build, the resize stays with the caller).  It is taken from the
+        generator's NHWC images as ``_core`` leaves them — the fp32 values of ``forward_batch(return_prior=True)``'s NCHW tensor."""
+        keep = self._kept(strips)
+        lq = torch.cat([strips[i]["lq"] for i in keep]).to(next(self.sr.parameters()).device) if keep else None
+        return self._show_sr(lq, strips, keep, with_prior)
 
     @torch.no_grad()
     def restore_images(self, images, texts=None, boxes=None, with_prior=False, max_glyphs=16, details=False):
@@ -355,11 +367,9 @@ class MarconetPipeline:
         ``forward_blind``.
         ``details=True`` → ``(results, strips)``: per image also the dict ``restore_strips`` consumed (lq on the device, labels, locs, text,
         content_w, show_w) plus ``show``, the uint8 RGB preview [128, show_w, 3] (``lq_io.show_lq``, resized on the device); None where skipped."""
-        _, strips = self._strips_from_images(images, texts, boxes, max_glyphs, preview=details, host_preview=details)
-        live = [i for i, s in enumerate(strips) if s is not None and s["labels"].numel() > 0]
-        out = [None] * len(images)
-        for i, r in zip(live, self.restore_strips([strips[i] for i in live], with_prior=with_prior)):
-            out[i] = r
+        prep, strips = self._strips_from_images(images, texts, boxes, max_glyphs, preview=details, host_preview=details)
+        keep = self._kept(strips)
+        out = self._show_sr(prepared_rows(prep, keep)[1], strips, keep, with_prior)
         return (out, strips) if details else out
 
     @torch.no_grad()
@@ -372,29 +382,16 @@ class MarconetPipeline:
         launch composes all panels (``panel_device.compose_panels``) and ONE device→host copy brings them back.
         ``details=True`` → ``(panels, strips)``: per image also the dict of its inputs (``text`` for the file name), None where too wide."""
         from . import panel_device
-        if not self.need_prior_image:
-            raise ValueError("restore_panels needs MarconetPipeline(need_prior_image=True): the 128-px level is what produces the panel's last row")
-        dev = next(self.sr.parameters()).device
+        self._require_prior_image("restore_panels")
         prep, strips = self._strips_from_images(images, texts, boxes, max_glyphs, preview=True, host_preview=False)
-        n_cls = self.gan.TextGenerator.class_num
-        keep = [i for i, s in enumerate(strips) if s is not None and s["labels"].numel() > 0
-                and int(s["labels"].min()) >= 0 and int(s["labels"].max()) < n_cls]                  # restore_strips' decisions
+        keep = self._kept(strips)
         out = [None] * len(images)
         if keep:
-            rows = [prep.index.index(i) for i in keep]
-            labels = [strips[i]["labels"] for i in keep]
-            counts = [int(l.shape[0]) for l in labels]
-            show_w = [strips[i]["show_w"] for i in keep]
-            locs = torch.zeros((len(keep), 2 * max(counts)), dtype=torch.float32)
-            for k, i in enumerate(keep):
-                locs[k, :strips[i]["locs"].shape[1]] = strips[i]["locs"][0]
-            with ops.on_device(prep.lq):
-                lq = prep.lq.index_select(0, torch.tensor(rows, device=dev))
-                lab, img_of = self._host_prep(labels, counts, dev)
-                prior = torch.empty((sum(counts), 128, 128, 4), dtype=torch.float32, device=dev)
-                y, flag = self._core(lq, lab, img_of, counts, locs, None, False, "u8_bgr", prior_images=prior)
-                self._raise_if_not_finite(flag)
-                panels = panel_device.compose_panels(prep.preview, rows, show_w, y, prior, counts, [strips[i]["locs"][0] for i in keep])
+            kept = [strips[i] for i in keep]
+            rows, lq = prepared_rows(prep, keep)
+            labels, locs_rows, show_w = [s["labels"] for s in kept], [s["locs"] for s in kept], [s["show_w"] for s in kept]
+            y, prior = self._restore_batch(lq, labels, locs_rows, with_prior=True)
+            panels = panel_device.compose_panels(prep.preview, rows, show_w, y, prior, [int(l.shape[0]) for l in labels], [r[0] for r in locs_rows])
             panels = panels.cpu().numpy()                                                            # the one device→host copy
             for k, i in enumerate(keep):
                 out[i] = panels[k, :, :show_w[k], :]
@@ -418,12 +415,11 @@ class MarconetPipeline:
                              "(restore_images(texts=None) reads a strip of at most 512 px at height 32 without them)")
         if len(texts) != len(images):
             raise ValueError("restore_lines: one text per image expected (%d images, %d texts)" % (len(images), len(texts)))
-        dev = next(self.sr.parameters()).device
         n_cls = self.gan.TextGenerator.class_num
         plans, crops, labels, locs_rows = [None] * len(images), [], [], []
         for i, (img, text) in enumerate(zip(images, texts)):
-            lab = lq_io.labels_from_text(text)
-            if not lab or min(lab) < 0 or max(lab) >= n_cls:                    # test_sr.py:168-170, :181-190
+            lab = lq_io.label_tensor(text)
+            if script_skips(lab, n_cls):
                 continue
             h, w = int(img.shape[0]), int(img.shape[1])
             bx = boxes[i] if boxes is not None and boxes[i] is not None else lq_io.evenly_spaced_boxes(len(text), w, h)
@@ -433,22 +429,14 @@ class MarconetPipeline:
                 raise ValueError("restore_lines: image %d: %s" % (i, e)) from None
             for p in plans[i]:
                 crops.append(np.ascontiguousarray(img[:, p.c0:p.c1]))
-                labels.append(torch.tensor(lab[p.g0:p.g1], dtype=torch.float32).type(torch.LongTensor).reshape(-1, 1))   # test_sr.py:179
+                labels.append(lab[p.g0:p.g1])
                 locs_rows.append(lq_io.locs_from_boxes([[b[0] - p.c0, b[1], b[2] - p.c0, b[3]] for b in bx[p.g0:p.g1]], h))
         out = [None] * len(images)
         live = [i for i, p in enumerate(plans) if p is not None]
         if live:
-            prep = lq_device.prepare_strips(crops, dev)
-            counts = [int(l.shape[0]) for l in labels]
-            locs = torch.zeros((len(crops), 2 * max(counts)), dtype=torch.float32)
-            for k, row in enumerate(locs_rows):
-                locs[k, :row.shape[1]] = row[0]
-            with ops.on_device(prep.lq):
-                lab, img_of = self._host_prep(labels, counts, dev)
-                y, flag = self._core(prep.lq, lab, img_of, counts, locs, None, False, "u8_bgr")
-                self._raise_if_not_finite(flag)
-                joined = long_lines.compose_lines(y, [plans[i] for i in live])
-            joined = joined.cpu().numpy()                                        # the one device→host copy
+            prep = lq_device.prepare_strips(crops, next(self.sr.parameters()).device)
+            y, _ = self._restore_batch(prep.lq, labels, locs_rows)
+            joined = long_lines.compose_lines(y, [plans[i] for i in live]).cpu().numpy()          # the one device→host copy
             for l, i in enumerate(live):
                 out[i] = joined[l, :, :long_lines.plan_out_w(plans[i]), :]
         return (out, plans) if details else out
@@ -478,7 +466,7 @@ class MarconetPipeline:
                     text = texts[i]
                     n = len(text)
                     bx = boxes[i] if boxes is not None and boxes[i] is not None else lq_io.evenly_spaced_boxes(n, int(images[i].shape[1]), h)
-                    labels = torch.tensor(lq_io.labels_from_text(text), dtype=torch.float32).type(torch.LongTensor).reshape(-1, 1)   # test_sr.py:179
+                    labels = lq_io.label_tensor(text)
                     locs = lq_io.locs_from_boxes(bx, h)
                 strips[i] = dict(lq=prep.lq[k:k + 1], labels=labels, locs=locs, text=text, content_w=prep.content_w[k], show_w=prep.show_w[k])
                 if host_preview:
@@ -496,6 +484,33 @@ class MarconetPipeline:
         labels = [l[:max_glyphs] for l in labels]
         locs = locs_from_left_right(locs_lr)
         return self.forward_batch(lq, [l.to(lq.device) for l in labels], locs), labels, locs
+
+
+def script_skips(labels, class_num):
+    """True for a strip the script would skip: no character (test_sr.py:168-170), or a label the generator raises on — −1 for a character
+    outside the alphabet, or one at or beyond ``class_num`` (:181-190).  ``labels``: the strip's int64 label tensor"""
+    return labels.numel() == 0 or int(labels.min()) < 0 or int(labels.max()) >= class_num
+
+
+def padded_locs(rows):
+    """the strips' ``preds_locs`` rows (each [1, 2·n_k]) → one fp32 [n, max 2·n_k] host tensor, zeros behind each row's end"""
+    locs = torch.zeros((len(rows), max(int(r.shape[1]) for r in rows)), dtype=torch.float32)
+    for k, r in enumerate(rows):
+        locs[k, :r.shape[1]] = r[0]
+    return locs
+
+
+def prepared_rows(prep, keep):
+    """the images ``keep`` (positions in the caller's list) in a ``lq_device.Prepared`` batch → (their rows in it, those rows of ``prep.lq``)"""
+    rows = [prep.index.index(i) for i in keep]
+    return rows, prep.lq.index_select(0, torch.tensor(rows, dtype=torch.int64, device=prep.lq.device))
+
+
+def raise_if_flagged(flag, precision):
+    """flag: int32 flags of ``ops.nonfinite_flag`` on the device (1 = inf / NaN found) — ONE device→host copy, tested on the host"""
+    if any(flag.cpu().tolist()):
+        raise FloatingPointError("marconet_amd: non-finite SR output in %s mode (activations beyond the fp16 range 65504?) — use "
+                                 "precision='fp32' for these weights" % precision)
 
 
 ALPHABET_SIZE = 6735          # utils/alphabets.py: 6735 characters; class 6735 = blank / padding
@@ -583,9 +598,7 @@ class GraphedForward:
                 return       # fp32 has no half-range overflow to report: code shared with the half-range modes may call this unconditionally
             raise RuntimeError("GraphedForward: this graph was captured with the finiteness check off (check_finite=False): "
                                "there is no flag to read — capture with MarconetPipeline(check_finite=True); `has_flag` tells")
-        if any(self._flag.cpu().tolist()):
-            raise FloatingPointError("marconet_amd: non-finite SR output in %s mode (activations beyond the fp16 range 65504?) — use "
-                                     "precision='fp32' for these weights" % self.pipe.precision)
+        raise_if_flagged(self._flag, self.pipe.precision)
 
     @torch.no_grad()
     def __call__(self, lq, labels, locs, check=None):

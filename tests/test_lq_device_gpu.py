@@ -194,6 +194,26 @@ def test_restore_images_equals_restore_strips(pipe):
     assert all(np.array_equal(plain[k], want[k][0]) for k in range(2))
 
 
+def test_restore_entry_points_skip_the_same_strips(pipe):
+    """one batch through restore_images, restore_panels and restore_lines: a restorable strip, a text with a character outside the alphabet,
+    an empty text, and a strip wider than 512 px at height 32 — which only restore_lines restores; the restorable strip's bytes agree"""
+    from marconet_amd import long_lines
+    name = cases_png.SR_STRIPS["lqe01"]
+    strip, text = lq_io.load_png(os.path.join(cases_png.PNG_DIR, name)), lq_io.manual_text(name)[:3]
+    wide = np.random.default_rng(5).integers(0, 256, (32, 600, 3), dtype=np.uint8)
+    images, texts = [strip, strip, strip, wide], [text, text[0] + " ", "", text]
+    assert len(text) == 3 and min(lq_io.labels_from_text(text)) >= 0 and min(lq_io.labels_from_text(texts[1])) == -1
+    assert not long_lines.too_wide(*strip.shape[:2]) and long_lines.too_wide(*wide.shape[:2])
+    singles, panels = pipe.restore_images(images, texts), pipe.restore_panels(images, texts)
+    lines = pipe.restore_lines(images, texts, overlap_glyphs=1)              # 3 characters in windows of 2: one shared character
+    show_w = lq_device.strip_geometry(strip).show_w
+    assert singles[1:] == [None] * 3 and singles[0].dtype == np.uint8 and singles[0].shape == (128, show_w, 3)
+    assert panels[1:] == [None] * 3 and panels[0].dtype == np.uint8 and panels[0].shape == (512, show_w, 3)
+    assert lines[1] is None and lines[2] is None
+    assert lines[3].dtype == np.uint8 and lines[3].shape[0] == 128 and abs(lines[3].shape[1] - 4 * 600) <= 1
+    assert lines[0].dtype == np.uint8 and np.array_equal(lines[0], singles[0])
+
+
 def test_restore_images_blind_equals_the_host_prepared_path(pipe):
     """texts=None: labels and locations from the encoder, as forward_blind's sources — the same bytes as the host-prepared strips give"""
     from marconet_amd.pipeline import clear_labels_batch, locs_from_left_right
