@@ -1,0 +1,65 @@
+#!/usr/bin/env python
+"""A page and its text-line boxes in, the enlarged page with every text line restored in place out (MarconetPipeline.restore_page).
+
+    python examples/restore_page.py -i page.png -r regions.json -o out.png [--scale 4] [--feather 8] [--precision fp16x2]
+
+``regions.json`` is a list of ``{"box": [x1, y1, x2, y2], "text": "...", "char_boxes": [[x1, y1, x2, y2], ...]}``: a text line's box in page pixels
+(axis-aligned; numbers that are not integers are rounded outward), its characters, and — optionally — its character boxes in page pixels (evenly
+spaced ones otherwise).  The detector and the recogniser that produce them are the caller's (SURVEY.md §8f NEXT-4).  A region with no character or
+with a character outside the alphabet keeps the enlarged page's own pixels, as the script skips such a strip (test_sr.py:168-170, :181-190).
+Not covered: overlapping regions (refused), rotated / perspective / vertical text, several pages per call.
+
+All regions are restored as one batch; the page is enlarged (cv2's INTER_CUBIC arithmetic) and every line resized, pasted and feathered on the GPU —
+only the PNG decode and encode run on the host.  Weights: ``$MARCONET_CKPT_DIR`` as in examples/restore_strips.py; without them the seeded
+synthetic weights run and the page shows the plumbing, not a restoration.  Needs the GPU (there is no CPU path in this package)."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from marconet_amd import checkpoints, lq_io                                      # noqa: E402
+from marconet_amd.pipeline import MarconetPipeline                               # noqa: E402
+
+
+def load_regions(path):
+    """→ (boxes, texts, char_boxes or None)"""
+    with open(path, encoding="utf8") as f:
+        regions = json.load(f)
+    if not isinstance(regions, list) or any(not isinstance(r, dict) or "box" not in r or "text" not in r for r in regions):
+        raise SystemExit('restore_page.py: %s must hold a list of {"box": [x1, y1, x2, y2], "text": "..."} objects' % path)
+    char_boxes = [r.get("char_boxes") for r in regions]
+    return [r["box"] for r in regions], [r["text"] for r in regions], char_boxes if any(c is not None for c in char_boxes) else None
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("-i", "--image", type=str, required=True)
+    ap.add_argument("-r", "--regions", type=str, required=True)
+    ap.add_argument("-o", "--output", type=str, required=True)
+    ap.add_argument("--scale", type=int, default=4, help="integer enlargement of the page, 1..8")
+    ap.add_argument("--feather", type=int, default=8, help="width in output pixels of the blend at a region's edge, 0..1024 (0: none)")
+    ap.add_argument("--precision", default="fp16x2", choices=["fp16x2", "fp16x3", "fp16", "fp32"])
+    a = ap.parse_args()
+    boxes, texts, char_boxes = load_regions(a.regions)
+    if not torch.cuda.is_available():
+        raise SystemExit("restore_page.py: no GPU visible — this package has no CPU path")
+    from PIL import Image
+    sde, sdg, sds, source = checkpoints.load_state_dicts()
+    print("%28s : %s" % ("Weights", source))
+    pipe = MarconetPipeline(*checkpoints.build_networks(sde, sdg, sds, "cuda"), precision=a.precision)
+    page, regions = pipe.restore_page(lq_io.load_png(a.image), boxes, texts, char_boxes=char_boxes, scale=a.scale, feather=a.feather, details=True)
+    for i, (r, text) in enumerate(zip(regions, texts)):
+        if r is None:
+            print("Region %d keeps the page's pixels (no character, or a character outside the alphabet): %r" % (i, text))
+        else:
+            print("Region %d: %d window(s), restored line %d px wide -> rectangle %s: %s" % (i, len(r["plan"]), r["out_w"], r["rect"], text))
+    Image.fromarray(page).save(a.output)
+    print("%s: %d x %d" % (a.output, page.shape[1], page.shape[0]))
+
+
+if __name__ == "__main__":
+    main()

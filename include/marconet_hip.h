@@ -459,6 +459,36 @@ typedef struct {
 int mnet_stitch_u8(const uint8_t* sr, int32_t n_sr, int32_t rows, int32_t sr_w, const mnet_stitch_line* lines, const mnet_stitch_window* windows,
                    int32_t n_lines, int32_t out_w, uint8_t* dst, void* stream);
 
+/* The page (no counterpart in the script, which ends at the restored strip): ONE launch brings every restored text line of a page to its rectangle
+ * of the enlarged page and blends it in — the bytes of marconet_amd/pages.py::paste_host, region by region.  lines uint8 [n_lines][rows][line_w][3]
+ * BGR (mnet_stitch_u8's result: rows = 128 in the product); page uint8 [page_h][page_w][3] RGB, which already holds the background (the enlarged
+ * page: mnet_lq_from_u8, MNET_LQ_FORM_U8_HWC) and is modified IN PLACE, inside the regions' rectangles only.  Region r shows columns [0, src_w) of
+ * lines[line_index] in the rectangle [x0, x0 + rw) x [y0, y0 + rh) of the page:
+ *   1. every k x k block of the line (k x c, c < k, at a ragged right edge) → per channel (2 sum + cnt) / (2 cnt) in integers (csrc/page_blend.h):
+ *      an intermediate of rows / k rows and ceil(src_w / k) columns, each value a byte;
+ *   2. that intermediate → exactly rw x rh with mnet_lq_from_u8's 8-bit INTER_CUBIC arithmetic (the taps of csrc/lq_taps.h at the sampling steps
+ *      scale_x, scale_y; both passes in integers; clip((v + 2^21) >> 22, 0, 255)); BGR → RGB;
+ *   3. feather = 0: the pixel is that byte; else, at local (u, v), a = min(2 min(u, rw - 1 - u) + 1, 2 feather), b the same on (v, rh), m = a b,
+ *      D = 4 feather^2: (bg (D - m) + fg m + D / 2) / D in integers (csrc/page_blend.h).
+ * `regions`: a DEVICE table; the caller computes per region only scalars.  A region's rectangle is left untouched (the background stays; the other
+ * regions are not affected) if line_index lies outside [0, n_lines), src_w outside [1, line_w], the rectangle not inside the page, rw or rh < 1,
+ * feather outside [0, 1024], k is not 1, 2, 4 or 8, or rows % k != 0; a table cannot take the kernel out of its buffers.  Rectangles that overlap
+ * give unspecified bytes inside the overlap and nothing outside it.  MNET_E_ARG (nothing enqueued, checked before any HIP call) for a null pointer,
+ * n_lines < 1, rows < 1, line_w < 1, n_regions < 1, page_h < 1, page_w < 1, or more than 2^31 - 1 tiles (n_regions x the page's 64 x 16 tiles);
+ * MNET_E_ALIGN for a table that is not 8-byte aligned. */
+typedef struct {
+    int32_t line_index;         /* the region's line in `lines`                                              */
+    int32_t src_w;              /* the line's width: columns [0, src_w) are shown                            */
+    int32_t x0, y0;             /* the rectangle's top left corner in the page                               */
+    int32_t rw, rh;             /* its size                                                                  */
+    int32_t feather;            /* 0 .. 1024: width of the blend ramp in page pixels, 0 for none             */
+    int32_t k;                  /* the box reduction: 1, 2, 4 or 8                                           */
+    double scale_x;             /* 1.0 / (rw / ceil(src_w / k)): intermediate step per destination column    */
+    double scale_y;             /* 1.0 / (rh / (rows / k)): the same for rows                                */
+} mnet_paste_region;
+int mnet_paste_u8(const uint8_t* lines, int32_t n_lines, int32_t rows, int32_t line_w, const mnet_paste_region* regions, int32_t n_regions,
+                  uint8_t* page, int32_t page_h, int32_t page_w, void* stream);
+
 /* Finiteness guard of the half-range precision modes (the role `torch.isfinite(y).all()` would play after test_sr.py:197 — the
  * reference has no such check because its fp32 activations cannot overflow): *flag (int32, device) is set to 0 and then to 1 by any
  * thread that finds an element of x (n elements, MNET_F32 or MNET_F16) that is inf or NaN.  One streaming read of x, no atomics

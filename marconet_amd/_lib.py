@@ -64,6 +64,12 @@ class StitchWindow(ctypes.Structure):
     _fields_ = [("sr_index", c_int), ("offset", c_int), ("show_w", c_int), ("reserved", c_int)]
 
 
+class PasteRegion(ctypes.Structure):
+    """mirror of ``mnet_paste_region`` (include/marconet_hip.h): one text region of mnet_paste_u8's device table"""
+    _fields_ = [("line_index", c_int), ("src_w", c_int), ("x0", c_int), ("y0", c_int), ("rw", c_int), ("rh", c_int), ("feather", c_int), ("k", c_int),
+                ("scale_x", c_double), ("scale_y", c_double)]
+
+
 class CmpStats(ctypes.Structure):
     """mirror of ``mnet_cmp_stats`` (include/marconet_hip.h): one group's record of mnet_compare_stats"""
     _fields_ = [("max_abs_diff", c_float), ("max_abs_ref", c_float), ("max_abs_mode", c_float), ("reserved", c_int),
@@ -141,6 +147,7 @@ SYMBOLS = {
     "mnet_lq_from_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "mnet_panel_u8": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "mnet_stitch_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "mnet_paste_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     "mnet_pack_weights": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p,
                                   c_void_p, c_void_p]),
     "mnet_pack_wsq": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),

@@ -18,7 +18,7 @@ from .packing import MX_DTYPE, SPLIT_DTYPE, is_split, mx_weight_rows, new_tensor
 
 __all__ = ["conv2d", "linear", "nchw_to_nhwc", "nhwc_to_nchw", "upsample2x", "affine_act", "groupnorm_affine",
            "adain_crop_concat", "adain_crop_concat_gn", "glyph_scatter_affine", "layernorm", "token_mix", "attention", "pixelnorm",
-           "embed_gather", "demod", "argmax_rows", "convert", "fused_bias_act", "sr_postprocess", "lq_from_u8", "panel_u8", "conv3x3_rgb", "torgb", "stats",
+           "embed_gather", "demod", "argmax_rows", "convert", "fused_bias_act", "sr_postprocess", "lq_from_u8", "panel_u8", "paste_u8", "conv3x3_rgb", "torgb", "stats",
            "pack_weights", "pack_wsq", "gather_rows", "style_rows", "nonfinite_flag", "compare_stats", "gn_partial_buffer", "can_emit_gn_partial", "groupnorm_affine_from_partial",
            "polyphase_plan", "upconv3x3_polyphase", "polyphase_ring_fix", "groupnorm_affine_from_partial_ring",
            "ACT_NONE", "ACT_RELU", "ACT_LRELU", "ACT_LRELU_SQRT2", "ACT_TANH", "ACT_GELU", "ACT_SIGMOID"]
@@ -709,6 +709,24 @@ def stitch_u8(sr, lines, windows, out_w, out=None):
     _lib.check(lib.mnet_stitch_u8(_p(sr), int(sr.shape[0]), int(sr.shape[1]), int(sr.shape[2]), _p(lines), _p(windows), n_lines, out_w, _p(out),
                                   _stream()), "mnet_stitch_u8")
     return out
+
+
+def paste_u8(lines, regions, page):
+    """mnet_paste_u8 (the bytes of pages.paste_host, region by region): ``lines`` uint8 [L,rows,line_w,3] BGR (``stitch_u8``), ``regions`` uint8
+    [R, sizeof(mnet_paste_region)] (``_lib.PasteRegion``), ``page`` uint8 [H,W,3] RGB holding the background — all on the device.  ``page`` is
+    modified IN PLACE inside the regions' rectangles and returned; a region whose descriptor cannot be followed keeps the background."""
+    lib = _lib.load()
+    _need_cuda(lines, regions, page)
+    if lines.dtype != torch.uint8 or lines.dim() != 4 or lines.shape[3] != 3:
+        raise TypeError("paste_u8: lines must be uint8 [L,rows,W,3]")
+    if page.dtype != torch.uint8 or page.dim() != 3 or page.shape[2] != 3:
+        raise TypeError("paste_u8: page must be uint8 [H,W,3]")
+    _check_table("paste_u8", "region table", regions, _lib.PasteRegion, 8)
+    if regions.shape[0] < 1 or lines.numel() == 0 or page.numel() == 0:
+        raise ValueError("paste_u8: empty batch (%d regions, lines %s, page %s)" % (regions.shape[0], list(lines.shape), list(page.shape)))
+    _lib.check(lib.mnet_paste_u8(_p(lines), int(lines.shape[0]), int(lines.shape[1]), int(lines.shape[2]), _p(regions), int(regions.shape[0]), _p(page),
+                                 int(page.shape[0]), int(page.shape[1]), _stream()), "mnet_paste_u8")
+    return page
 
 
 def nonfinite_flag(x, out=None):

@@ -1,0 +1,226 @@
+"""A page and its text regions: the enlarged page with every restored text line pasted back in place.  The script restores strips and stops there;
+its user has a scanned page or a photo and a detector's text-line boxes.  This module states what "in place" means, in integers, and returns the
+same bytes from the device:
+
+    box_factor, box_reduce    a restored line (height ``ROW_H`` = 128) is first averaged over k x k blocks, so that the cubic below never skips a pixel
+    resize_cubic_to           ``lq_io.resize_cubic``'s arithmetic to a GIVEN size: the intermediate → exactly the region's rectangle
+    feather_blend             the integer blend of the line into the background near the rectangle's edge
+    paste_host, compose_host  the pure-host definition of one region and of a page
+    build_table, compose_page the same bytes with one kernel launch (``mnet_paste_u8``) from the joined lines ``long_lines.compose_lines`` leaves on
+                              the device and the background ``ops.lq_from_u8(preview=True)`` makes of the page: ``lq_io.resize_cubic(page, s, s)``
+
+``MarconetPipeline.restore_page`` ties them to the networks.  A region is an axis-aligned integer box [x1, y1, x2, y2] in page pixels: the reference
+handles regular layouts without perspective only, so rotated, quadrilateral and vertical regions are out of scope, as are overlapping regions (the
+paste blends in place: an overlap has no defined order), detection and recognition (the caller's), and several pages in one launch.
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import _lib, lq_device, lq_io, ops
+
+ROW_H = lq_device.SHOW_H      # the height of a restored line (``restore_lines``)
+MAX_SCALE, MAX_FEATHER, MAX_K = 8, 1024, 8
+MIN_RECT_H_DIV = 16           # a rectangle under ROW_H / 16 = 8 rows is refused: the box reduction stops at 8, the cubic would skip rows
+
+
+def box_factor(rh, rows=ROW_H):
+    """the largest power of two k with k·rh ≤ rows, at most 8; 1 for a rectangle that is not lower than the line"""
+    k = 1
+    while k < MAX_K and 2 * k * int(rh) <= int(rows):
+        k *= 2
+    return k
+
+
+def box_reduce(line, k):
+    """uint8 [rows, w, c] → uint8 [rows / k, ceil(w / k), c]: every k x k block (k x c', c' < k, at a ragged right edge) replaced per channel by
+    its mean rounded half up, (2·sum + cnt) // (2·cnt) — csrc/page_blend.h's page_box_avg"""
+    line, k = np.asarray(line), int(k)
+    if line.dtype != np.uint8 or line.ndim != 3:
+        raise TypeError("box_reduce: uint8 HxWxC image expected")
+    rows, w, c = line.shape
+    if k not in (1, 2, 4, 8) or rows % k or w < 1:
+        raise ValueError("box_reduce: k in {1, 2, 4, 8} dividing the %d rows, and at least one column, expected (k = %d, w = %d)" % (rows, k, w))
+    nx = -(-w // k)
+    pad = np.zeros((rows, nx * k, c), dtype=np.int64)
+    pad[:, :w] = line
+    s = pad.reshape(rows // k, k, nx, k, c).sum(axis=(1, 3))
+    cnt = (k * np.minimum(k, w - k * np.arange(nx)))[None, :, None]
+    return ((2 * s + cnt) // (2 * cnt)).astype(np.uint8)
+
+
+def axis_scale(n_dst, n_src):
+    """the sampling step of one axis as ``lq_io._cubic_taps(n_dst, n_src, n_dst / n_src)`` computes it — the double the device table carries"""
+    return 1.0 / (int(n_dst) / int(n_src))
+
+
+def resize_cubic_to(img, dst_w, dst_h):
+    """``cv2.resize(img, (dst_w, dst_h), interpolation=cv2.INTER_CUBIC)`` for a uint8 HxWxC image: ``lq_io.resize_cubic``'s integer passes and its
+    single rounding shift by 22 bits, with the taps ``lq_io._cubic_taps(n_dst, n_src, n_dst / n_src)`` of the two sizes themselves, per axis"""
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim != 3:
+        raise TypeError("resize_cubic_to: uint8 HxWxC image expected")
+    h, w, _ = img.shape
+    dst_w, dst_h = int(dst_w), int(dst_h)
+    if dst_w < 1 or dst_h < 1 or h < 1 or w < 1:
+        raise ValueError("resize_cubic_to: empty image or output")
+    xi, xt = lq_io._cubic_taps(dst_w, w, dst_w / w)
+    yi, yt = lq_io._cubic_taps(dst_h, h, dst_h / h)
+    src = img.astype(np.int64)
+    hor = (src[:, xi, :] * xt[None, :, :, None]).sum(axis=2)                 # [h, dst_w, c]
+    ver = (hor[yi, :, :] * yt[:, :, None, None]).sum(axis=1)                 # [dst_h, dst_w, c]
+    return np.clip((ver + (1 << 21)) >> 22, 0, 255).astype(np.uint8)
+
+
+def feather_axis(n, feather):
+    """csrc/page_blend.h's page_feather_axis for every coordinate of an axis of n pixels: min(2·min(u, n−1−u) + 1, 2F)"""
+    u = np.arange(int(n), dtype=np.int64)
+    return np.minimum(2 * np.minimum(u, int(n) - 1 - u) + 1, 2 * int(feather))
+
+
+def feather_blend(bg, fg, feather):
+    """bg, fg: uint8 [RH, RW, c] → the rectangle's bytes.  F = 0: fg.  Else at (u, v): m = a·b with a = ``feather_axis(RW, F)[u]``, b the same on
+    (v, RH); D = 4F²; (bg·(D − m) + fg·m + D // 2) // D — csrc/page_blend.h's page_feather.  The line's weight m / D is symmetric, at most 1 / (2F) at
+    the edge and exactly 1 from F pixels inside, on both axes."""
+    bg, fg, F = np.asarray(bg), np.asarray(fg), int(feather)
+    if bg.shape != fg.shape or bg.dtype != np.uint8 or fg.dtype != np.uint8 or bg.ndim != 3:
+        raise ValueError("feather_blend: two uint8 images of one shape expected")
+    if not 0 <= F <= MAX_FEATHER:
+        raise ValueError("feather_blend: feather %d outside [0, %d]" % (F, MAX_FEATHER))
+    if F == 0:
+        return fg.copy()
+    m = (feather_axis(bg.shape[0], F)[:, None] * feather_axis(bg.shape[1], F)[None, :])[:, :, None]
+    D = 4 * F * F
+    return ((bg.astype(np.int64) * (D - m) + fg.astype(np.int64) * m + D // 2) // D).astype(np.uint8)
+
+
+def line_to_rect(line_bgr, rw, rh):
+    """a restored line, uint8 BGR [rows, src_w, 3] → the rectangle's foreground, uint8 RGB [rh, rw, 3]: box reduction, cubic, channel flip"""
+    line_bgr = np.asarray(line_bgr)
+    return np.ascontiguousarray(resize_cubic_to(box_reduce(line_bgr, box_factor(rh, line_bgr.shape[0])), rw, rh)[:, :, ::-1])
+
+
+def paste_host(page_up, line_bgr, rect, feather):
+    """the definition of one region: ``page_up`` (uint8 RGB [PH, PW, 3], the enlarged page) is changed IN PLACE inside ``rect`` = (x0, y0, rw, rh)
+    and returned; ``line_bgr``: the region's restored line, uint8 BGR [rows, src_w, 3]"""
+    x0, y0, rw, rh = (int(v) for v in rect)
+    if page_up.dtype != np.uint8 or page_up.ndim != 3 or page_up.shape[2] != 3:
+        raise TypeError("paste_host: uint8 RGB HxWx3 page expected")
+    if rw < 1 or rh < 1 or x0 < 0 or y0 < 0 or x0 + rw > page_up.shape[1] or y0 + rh > page_up.shape[0]:
+        raise ValueError("paste_host: rectangle %s outside the %d x %d page" % ((x0, y0, rw, rh), page_up.shape[1], page_up.shape[0]))
+    view = page_up[y0:y0 + rh, x0:x0 + rw]
+    view[...] = feather_blend(view, line_to_rect(line_bgr, rw, rh), feather)
+    return page_up
+
+
+def round_box(box, page_h, page_w):
+    """a detector's box [x1, y1, x2, y2] (any numbers) → integers, rounded outward and clamped into the page"""
+    x1, y1, x2, y2 = (float(v) for v in box)
+    return [min(max(int(math.floor(x1)), 0), int(page_w)), min(max(int(math.floor(y1)), 0), int(page_h)),
+            min(max(int(math.ceil(x2)), 0), int(page_w)), min(max(int(math.ceil(y2)), 0), int(page_h))]
+
+
+def region_rects(page_h, page_w, boxes, restored, scale, feather, rows=ROW_H):
+    """the refusals, all ValueError naming the region, and the regions' rectangles (x0, y0, rw, rh) in the enlarged page.  ``restored[i]``: region i
+    has a line to paste (the others keep the background: only their box is checked).  Refused: ``scale`` outside [1, 8] or ``feather`` outside
+    [0, 1024] (integers); a box that is not four integers with 0 ≤ x1 < x2 ≤ W and 0 ≤ y1 < y2 ≤ H; a restored region's rectangle under rows / 16
+    rows; two restored regions whose rectangles overlap."""
+    if int(scale) != scale or not 1 <= int(scale) <= MAX_SCALE:
+        raise ValueError("scale must be an integer in [1, %d], got %r" % (MAX_SCALE, scale))
+    if int(feather) != feather or not 0 <= int(feather) <= MAX_FEATHER:
+        raise ValueError("feather must be an integer in [0, %d], got %r" % (MAX_FEATHER, feather))
+    if len(restored) != len(boxes):
+        raise ValueError("one line (or None) per box expected (%d boxes, %d lines)" % (len(boxes), len(restored)))
+    s, rects = int(scale), []
+    for i, b in enumerate(boxes):
+        if len(b) != 4 or any(int(v) != v for v in b):
+            raise ValueError("region %d: an integer box [x1, y1, x2, y2] expected, got %r (round_box rounds a detector's box outward)" % (i, list(b)))
+        x1, y1, x2, y2 = (int(v) for v in b)
+        if not (0 <= x1 < x2 <= page_w and 0 <= y1 < y2 <= page_h):
+            raise ValueError("region %d: box %s is empty or lies outside the %d x %d page" % (i, [x1, y1, x2, y2], page_w, page_h))
+        rects.append((s * x1, s * y1, s * (x2 - x1), s * (y2 - y1)))
+        if restored[i] and rects[i][3] * MIN_RECT_H_DIV < rows:
+            raise ValueError("region %d: its rectangle is %d rows high at scale %d, under the %d a %d-row line can be reduced to"
+                             % (i, rects[i][3], s, rows // MIN_RECT_H_DIV, rows))
+    live = [i for i in range(len(boxes)) if restored[i]]
+    for n, i in enumerate(live):
+        for j in live[:n]:
+            a, b = rects[i], rects[j]
+            if a[0] < b[0] + b[2] and b[0] < a[0] + a[2] and a[1] < b[1] + b[3] and b[1] < a[1] + a[3]:
+                raise ValueError("regions %d and %d overlap: the paste blends in place, so an overlap has no defined order" % (j, i))
+    return rects
+
+
+def _page_array(page):
+    page = np.asarray(page)
+    if page.dtype != np.uint8 or page.ndim != 3 or page.shape[2] != 3 or page.shape[0] < 1 or page.shape[1] < 1:
+        raise TypeError("uint8 RGB HxWx3 page expected")
+    return page
+
+
+def compose_host(page, lines, boxes, scale=4, feather=8):
+    """the definition of a page: ``page`` uint8 RGB [H, W, 3]; ``lines[i]``: region i's restored line, uint8 BGR [rows, src_w, 3]
+    (``MarconetPipeline.restore_lines`` of the crop ``page[y1:y2, x1:x2]``), or None for a region that keeps the background; ``boxes[i]`` its
+    integer box → uint8 RGB [s·H, s·W, 3]: ``lq_io.resize_cubic(page, s, s)`` with ``paste_host`` of every line in its rectangle
+    (s·x1, s·y1, s·(x2 − x1), s·(y2 − y1))."""
+    page = _page_array(page)
+    rows = next((int(np.shape(l)[0]) for l in lines if l is not None), ROW_H)
+    rects = region_rects(page.shape[0], page.shape[1], boxes, [l is not None for l in lines], scale, feather, rows)
+    out = lq_io.resize_cubic(page, int(scale), int(scale))
+    for line, rect in zip(lines, rects):
+        if line is not None:
+            paste_host(out, line, rect, int(feather))
+    return out
+
+
+def build_table(rects, out_ws, feather, rows=ROW_H):
+    """→ numpy record array of ``mnet_paste_region``, one per region with a line (``out_ws[i]`` is not None), in order: region i reads line number
+    (count of such regions before it), ``out_ws[i]`` columns wide, into ``rects[i]``"""
+    live = [i for i, w in enumerate(out_ws) if w is not None]
+    tab = np.zeros((len(live),), dtype=np.dtype(_lib.PasteRegion))
+    for l, i in enumerate(live):
+        x0, y0, rw, rh = rects[i]
+        k = box_factor(rh, rows)
+        tab[l] = (l, int(out_ws[i]), x0, y0, rw, rh, int(feather), k, axis_scale(rw, -(-int(out_ws[i]) // k)), axis_scale(rh, rows // k))
+    return tab
+
+
+def compose_page(page, joined, out_ws, boxes, scale=4, feather=8, device=None):
+    """the device path of ``compose_host``.  ``page``: uint8 RGB [H, W, 3], a host array (copied once) or a device tensor; ``joined``: uint8 BGR
+    [L, rows, line_w, 3] on the device, the lines of the regions that have one, in the regions' order (``long_lines.compose_lines``), or None where
+    no region has one; ``out_ws[i]``: the width of region i's line, None for a region that keeps the background; ``boxes[i]``: its integer box.
+    → uint8 RGB [s·H, s·W, 3] on the device.  Every refusal of ``compose_host`` is raised before anything is copied or launched; then one copy of
+    the page and one of each small table (the background's descriptor, the regions), one launch for the background and one for all regions."""
+    host = not torch.is_tensor(page)
+    if host:
+        page = torch.from_numpy(np.ascontiguousarray(_page_array(page)))
+    elif page.dtype != torch.uint8 or page.dim() != 3 or page.shape[2] != 3 or page.numel() == 0:
+        raise TypeError("uint8 RGB HxWx3 page expected")
+    H, W = int(page.shape[0]), int(page.shape[1])
+    n_live = sum(w is not None for w in out_ws)
+    if n_live and (joined is None or joined.dim() != 4 or joined.shape[0] != n_live or joined.dtype != torch.uint8):
+        raise ValueError("compose_page: one joined line per region with a width expected (%d widths, lines %s)"
+                         % (n_live, None if joined is None else list(joined.shape)))
+    rows = int(joined.shape[1]) if n_live else ROW_H
+    rects = region_rects(H, W, boxes, [w is not None for w in out_ws], scale, feather, rows)
+    for i, w in enumerate(out_ws):
+        if w is not None and not 1 <= int(w) <= joined.shape[2]:
+            raise ValueError("compose_page: region %d: line width %d outside [1, %d]" % (i, int(w), joined.shape[2]))
+        if w is not None and rows % box_factor(rects[i][3], rows):
+            raise ValueError("compose_page: region %d: lines of %d rows cannot be box-reduced by %d" % (i, rows, box_factor(rects[i][3], rows)))
+    s = int(scale)
+    if host:
+        device = torch.device(device) if device is not None else joined.device if n_live else None
+        if device is None:
+            raise ValueError("compose_page: a device is needed for a host page without lines")
+        page = page.to(device)                                                             # the one copy of the pixels
+    desc = np.zeros((1,), dtype=np.dtype(_lib.LqImage))
+    desc[0] = (0, H, W, s * W, 0, 1.0 / s)
+    desc_d = ops.table_to_device(desc, page.device)
+    regions_d = ops.table_to_device(build_table(rects, out_ws, feather, rows), page.device) if n_live else None
+    with ops.on_device(page):
+        out = ops.lq_from_u8(page.reshape(-1), desc_d, s * H, s * W, preview=True)[0]      # lq_io.resize_cubic(page, s, s), bit for bit
+        if n_live:
+            ops.paste_u8(joined, regions_d, out)
+    return out

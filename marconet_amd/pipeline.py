@@ -409,12 +409,25 @@ class MarconetPipeline:
         → per image a uint8 BGR array [128, out_w, 3] (a line that fits one window: ``restore_images``' own bytes); ``None`` for a line with no
         character or with a character outside the alphabet — ``restore_strips``' decisions, applied to the line as a whole.
         ``texts`` is required: windows cut without character boxes would cut characters in half.  ``details=True`` → ``(lines, plans)``."""
+        joined, plans, live = self._joined_lines(images, texts, boxes, max_glyphs, overlap_glyphs, "restore_lines", "image")
+        out = [None] * len(images)
+        if live:
+            from . import long_lines
+            joined = joined.cpu().numpy()                                                         # the one device→host copy
+            for l, i in enumerate(live):
+                out[i] = joined[l, :, :long_lines.plan_out_w(plans[i]), :]
+        return (out, plans) if details else out
+
+    def _joined_lines(self, images, texts, boxes, max_glyphs, overlap_glyphs, who, what):
+        """``restore_lines`` up to the joined lines on the device: → (uint8 BGR [L,128,max out_w,3] — ``long_lines.compose_lines`` of the L lines
+        that are restored, or None where there is none —, the plan per image (None for a line that is skipped), the positions of the L lines in
+        ``images``).  ``who`` / ``what`` name the entry point and its unit ("image", "region") in the errors."""
         from . import long_lines, lq_device, lq_io
         if texts is None:
-            raise ValueError("restore_lines needs texts: a window is a run of whole characters, and windows cut blind would cut characters in half "
-                             "(restore_images(texts=None) reads a strip of at most 512 px at height 32 without them)")
+            raise ValueError("%s needs texts: a window is a run of whole characters, and windows cut blind would cut characters in half "
+                             "(restore_images(texts=None) reads a strip of at most 512 px at height 32 without them)" % who)
         if len(texts) != len(images):
-            raise ValueError("restore_lines: one text per image expected (%d images, %d texts)" % (len(images), len(texts)))
+            raise ValueError("%s: one text per %s expected (%d %ss, %d texts)" % (who, what, len(images), what, len(texts)))
         n_cls = self.gan.TextGenerator.class_num
         plans, crops, labels, locs_rows = [None] * len(images), [], [], []
         for i, (img, text) in enumerate(zip(images, texts)):
@@ -426,20 +439,62 @@ class MarconetPipeline:
             try:
                 plans[i] = long_lines.plan_windows(h, w, bx, max_glyphs, overlap_glyphs)
             except ValueError as e:
-                raise ValueError("restore_lines: image %d: %s" % (i, e)) from None
+                raise ValueError("%s: %s %d: %s" % (who, what, i, e)) from None
             for p in plans[i]:
                 crops.append(np.ascontiguousarray(img[:, p.c0:p.c1]))
                 labels.append(lab[p.g0:p.g1])
                 locs_rows.append(lq_io.locs_from_boxes([[b[0] - p.c0, b[1], b[2] - p.c0, b[3]] for b in bx[p.g0:p.g1]], h))
-        out = [None] * len(images)
         live = [i for i, p in enumerate(plans) if p is not None]
-        if live:
-            prep = lq_device.prepare_strips(crops, next(self.sr.parameters()).device)
-            y, _ = self._restore_batch(prep.lq, labels, locs_rows)
-            joined = long_lines.compose_lines(y, [plans[i] for i in live]).cpu().numpy()          # the one device→host copy
-            for l, i in enumerate(live):
-                out[i] = joined[l, :, :long_lines.plan_out_w(plans[i]), :]
-        return (out, plans) if details else out
+        if not live:
+            return None, plans, live
+        prep = lq_device.prepare_strips(crops, next(self.sr.parameters()).device)
+        y, _ = self._restore_batch(prep.lq, labels, locs_rows)
+        return long_lines.compose_lines(y, [plans[i] for i in live]), plans, live
+
+    @torch.no_grad()
+    def restore_page(self, image, boxes, texts, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False):
+        """A page and its text regions → the page enlarged ``scale`` times with every text line restored in place: uint8 RGB [s·H, s·W, 3] on the
+        host, the bytes of ``pages.compose_host(image, self.restore_lines(crops, texts, char_boxes), boxes, scale, feather)`` for the crops
+        ``image[y1:y2, x1:x2]``.  ``image``: uint8 RGB [H, W, 3]; ``boxes[i]``: region i's text-line box [x1, y1, x2, y2] in page pixels (numbers that
+        are not integers are rounded outward and clamped into the page: ``pages.round_box``); ``texts[i]``: its characters; ``char_boxes[i]``: its
+        character boxes in PAGE pixels, or evenly spaced ones.  ``scale``: an integer 1..8; ``feather``: 0..1024, the width in output pixels of the
+        ramp over which a line is blended into the background at its rectangle's edge (``pages.feather_blend``; 0: none).
+        The crops are taken on the host and ALL regions are restored as ONE batch by ``restore_lines``' own machinery (the windows of a region wider
+        than 512 px at height 32, ``lq_device.prepare_strips``, one forward, the finiteness check); the joined lines stay on the device.  The page is
+        uploaded once, ``mnet_lq_from_u8`` makes the background (``lq_io.resize_cubic(image, s, s)``), ONE ``mnet_paste_u8`` launch pastes every
+        region (``pages.compose_page``) and ONE device→host copy brings the page back: nothing per pixel happens on the host.
+        A region ``restore_lines`` answers with ``None`` (no character, a character outside the alphabet) keeps the background; with no boxes at all
+        the result is the background.  ValueError naming the region, before anything is copied or launched, for a box that is empty or outside the
+        page, a rectangle under 8 output rows, and two restored regions that overlap.
+        ``texts`` is required, for ``restore_lines``' reason.  ``details=True`` → ``(page, regions)``: per region a dict with ``plan`` (its windows),
+        ``out_w`` (the width of its restored line at height 128) and ``rect`` (x0, y0, rw, rh in the result), None where it kept the background.
+        Not covered: overlapping regions; rotated, quadrilateral, perspective or vertical text (the reference handles regular layouts only);
+        detection and recognition (the caller's); several pages in one launch."""
+        from . import long_lines, lq_io, pages
+        if texts is None:
+            raise ValueError("restore_page needs texts: a window is a run of whole characters, and windows cut blind would cut characters in half")
+        if len(texts) != len(boxes) or (char_boxes is not None and len(char_boxes) != len(boxes)):
+            raise ValueError("restore_page: one text (and one list of character boxes, or None) per box expected (%d boxes, %d texts)" % (len(boxes), len(texts)))
+        image = np.asarray(image)
+        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3 or image.size == 0:
+            raise TypeError("restore_page: uint8 RGB HxWx3 page expected")
+        H, W = int(image.shape[0]), int(image.shape[1])
+        n_cls = self.gan.TextGenerator.class_num
+        boxes = [pages.round_box(b, H, W) for b in boxes]
+        restored = [not script_skips(lq_io.label_tensor(t), n_cls) for t in texts]
+        try:
+            rects = pages.region_rects(H, W, boxes, restored, scale, feather)
+        except ValueError as e:
+            raise ValueError("restore_page: %s" % e) from None
+        crops = [image[b[1]:b[3], b[0]:b[2]] for b in boxes]
+        local = [None if char_boxes is None or char_boxes[i] is None else [[c[0] - b[0], c[1] - b[1], c[2] - b[0], c[3] - b[1]] for c in char_boxes[i]]
+                 for i, b in enumerate(boxes)]
+        joined, plans, live = self._joined_lines(crops, texts, local, max_glyphs, overlap_glyphs, "restore_page", "region")
+        out_ws = [None if p is None else long_lines.plan_out_w(p) for p in plans]
+        page = pages.compose_page(image, joined, out_ws, boxes, scale, feather, device=next(self.sr.parameters()).device).cpu().numpy()   # the one device→host copy
+        if not details:
+            return page
+        return page, [None if p is None else dict(plan=p, out_w=w, rect=r) for p, w, r in zip(plans, out_ws, rects)]
 
     @torch.no_grad()
     def _strips_from_images(self, images, texts, boxes, max_glyphs, preview, host_preview):
