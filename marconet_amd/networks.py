@@ -18,13 +18,14 @@ import torch.nn as nn
 from . import _lib, ops
 from .glyphs import GlyphTables
 from .packing import (MX_DTYPE, PRECISIONS, SPLIT_DTYPE, PackCache, is_split, default_precision, equal_linear_scale, pack_conv_weight,
-                      pack_linear_weight, pack_polyphase_conv_weight, pack_vec, pack_wsq, padded_cout, rgb_pad, torch_dtype)
+                      pack_linear_weight, pack_polyphase_conv_weight, pack_tapconv_weight, pack_vec, pack_wsq, padded_cout, rgb_pad, torch_dtype)
 from .resnet import resnet45stride as resnet45
 from .textvit_arch import TextViT as TextEncoder
 
 _STYLE_NORM = not bool(int(os.environ.get("MNET_NO_STYLE_NORM", "0")))     # A/B knob (tests): style rows normalised by a power of two
 _FOLD_SKIP = not bool(int(os.environ.get("MNET_NO_FOLD_SKIP", "0")))       # A/B knob: ResTextBlockV2's 1x1 skip conv as extra K of its conv2
 _NO_POLYPHASE = os.environ.get("MNET_NO_POLYPHASE", "0") == "1"             # A/B knob: the SR up-convs keep up-sample + conv (no polyphase form)
+_NO_UPFOLD = os.environ.get("MNET_NO_UPFOLD", "0") == "1"                   # A/B knob: the generator's up-convs keep up-sample + conv (no tap-conv + fold form)
 _POLYPHASE_CONV_UP = os.environ.get("MNET_POLYPHASE_CONV_UP", "0") == "1"    # A/B knob: conv_up.1 takes the polyphase form too (default: conv_final.3 only)
 _FUSE_IMG_CONVERT = os.environ.get("MNET_NO_FUSE_IMG_CONVERT", "0") != "1"   # image-only levels: the f16 conversion rides in the up-sample's store (A/B knob)
 _FUSE_CONV1_MOD = os.environ.get("MNET_NO_FUSE_CONV1_MOD", "0") != "1"      # conv1's style multiply in the SelectText gather (A/B knob)
@@ -195,6 +196,8 @@ class TextGenerator(nn.Module):
             w0 = mc.weight.detach()[0]                                             # [Cout,Cin,3,3]; scale folded in (networks.py:284)
             return dict(cin=mc.in_channel, cout=mc.out_channel, up=mc.upsample,
                         w=pack_conv_weight(w0, dtype, scale=mc.scale),
+                        # the tap-conv form of an up-conv (fp16+8 storage: ops.upfold_plan): the same weights as a 1x1 conv with 9·Cout tap-major rows
+                        w_tap=pack_tapconv_weight(w0, dtype, scale=mc.scale) if mc.upsample and dtype == MX_DTYPE and (mc.in_channel, mc.out_channel) in ops.UPFOLD_LEVELS else None,
                         wsq_t=pack_wsq(w0, mc.scale),                              # [Cin,Cout] for the demod table
                         mod_w=pack_linear_weight(mc.modulation.weight, mc.modulation.scale), mod_b=f(mc.modulation.bias),
                         bias=f(sc.bias.detach().reshape(-1) + sc.activate.bias.detach()))   # :244 then :245
@@ -305,9 +308,19 @@ class TextGenerator(nn.Module):
             La, Lb = pkl["convs"][2 * lvl], pkl["convs"][2 * lvl + 1]
             sa, da = self._style(mod, La)
             sb, db = self._style(mod, Lb)
-            xu = ops.upsample2x(x, scale=sa, out_dtype=up_dtype if up_dtype != x.dtype else None)   # bilinear ×2 (:293) with ·s_a fused
-            xa = self._styled(La, xu, sa, da, premodulated=True, post=sb)      # emits x_a·s_b (x_a has no other reader)
-            del xu
+            if La["w_tap"] is not None and up_dtype is None and not _NO_UPFOLD and ops.upfold_plan(x, La["cout"]) >= 0:
+                # tap-conv + fold (fp16+8 storage, the levels of ops.UPFOLD_LEVELS): the up-sample commutes with the conv's channel contraction, so the nine taps
+                # run as ONE 1x1 conv on the low-res map (a quarter of the MACs; the 4×-sized up-sampled tensor is never written) and a streaming kernel sums
+                # their up-sampled, shifted planes under the StyledConv's epilogue.  x keeps its other readers (ToRGB, the SR net's prior): ·s_a is its own pass
+                xs = ops.affine_act(x, sa)
+                z = ops.conv2d(xs, La["w_tap"], 9 * La["cout"], 1, 1)
+                del xs
+                xa = ops.upfold3x3(z, La["cout"], out_scale=da, bias=La["bias"], act=ops.ACT_LRELU_SQRT2, post_scale=sb)
+                del z
+            else:
+                xu = ops.upsample2x(x, scale=sa, out_dtype=up_dtype if up_dtype != x.dtype else None)   # bilinear ×2 (:293) with ·s_a fused
+                xa = self._styled(La, xu, sa, da, premodulated=True, post=sb)      # emits x_a·s_b (x_a has no other reader)
+                del xu
             wx = xa.shape[2]                                                   # this level's width (absolute, see below)
             x = self._styled(Lb, xa, sb, db, premodulated=True, out=p64_out if wx == 64 else (p32_out if wx == 32 else None))
             del xa

@@ -20,7 +20,7 @@ __all__ = ["conv2d", "linear", "nchw_to_nhwc", "nhwc_to_nchw", "upsample2x", "af
            "adain_crop_concat", "adain_crop_concat_gn", "glyph_scatter_affine", "layernorm", "token_mix", "attention", "pixelnorm",
            "embed_gather", "demod", "argmax_rows", "convert", "fused_bias_act", "sr_postprocess", "lq_from_u8", "panel_u8", "paste_u8", "conv3x3_rgb", "torgb", "stats",
            "pack_weights", "pack_wsq", "gather_rows", "style_rows", "nonfinite_flag", "compare_stats", "gn_partial_buffer", "can_emit_gn_partial", "groupnorm_affine_from_partial",
-           "polyphase_plan", "upconv3x3_polyphase", "polyphase_ring_fix", "groupnorm_affine_from_partial_ring",
+           "polyphase_plan", "upconv3x3_polyphase", "polyphase_ring_fix", "groupnorm_affine_from_partial_ring", "upfold_plan", "upfold3x3",
            "ACT_NONE", "ACT_RELU", "ACT_LRELU", "ACT_LRELU_SQRT2", "ACT_TANH", "ACT_GELU", "ACT_SIGMOID"]
 
 
@@ -404,6 +404,50 @@ def upconv3x3_polyphase(x, wgt_poly, bias_poly, wgt, bias, c, act=ACT_NONE, algo
     tb = conv2d(upsample2x(_strip_pair(x, 1)), wgt, c, 3, 3, (1, 1), (1, 1), bias=bias, act=act)        # [2N,4,2W,c]
     lr = conv2d(upsample2x(_strip_pair(x, 2)), wgt, c, 3, 3, (1, 1), (1, 1), bias=bias, act=act)        # [2N,2H,4,c]
     return y, part, polyphase_ring_fix(tb[:n], tb[n:], lr[:n], lr[n:], y)
+
+
+# Up-convs that take the tap-conv + fold form: (cin, cout) → the smallest low-res map height accepted.  The generator's 16→32 (512→512) and 32→64 (512→256)
+# levels — the ones that measured faster than up-sample + conv (profiles/upfold_ab.txt); 4→8 and 8→16 (512→512 on smaller maps) keep the old form.
+# A table of per-glyph shapes: the form of a layer never depends on the batch.
+UPFOLD_LEVELS = {(512, 512): 16, (512, 256): 16}
+
+
+def upfold_plan(x, cout, levels=None):
+    """the planner's answer for the 1x1 launch of the tap-conv form of conv3x3(bilinear_x2(x)) with ``cout`` output channels (``conv2d(x, w_tap, 9·cout)``,
+    then ``upfold3x3``), or a negative value — the caller keeps up-sample + conv.  fp16+8 storage only, the levels of ``UPFOLD_LEVELS`` (``levels``: another
+    table), and only when the planner hands the launch to an LDS-DMA tile.  It depends on the per-glyph map shape, the channel counts and the storage type,
+    never on the batch."""
+    if x.dtype != MX_DTYPE:
+        return -1
+    _, h, _, cin = x.shape
+    min_h = (UPFOLD_LEVELS if levels is None else levels).get((cin, cout))
+    if min_h is None or h < min_h:
+        return -1
+    k = conv_plan(x, 9 * cout, 1, 1)
+    return k if k >= 0 and plan_is_lds_dma(k) else -1
+
+
+@_plumbing
+def upfold3x3(z, c, out_scale=None, bias=None, act=ACT_NONE, post_scale=None, out=None):
+    """mnet_upfold3x3_nhwc: ``z`` [N,h,w,9·c] (tap-major: channel t·c + o, t = 3·ky + kx; the 1x1 conv of the low-res map with packing.pack_tapconv_weight) →
+    y [N,2h,2w,c] = post_scale · act(out_scale · Σ_t (bilinear_x2 z_t) shifted by tap t + bias): conv3x3(bilinear_x2(x)) with the conv epilogue's contract,
+    without the up-sampled tensor"""
+    lib = _lib.load()
+    _need_cuda(z, out_scale, bias, post_scale, out)
+    n, h, w, c9 = z.shape
+    if c9 != 9 * c:
+        raise RuntimeError("upfold3x3: z has %d channels, expected 9 x %d" % (c9, c))
+    for t, nm in ((out_scale, "out_scale"), (bias, "bias"), (post_scale, "post_scale")):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError("upfold3x3: %s must be float32" % nm)
+    oshape = (n, 2 * h, 2 * w, c)
+    if out is None:
+        out = new_tensor(oshape, z.dtype, z.device)
+    elif tuple(out.shape) != oshape or out.dtype != z.dtype:
+        raise RuntimeError("upfold3x3: out is %s %s, expected %s %s" % (tuple(out.shape), out.dtype, oshape, z.dtype))
+    stats.tail("upfold", (z, out), lambda: _lib.check(lib.mnet_upfold3x3_nhwc(_p(z), _p(out), _dt(z), n, h, w, c, _p(out_scale), _p(bias), act, _p(post_scale),
+                                                                             _stream()), "mnet_upfold3x3_nhwc"))
+    return out
 
 
 def plan_is_lds_dma(k):

@@ -215,6 +215,23 @@ def pack_conv_weight(w, dtype, cin_mult=8, cout_mult=4, scale=1.0, sn=None):
     return w.permute(0, 2, 3, 1).contiguous().to(dtype)
 
 
+def tapconv_weight(w):
+    """w [O,I,3,3] → [9·O,I,1,1], tap-major: row t·O + o (t = 3·ky + kx) is w[o,:,ky,kx] — the 1x1 conv of the LOW-res map whose nine output planes
+    ops.upfold3x3 up-samples, shifts and sums into conv3x3(bilinear_x2(x); w).  A permutation: no arithmetic."""
+    o, i, kh, kw = w.shape
+    if (kh, kw) != (3, 3):
+        raise ValueError("tapconv_weight: 3x3 filters only (got %dx%d)" % (kh, kw))
+    return w.detach().permute(2, 3, 0, 1).reshape(9 * o, i, 1, 1).contiguous()
+
+
+def pack_tapconv_weight(w0, dtype, scale=1.0):
+    """``w0`` [O,I,3,3] (O a whole number of 32-channel blocks in the blocked storages: the taps' row blocks must not be padded apart) → the packed
+    [9·O,1,1,I] weights of the tap-conv form in ``dtype``, every element w0 · scale"""
+    if is_split(dtype) and w0.shape[0] % 32 != 0:
+        raise ValueError("pack_tapconv_weight: %d output channels are no whole number of 32-channel blocks" % w0.shape[0])
+    return pack_conv_weight(tapconv_weight(w0), dtype, scale=scale)
+
+
 # conv3x3 ∘ bilinear×2 (align_corners=False) as four 3x3 convs on the low-res map, one per output phase: with up[2i] = ¼x[i-1] + ¾x[i] and
 # up[2i+1] = ¾x[i] + ¼x[i+1], hi-res tap r of phase p reads low-res tap a with weight POLYPHASE_TAPS[p][a][r] (rows: low-res tap, columns: hi-res tap)
 POLYPHASE_TAPS = (((0.75, 0.25, 0.0), (0.25, 0.75, 0.75), (0.0, 0.0, 0.25)),
@@ -349,7 +366,7 @@ def equal_linear_scale(in_channels, lr_mul):
 # structure and the non-tensor leaves as JSON metadata, and a SHA-256 of each holder's parameters so that a blob is never
 # attached to different weights.
 PACK_FORMAT = "marconet_amd.packed.v2"
-PACK_LAYOUT = 6        # (6: ResTextBlockV2 emits '<block>.conv2+out', round 4; holders write every precision they have packed for) bump whenever any holder's _build() changes what it emits (keys, padding, layouts): a blob written by a
+PACK_LAYOUT = 7        # (7: TextGenerator's up-convs emit 'w_tap'; 6: ResTextBlockV2 emits '<block>.conv2+out', round 4; holders write every precision they have packed for) bump whenever any holder's _build() changes what it emits (keys, padding, layouts): a blob written by a
                        # different _build must not attach (it would fail with a KeyError mid-forward, or be read with another layout)
 
 
