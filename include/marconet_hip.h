@@ -111,7 +111,8 @@ typedef struct {
     const float* in_scale;      /* [n][cin] or NULL                                               */
     const float* in_shift;      /* [n][cin] or NULL (treated as 0)                                */
     int32_t in_swish;
-    const int32_t* valid_w;     /* [n] or NULL: input columns >= valid_w[n] read as zero          */
+    const int32_t* valid_w;     /* [n] or NULL: input columns >= valid_w[n] read as zero — INPUT columns whatever the stride
+                                 * (output column ow reads columns ow*sw-pw .. ow*sw-pw+kw-1); 0 is allowed: the image reads as zero */
     const float* out_scale;     /* [n][cout] or NULL (demodulation)                               */
     const float* bias;          /* [cout] fp32 or NULL                                            */
     const void* residual;       /* NHWC like y, or NULL                                           */
@@ -132,8 +133,9 @@ typedef struct {
 int mnet_conv2d_nhwc(const mnet_conv_desc* d, void* stream);
 
 /* same with an explicit kernel choice (A/B measurements, tests): AUTO picks the LDS-DMA kernel when the launch is
- * eligible (f16, (c0+c1) % 64 == 0, c0 % 64 == 0, cout >= 64, cout % 8 == 0, no in_scale, act <= LRELU_SQRT2) and the
- * register-staged one otherwise; MNET_CONV_ALGO_DMA_CFG0 + id pins one LDS-DMA tile configuration
+ * eligible (f16, (c0+c1) % 64 == 0, c0 % 64 == 0, cout >= 64, cout % 8 == 0, no in_scale, act <= LRELU_SQRT2, and a filter of
+ * kh * kw <= 32 taps with kh, kw <= 8 — the tap mask of a pixel is one 32-bit word; any stride and any padding >= 0) and the
+ * register-staged one otherwise (it takes every filter); MNET_CONV_ALGO_DMA_CFG0 + id pins one LDS-DMA tile configuration
  * (cout x pixel tile, waves, LDS stages):
  *   id 0: 256x256 16w 2st   1: 256x128 8w 3st   2: 128x256 8w 3st   3: 64x256 8w 3st   4: 128x512 16w 2st
  *      5: 64x512 8w 2st     6: 256x256 8w 2st (128x64 per wave)      — all on v_mfma_f32_16x16x32_f16 walking k in the

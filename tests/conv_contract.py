@@ -37,32 +37,33 @@ def family_levels(family):
     return lv
 
 
-def _pairs(levels):
-    return {((a, la), (b, lb)) for a, b in itertools.combinations(NAMES, 2) for la in levels[a] for lb in levels[b]}
+def _pairs(levels, names=NAMES):
+    return {((a, la), (b, lb)) for a, b in itertools.combinations(names, 2) for la in levels[a] for lb in levels[b]}
 
 
-def row_pairs(row):
-    return {((a, row[a]), (b, row[b])) for a, b in itertools.combinations(NAMES, 2)}
+def row_pairs(row, names=NAMES):
+    return {((a, row[a]), (b, row[b])) for a, b in itertools.combinations(names, 2)}
 
 
-def all_pairs(levels, seed=0):
+def all_pairs(levels, seed=0, names=NAMES):
     """greedy all-pairs cover: every new row starts from the first uncovered pair and fills the other factors, in a seeded order, with the level that
-    covers the most still-uncovered pairs (ties: the seeded generator).  Deterministic for a given seed."""
+    covers the most still-uncovered pairs (ties: the seeded generator).  Deterministic for a given seed.  ``names``: the factors, in order (the
+    epilogue contract's by default; tests/conv_geometry.py passes its own)."""
     rng = random.Random(seed)
-    todo = _pairs(levels)
+    todo = _pairs(levels, names)
     rows = []
     while todo:
         (a, la), (b, lb) = min(todo, key=repr)
         row = {a: la, b: lb}
-        rest = [f for f in NAMES if f not in row]
+        rest = [f for f in names if f not in row]
         rng.shuffle(rest)
         for f in rest:
             def gain(lv):
                 return sum(((g, row[g]), (f, lv)) in todo or ((f, lv), (g, row[g])) in todo for g in row)
             best = max(gain(lv) for lv in levels[f])
             row[f] = rng.choice([lv for lv in levels[f] if gain(lv) == best])
-        row = {f: row[f] for f in NAMES}
-        todo -= row_pairs(row)
+        row = {f: row[f] for f in names}
+        todo -= row_pairs(row, names)
         rows.append(row)
     return rows
 
