@@ -18,7 +18,9 @@ extern "C" {
  *   y[n,Y,X,c] = post_scale[n,c] * act( out_scale[n,c] * sum_{ky,kx} (U z_{ky,kx})[n, Y + ky - 1, X + kx - 1, c] + bias[c] ),     y [n,2h,2w,c]
  * U = the bilinear x2 of mnet_upsample2x_nhwc (1/4, 3/4 weights, align_corners=False, edge clamp); terms outside the hi-res map are zero (the conv's zero padding),
  * so the identity with conv3x3(U x) is exact at the borders as well.  fp32 sums in a fixed order per output (batch-invariant bytes), one rounding to storage.
- * z and y in the same storage `dtype` (c % 8 == 0, f32: c % 4 == 0; blocked storages: c % 32 == 0, 128-byte aligned); act: MNET_ACT_NONE, MNET_ACT_LRELU or
+ * The fold takes all four storages, MNET_F32, MNET_F16, MNET_F16X2 (split half) and MNET_F16M (fp16+8), with their alignment rules: z and y in the same storage
+ * `dtype`, 16-byte aligned, c % 8 == 0 (f32: c % 4 == 0); blocked storages: c % 32 == 0, 128-byte aligned.  Maps with w * 9 c >= 2^29 or h * w * (c / 8) * 4
+ * >= 2^31 (f32: c / 4) are refused with MNET_E_ARG.  act: MNET_ACT_NONE, MNET_ACT_LRELU or
  * MNET_ACT_LRELU_SQRT2; out_scale, bias, post_scale: fp32, 16-byte aligned, each may be NULL. */
 int mnet_upfold3x3_nhwc(const void* z, void* y, int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c,
                         const float* out_scale, const float* bias, int32_t act, const float* post_scale, void* stream);

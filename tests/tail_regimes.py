@@ -7,6 +7,8 @@ The formulas are COPIED from the sources (the line each one mirrors is named nex
 re-derive the shapes below."""
 
 import functools
+import os
+import re
 
 F32, F16, SPLIT, MX = "fp32", "f16", "split", "mx"
 STORAGES = (F32, F16, SPLIT, MX)
@@ -40,6 +42,38 @@ def ups_runs(h):
     """(number of row runs, rows in the last run) — aux_kernels.hip:131 `y0 = (col / W) * R, y1 = min(y0 + R, H)`; odd runs walk up (:175)"""
     runs = _cdiv(h, UPS_RUN)
     return runs, h - (runs - 1) * UPS_RUN
+
+
+# ---------------------------------------------------------------------------------------------------------------- upfold3x3
+def _upf_run():
+    """the #define MNET_UPF_RUN line of upfold_kernels.hip (read, not copied: tests/test_upfold_gpu.py reads it the same way)"""
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "marconet_amd", "csrc", "upfold_kernels.hip")
+    with open(src) as f:
+        return int(re.search(r"#define MNET_UPF_RUN (\d+)", f.read()).group(1))
+
+
+UPF_RUN = _upf_run()
+UPF_CAP = 2048                # upfold_kernels.hip, launcher: `(per + 255) / 256 < 2048 ? (per + 255) / 256 : 2048`
+
+
+def upf_launch(n, h, w, c, dtype):
+    """-> (per, gx, trips, xcd_remap_on) of mnet_upfold3x3_nhwc (c: OUTPUT channels; z holds 9 c).
+    per: `((h + MNET_UPF_RUN - 1) / MNET_UPF_RUN) * 2 * w * (c / N)` — one thread per (chunk, HI-res column, run of low-res rows); gx: the cap line;
+    grid (gx, n); trips of `for (id = bx * 256u + threadIdx.x; id < items_per_image; id += gridDim.x * 256u)`; remap: `(NWG & 7u) == 0u`"""
+    per = _cdiv(h, UPF_RUN) * 2 * w * (c // vec_n(dtype))
+    gx = min(_cdiv(per, WG), UPF_CAP)
+    return per, gx, _cdiv(per, gx * WG), (gx * n) % 8 == 0
+
+
+def upf_runs(h):
+    """(number of row runs, low-res rows in the last run) — `y0 = (col / W2) * R, y1 = min(y0 + R, H)`"""
+    runs = _cdiv(h, UPF_RUN)
+    return runs, h - (runs - 1) * UPF_RUN
+
+
+def upf_guards_ok(n, h, w, c, dtype):
+    """the launcher's two "image too large" guards"""
+    return w * 9 * c < 1 << 29 and h * w * (c // vec_n(dtype)) * 4 < 1 << 31
 
 
 # ---------------------------------------------------------------------------------------------------------------- GroupNorm statistics
@@ -214,6 +248,60 @@ UPS_REGIME = {
 for _m in range(4):
     UPS_REGIME["H%%4=%d, even runs" % _m] = _ups_h(_m, False)
     UPS_REGIME["H%%4=%d, odd runs" % _m] = _ups_h(_m, True)
+
+# ---- upfold3x3: (regime, (n, h, w, c)), c = output channels.  h x 24 x 64 maps: 48 hi-res columns x 8 (16 in fp32) chunks per run = 384 (768) items,
+#      so two runs make 3 (6) workgroups per image; c = 64 gives two 32-channel blocks per pixel in the blocked storages
+UPF_CASES = [
+    ("several workgroups, XCD remap on", (8, 16, 24, 64)),
+    ("several workgroups, XCD remap off", (3, 16, 24, 64)),
+    ("H%8=0", (3, 16, 24, 64)), ("H%8=1", (8, 9, 24, 64)), ("H%8=2", (3, 10, 24, 64)), ("H%8=3", (8, 11, 24, 64)),
+    ("H%8=4", (3, 12, 24, 64)), ("H%8=5", (8, 13, 24, 64)), ("H%8=6", (3, 14, 24, 64)), ("H%8=7", (8, 15, 24, 64)),
+    ("three runs", (3, 17, 24, 64)), ("three runs", (8, 24, 24, 64)),
+    ("one run, H<8", (3, 1, 40, 64)), ("one run, H<8", (3, 2, 40, 64)), ("one run, H<8", (3, 3, 40, 64)), ("one run, H<8", (3, 7, 40, 64)),
+    ("one run, H=8", (3, 8, 40, 64)),                       # the top and the bottom edge fall into the same full run
+    ("W=1", (3, 17, 1, 512)), ("W=1", (8, 9, 1, 1024)),     # every column clamps on both sides ((8, 9, 1, 512) is ONE workgroup per image in the 8-channel-chunk storages)
+    ("W=2", (3, 9, 2, 512)),                                # the left and the right clamp on neighbouring columns
+]
+# the smallest map that reaches the second trip with one 32-channel block: per = 2 * 65600 * 4 = 2 * 32800 * 8 = 524 800 items > 2048 * 256 = 524 288;
+# z = 2 * 65600 * 288 elements (151 MB at 4 bytes), y = 4 * 131200 * 32 (67 MB)
+UPF_CAP_CASE = ("2 trips + XCD", {F32: (1, 2, 32800, 32), F16: (1, 2, 65600, 32), SPLIT: (1, 2, 65600, 32), MX: (1, 2, 65600, 32)})
+
+
+# input scale of z per case: 1.5 (the scale of tests/test_upfold_gpu.py's first cases) unless the case has no headroom with it.  fp16+8 holds an output in [8, 16)
+# to 2^-13 = 1.22e-4, so the half bound 1e-5 x max |ref| of tests/test_tail_regimes.py::test_upfold_reference_headroom needs max |ref| >= 12.2: at scale 1.5 the
+# (3, 17, 1, 512) map has max |ref| = 12.22 (0.9998 of the half bound); at 1.8 it is 14.7, still below 16
+UPF_Z_SCALE = {(3, 17, 1, 512): 1.8}
+
+
+def upf_z_scale(p):
+    return UPF_Z_SCALE.get(tuple(p), 1.5)
+
+
+def _upf_h(mod):
+    def ok(p, dt):
+        runs, last = upf_runs(p[1])
+        per, gx, trips, _ = upf_launch(*p, dt)
+        return p[1] % UPF_RUN == mod and runs >= 2 and last == (mod or UPF_RUN) and gx > 1 and trips == 1
+    return ok
+
+
+def _upf_cap(p, dt):
+    per, gx, trips, remap = upf_launch(*p, dt)
+    return gx == UPF_CAP and trips == 2 and per % (UPF_CAP * WG) != 0 and remap and p[0] == 1 and upf_guards_ok(*p, dt)
+
+
+UPF_REGIME = {
+    "several workgroups, XCD remap on": lambda p, dt: upf_launch(*p, dt)[1] > 1 and upf_launch(*p, dt)[2] == 1 and upf_launch(*p, dt)[3],
+    "several workgroups, XCD remap off": lambda p, dt: upf_launch(*p, dt)[1] > 1 and upf_launch(*p, dt)[2] == 1 and not upf_launch(*p, dt)[3],
+    "three runs": lambda p, dt: upf_runs(p[1])[0] == 3 and upf_launch(*p, dt)[1] > 1 and upf_launch(*p, dt)[2] == 1,
+    "one run, H<8": lambda p, dt: p[1] < UPF_RUN and upf_runs(p[1]) == (1, p[1]) and upf_launch(*p, dt)[1] > 1 and upf_launch(*p, dt)[2] == 1,
+    "one run, H=8": lambda p, dt: p[1] == UPF_RUN and upf_runs(p[1]) == (1, UPF_RUN) and upf_launch(*p, dt)[1] > 1 and upf_launch(*p, dt)[2] == 1,
+    "W=1": lambda p, dt: p[2] == 1 and upf_runs(p[1])[0] >= 2 and upf_launch(*p, dt)[1] > 1 and upf_launch(*p, dt)[2] == 1,
+    "W=2": lambda p, dt: p[2] == 2 and upf_runs(p[1])[0] >= 2 and upf_launch(*p, dt)[1] > 1 and upf_launch(*p, dt)[2] == 1,
+    "2 trips + XCD": _upf_cap,
+}
+for _m in range(8):
+    UPF_REGIME["H%%8=%d" % _m] = _upf_h(_m)
 
 # ---- affine_act: (regime, (n, hw as (h, w), c)) per storage
 AFFINE_CASES = {

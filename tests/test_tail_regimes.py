@@ -99,3 +99,104 @@ def test_flat_kernel_cases_pass_their_caps():
     assert R.convert_regime_ok(), R.convert_launch(R.CONVERT_COUNT)
     assert R.sr_regime_ok() and R.fba_regime_ok()
     assert {c for _, p in R.AFFINE_CASES[R.F32] for c in (p[2],)} >= {512, 1024}          # the fp32 two-chunk form at both widths that reach it
+
+
+# ====================================================================================================================== upfold3x3
+def test_upfold_mirrored_constants_are_the_sources():
+    hip = _src("marconet_amd", "csrc", "upfold_kernels.hip")
+    assert re.search(r"#define MNET_UPF_RUN %d\b" % R.UPF_RUN, hip) and R.UPF_RUN == 8
+    upf = _body(hip, 'extern "C" int mnet_upfold3x3_nhwc', "MNET_LAUNCH_CHECK")
+    assert "((h + MNET_UPF_RUN - 1) / MNET_UPF_RUN) * 2 * w * (c / N)" in upf
+    assert "(per + 255) / 256 < %d ? (per + 255) / 256 : %d" % (R.UPF_CAP, R.UPF_CAP) in upf and "dim3(gx, n), dim3(256)" in upf
+    assert "(long long)h * w * (c / N) * 4 < (1ll << 31) && (long long)w * 9 * c < (1ll << 29)" in upf
+    assert "(NWG & 7u) == 0u" in hip and "id < items_per_image; id += gridDim.x * 256u" in hip
+    assert "y0 = (int)(col / (unsigned)W2) * R, y1 = min(y0 + R, H)" in hip
+
+
+def test_upfold_launch_mirror_on_known_shapes():
+    """worked out by hand from the launcher"""
+    assert R.upf_launch(2, 9, 6, 256, R.MX) == (2 * 12 * 32, 3, 1, False)             # two runs x 12 hi-res columns x 32 chunks: three workgroups per image
+    assert R.upf_launch(2, 16, 16, 256, R.MX) == (2 * 32 * 32, 8, 1, True)            # the generator's 16 -> 32 level, two glyphs
+    assert R.upf_launch(1, 32, 32, 256, R.MX) == (4 * 64 * 32, 32, 1, True)
+    assert R.upf_launch(3, 5, 7, 64, R.F32) == (14 * 16, 1, 1, False)
+    assert R.upf_launch(1, 8, 8192, 32, R.F16)[:3] == (16384 * 4, 256, 1)
+    assert R.upf_launch(1, 2, 65536, 32, R.MX)[:3] == (2048 * 256, 2048, 1) and R.upf_launch(1, 2, 65537, 32, R.MX)[:3] == (2048 * 256 + 8, 2048, 2)
+    assert [R.upf_runs(h) for h in (1, 7, 8, 9, 16, 17, 24)] == [(1, 1), (1, 7), (1, 8), (2, 1), (2, 8), (3, 1), (3, 8)]
+
+
+@pytest.mark.parametrize("dtype", R.STORAGES)
+def test_every_upfold_case_lands_in_its_regime(dtype):
+    for name, p in R.UPF_CASES:
+        assert R.UPF_REGIME[name](p, dtype), ("upfold3x3", name, p, R.upf_launch(*p, dtype), R.upf_runs(p[1]))
+        assert R.upf_guards_ok(*p, dtype) and p[3] % 32 == 0
+    name, shapes = R.UPF_CAP_CASE
+    p = shapes[dtype]
+    per, gx, trips, remap = R.upf_launch(*p, dtype)
+    assert R.UPF_REGIME[name](p, dtype), ("upfold3x3", name, p, (per, gx, trips, remap))
+    assert per == 524800 and 0 < per - gx * R.WG < gx * R.WG and remap            # a partial second trip, (gx * 1) % 8 == 0
+    assert p[2] * 9 * p[3] < 1 << 29 and p[1] * p[2] * (p[3] // R.vec_n(dtype)) * 4 < 1 << 31
+    assert {name for name, _ in R.UPF_CASES} | {R.UPF_CAP_CASE[0]} == set(R.UPF_REGIME)
+    hs = [p[1] for nm, p in R.UPF_CASES if nm.startswith("H%8=")]
+    assert sorted(h % 8 for h in hs) == list(range(8)) and {p[0] for nm, p in R.UPF_CASES if nm.startswith("H%8=")} == {3, 8}
+    assert [p[1] for nm, p in R.UPF_CASES if nm == "three runs"] == [17, 24] and [p[1] for nm, p in R.UPF_CASES if nm == "one run, H<8"] == [1, 2, 3, 7]
+    # the remap is on and off among the cases with several runs, and on in a case where the image alone has it off (the batch-invariance test)
+    assert any(R.upf_launch(*p, dtype)[3] and not R.upf_launch(1, *p[1:], dtype)[3] for _, p in R.UPF_CASES)
+
+
+HEADROOM = {}
+
+
+@pytest.mark.parametrize("dtype", R.STORAGES)
+def test_upfold_reference_headroom(dtype):
+    """what the bound of tests/test_kernels_gpu._check leaves to the kernel: fold_ref's formula evaluated in fp32 on the stored values and rounded ONCE to
+    the storage by the host packer lies within half the storage's bound (relative to max |ref|) of the fp64 fold_ref, on every small case with the
+    seed and the input scale the GPU tier uses — a kernel that sums in fp32 and rounds once has the other half for its own order of sums"""
+    import torch
+    from marconet_amd import packing as P
+    from tests.test_kernels_gpu import _tol, ALL_DTYPES
+    from tests.test_upfold import fold_f32, fold_input, fold_ref
+    tag = ALL_DTYPES[R.STORAGES.index(dtype)]
+    sdt = {R.F32: torch.float32, R.F16: torch.float16, R.SPLIT: P.SPLIT_DTYPE, R.MX: P.MX_DTYPE}[dtype]
+    worst = 0.0
+    for name, p in dict((p, (nm, p)) for nm, p in R.UPF_CASES).values():
+        zv = P.to_float(P.from_float(fold_input(p, 600, R.upf_z_scale(p)), sdt))                              # the values the storage holds, NHWC
+        z = zv.permute(0, 3, 1, 2).contiguous()
+        ref = fold_ref(z.double(), p[3])
+        got = P.to_float(P.from_float(fold_f32(z, p[3]).permute(0, 2, 3, 1).contiguous(), sdt)).permute(0, 3, 1, 2).double()
+        rel = (got - ref).abs().max().item() / ref.abs().max().item()
+        worst = max(worst, rel / _tol(tag))
+        assert rel <= 0.5 * _tol(tag), "%s %s %s: fp32 + one rounding is %.3e of max |ref|, bound %.1e" % (dtype, name, p, rel, _tol(tag))
+    print("upfold headroom %s: fp32 evaluation + one storage rounding uses at most %.3f of the bound" % (dtype, worst))
+
+
+def test_upfold_banded_reference_is_the_whole_map_reference():
+    """the two-trip map is compared in column bands (tests/test_upfold.fold_ref_banded): bands of 1, 2, 3, 5 columns and one band, with a band that ends at the
+    map's edge and one that is a single column, give fold_ref's fp64 values exactly"""
+    import torch
+    from tests.test_upfold import fold_ref, fold_ref_banded
+    for h, w in ((2, 11), (3, 1), (1, 2), (5, 7)):
+        z = torch.randn((2, 9 * 4, h, w), generator=torch.Generator().manual_seed(610 + w), dtype=torch.float64)
+        whole = fold_ref(z, 4)
+        for band in (1, 2, 3, 5, w, w + 3):
+            assert torch.equal(fold_ref_banded(z, 4, band), whole), (h, w, band)
+
+
+def test_upfold_refuses_maps_past_its_index_guards_without_a_device():
+    """the launcher's two "image too large" guards (32-bit element offsets inside a low-res row of z; 32-bit item index per image) answer MNET_E_ARG before
+    anything is enqueued — fake pointers, as tests/test_upfold.py::test_upfold_refuses_bad_arguments_without_a_device"""
+    import ctypes
+    from marconet_amd import _lib
+    lib = _lib.load()
+    buf = (ctypes.c_char * 4096)()
+    a = (ctypes.addressof(buf) + 127) // 128 * 128
+    z, y = ctypes.c_void_p(a), ctypes.c_void_p(a + 2048)
+    f = lib.mnet_upfold3x3_nhwc
+    for dt, n_ch in ((0, 4), (1, 8), (2, 8), (3, 8)):                       # MNET_F32, MNET_F16, MNET_F16X2, MNET_F16M
+        w_row = (1 << 29) // (9 * 32) + 1                                   # the first width with w * 9 * c >= 2^29 at c = 32
+        assert (w_row - 1) * 9 * 32 < 1 << 29 <= w_row * 9 * 32 and 1 * w_row * (32 // n_ch) * 4 < 1 << 31
+        assert f(z, y, dt, 1, 1, w_row, 32, None, None, 0, None, None) == -1
+        assert b"image too large" in lib.mnet_last_error()
+        h_big = (1 << 31) // (65536 * (32 // n_ch) * 4)                     # h * w * (c / N) * 4 == 2^31 exactly at w = 65536: the first refused height
+        assert h_big * 65536 * (32 // n_ch) * 4 == 1 << 31 and 65536 * 9 * 32 < 1 << 29
+        assert f(z, y, dt, 1, h_big, 65536, 32, None, None, 0, None, None) == -1
+        assert b"image too large" in lib.mnet_last_error()

@@ -19,17 +19,48 @@ def tap_planes(x, w):
     return F.conv2d(x, packing.tapconv_weight(w))
 
 
-def fold_ref(z, c):
-    """z [N,9·c,h,w] fp64 (channel t·c + o) → [N,c,2h,2w]: sum over the taps of the bilinear x2 of plane t, shifted by tap t, zero outside the hi-res map"""
+def _fold(z, c):
     n, c9, h, w = z.shape
-    assert c9 == 9 * c and z.dtype == torch.float64
+    assert c9 == 9 * c
     up = F.pad(F.interpolate(z, scale_factor=2, mode="bilinear", align_corners=False), (1, 1, 1, 1))
-    y = torch.zeros((n, c, 2 * h, 2 * w), dtype=torch.float64)
+    y = torch.zeros((n, c, 2 * h, 2 * w), dtype=z.dtype)
     for ky in range(3):
         for kx in range(3):
             t = 3 * ky + kx
             y += up[:, t * c:(t + 1) * c, ky:ky + 2 * h, kx:kx + 2 * w]
     return y
+
+
+def fold_ref(z, c):
+    """z [N,9·c,h,w] fp64 (channel t·c + o) → [N,c,2h,2w]: sum over the taps of the bilinear x2 of plane t, shifted by tap t, zero outside the hi-res map"""
+    assert z.dtype == torch.float64
+    return _fold(z, c)
+
+
+def fold_f32(z, c):
+    """fold_ref's formula evaluated in fp32 (what a correct fp32 kernel can at best hold before it rounds to its storage)"""
+    assert z.dtype == torch.float32
+    return _fold(z, c)
+
+
+def fold_ref_banded(z, c, band):
+    """fold_ref in bands of ``band`` low-res columns with a one-column halo on each side (maps whose padded up-sampled copy does not fit in memory): hi-res columns
+    2a ... 2b-1 read up-sampled columns 2a-1 ... 2b, i.e. low-res columns a-1 ... b; inside the halo the band's own clamp and zero padding are cut away, at the map's
+    edges they are the map's.  Equal to fold_ref bit for bit (the same products and the same order of sums per output)."""
+    n, _, h, w = z.shape
+    assert z.dtype == torch.float64 and band >= 1
+    y = torch.empty((n, c, 2 * h, 2 * w), dtype=torch.float64)
+    for a in range(0, w, band):
+        b = min(a + band, w)
+        lo, hi = max(a - 1, 0), min(b + 1, w)
+        y[:, :, :, 2 * a:2 * b] = fold_ref(z[:, :, :, lo:hi].contiguous(), c)[:, :, :, 2 * (a - lo):2 * (a - lo) + 2 * (b - a)]
+    return y
+
+
+def fold_input(p, seed, scale=1.5):
+    """random z [n,h,w,9c] fp32 NHWC for the map p = (n, h, w, c)"""
+    n, h, w, c = p
+    return torch.randn((n, h, w, 9 * c), generator=torch.Generator().manual_seed(seed)) * scale
 
 
 def epilogue_ref(v, out_scale=None, bias=None, act=3, post_scale=None):

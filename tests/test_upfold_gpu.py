@@ -12,6 +12,7 @@ errors are a few 1e-5 on outputs of magnitude 2: the ratio of two maxima over a 
     case 6  (2,16,16,512,256)  1.108  1.025  1.349
     heavy-tailed (case 6's shape, synthetic "trained"-regime weights, log-uniform style scales over three decades)  1.192  1.123  0.963
 K_END_TO_END = the largest of them, 1.965, + 0.25 for the unmeasured seeds.  The test runs seed 77."""
+import functools
 import os
 import re
 
@@ -19,8 +20,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.test_kernels_gpu import MX, _check
-from tests.test_upfold import epilogue_ref, fold_ref
+from tests import tail_regimes as R
+from tests.test_kernels_gpu import MX, SPLIT, _check, _tol
+from tests.test_upfold import epilogue_ref, fold_input, fold_ref, fold_ref_banded
 
 pytestmark = pytest.mark.gpu
 
@@ -32,7 +34,7 @@ CASES = [(2, 1, 1, 64, 32),                 # clamp and zero padding meet on eve
          (1, 1, 5, 64, 32),                 # the same on a one-row map
          (3, 5, 7, 64, 64),                 # odd, non-square, two channel blocks
          (2, 4, 4, 64, 32),                 # small square map
-         (2, RUN + 1, 6, 64, 256),          # a run boundary (the second run is one row), 2 x 6 x 32 = 384 items: two workgroups per image
+         (2, RUN + 1, 6, 64, 256),          # a run boundary (the second run is one row), 2 x 12 x 32 = 768 items: three workgroups per image
          (2, 16, 16, 512, 256)]             # a level's channel counts: the planner accepts
 IDS = ["%dx%dx%dx%dx%d" % c for c in CASES]
 K_END_TO_END = 1.965 + 0.25                 # see the module docstring
@@ -171,6 +173,184 @@ def test_one_glyph_alone_gives_its_batch_bytes(case):
                        post_scale=ps[1:2].contiguous().to(DEV))
     torch.cuda.synchronize()
     assert torch.equal(P.untag(yb[1:2]).contiguous().cpu().view(torch.uint8), P.untag(y1).cpu().view(torch.uint8))
+
+
+# ------------------------------------------------------------------------------------------------------------------ (g) every storage, every launch regime
+# The cases of tests/tail_regimes.py (UPF_CASES / UPF_CAP_CASE): each names the launch regime it is there for and asserts it before it launches.  z lies inside a
+# larger buffer whose other bytes are 0xFF — NaN in every storage — at least one low-res row and two pixels on each side, so a clamped index that leaves the
+# buffer puts a NaN into y; out_scale / bias / post_scale lie between NaN floats; y between 0xA5 bytes, which must stay.  Reference: fold_ref + epilogue_ref in fp64
+# of the stored values, through _check with the storage's own bound (test_tail_regimes.py::test_upfold_reference_headroom shows that half of it is free).
+DT = {R.F32: torch.float32, R.F16: torch.float16, R.SPLIT: SPLIT, R.MX: MX}
+ALL3 = ("out_scale", "bias", "post_scale")
+MIXES_REMAP = [(), ("out_scale",), ("bias",), ("post_scale",), ALL3]          # the vectors that are ABSENT
+MIXES = [(), ALL3]
+ACCEPTED = dict((s, 0) for s in R.STORAGES)                                    # launches the entry point accepted, per storage
+WORST = dict((s, 0.0) for s in R.STORAGES)                                     # worst error / bound, per storage
+
+
+def _sdt(dtype):
+    return {R.F32: torch.float32, R.F16: torch.float16, R.SPLIT: _P().SPLIT_DTYPE, R.MX: _P().MX_DTYPE}[dtype]
+
+
+def _esize(dtype):
+    return 2 if dtype == R.F16 else 4
+
+
+def _between(raw, guard, fill):
+    """a copy of the byte tensor ``raw`` (device or host) between ``guard`` bytes of ``fill`` on each side → (whole buffer, the view of the copy), on the device"""
+    assert guard % 128 == 0
+    buf = torch.full((raw.numel() + 2 * guard,), fill, dtype=torch.uint8, device=DEV)
+    buf[guard:guard + raw.numel()].copy_(raw)
+    return buf, buf[guard:guard + raw.numel()]
+
+
+def _z_guarded(stored, p, dtype):
+    """a stored z [n,h,w,9c] (host or device) → the same bytes on the device between 0xFF guards of at least one low-res row + two pixels, 128-byte aligned"""
+    n, h, w, c = p
+    guard = -(-((w + 2) * 9 * c * _esize(dtype)) // 128) * 128
+    buf, view = _between(_P().untag(stored).contiguous().view(torch.uint8).reshape(-1), guard, 0xFF)
+    z = _P().tag(view.view(_sdt(dtype)).reshape(n, h, w, 9 * c))
+    assert z.data_ptr() % 128 == 0 and z.data_ptr() == buf.data_ptr() + guard
+    return buf, z
+
+
+def _vec_guarded(t):
+    """an fp32 vector between 64 NaN floats on each side"""
+    if t is None:
+        return None
+    buf = torch.full((t.numel() + 128,), float("nan"), dtype=torch.float32, device=DEV)
+    buf[64:64 + t.numel()].copy_(t.reshape(-1))
+    return buf[64:64 + t.numel()].view(t.shape)
+
+
+def _y_guarded(p, dtype):
+    n, h, w, c = p
+    nbytes, guard = n * 4 * h * w * c * _esize(dtype), 512
+    buf = torch.full((nbytes + 2 * guard,), 0xA5, dtype=torch.uint8, device=DEV)
+    return buf, guard, _P().tag(buf[guard:guard + nbytes].view(_sdt(dtype)).reshape(n, 2 * h, 2 * w, c))
+
+
+def _y_guards_intact(buf, guard):
+    return bool((buf[:guard] == 0xA5).all().item()) and bool((buf[-guard:] == 0xA5).all().item())
+
+
+@functools.lru_cache(maxsize=4)
+def _small_operands(p, dtype):
+    """→ (stored z on the host, fp64 sums [n,c,2h,2w] of the values it holds, the three vectors): one pass through the HOST packer; computed once per (case, storage)"""
+    s = _P().from_float(fold_input(p, 600, R.upf_z_scale(p)), _sdt(dtype))
+    sums = fold_ref(_nchw(_P().to_float(s)).double().contiguous(), p[3])
+    return s, sums, _vectors(p[0], p[3], 601)
+
+
+def _compare(name, dtype, got, ref, ybuf, guard):
+    """got / ref NCHW: no NaN (a read outside z), the storage's bound, the guards of y"""
+    assert not bool(torch.isnan(got).any()), "%s: NaN in y — the kernel read a guard byte around z or a vector" % name
+    ratio = (got.double() - ref).abs().max().item() / (_tol(DT[dtype]) * max(ref.abs().max().item(), 1e-6))
+    ACCEPTED[dtype] += 1
+    WORST[dtype] = max(WORST[dtype], ratio)
+    print("upfold %-5s accepted launches %3d   this error / bound %.3f   worst so far %.3f" % (dtype, ACCEPTED[dtype], ratio, WORST[dtype]))
+    _check(name, got, ref, DT[dtype], extra=1.0)
+    assert _y_guards_intact(ybuf, guard), "%s: guard bytes around y were written" % name
+
+
+def _run_small(regime, p, dtype, mixes, act):
+    ops = _ops()
+    s, sums, vec = _small_operands(tuple(p), dtype)
+    zbuf, z = _z_guarded(s, p, dtype)
+    for absent in mixes:
+        v = dict(zip(ALL3, vec))
+        for k in absent:
+            v[k] = None
+        ybuf, guard, y = _y_guarded(p, dtype)
+        r = ops.upfold3x3(z, p[3], act=act, out=y, **{k: _vec_guarded(None if t is None else t.to(DEV)) for k, t in v.items()})
+        torch.cuda.synchronize()
+        assert r is y
+        ref = epilogue_ref(sums, v["out_scale"], v["bias"], act, v["post_scale"])
+        _compare("upfold %s %s %s act %d without %s" % (regime, p, dtype, act, "+".join(absent) or "nothing"), dtype, _nchw(_host(y)), ref, ybuf, guard)
+    assert bool((zbuf[:z.data_ptr() - zbuf.data_ptr()] == 0xFF).all().item())
+
+
+UPF_IDS = ["%s-%dx%dx%dx%d" % ((nm.replace(" ", "_").replace(",", ""),) + p) for nm, p in R.UPF_CASES]
+
+
+@pytest.mark.parametrize("dtype", R.STORAGES)
+@pytest.mark.parametrize("case", R.UPF_CASES, ids=UPF_IDS)
+def test_fold_launch_regimes_match_fp64(case, dtype):
+    """upfold_kernel<T> of every storage with several workgroups per image: the XCD-aware order on and off (all three vectors, each one absent, none), H % RUN =
+    0 ... 7 with two runs, three runs, one run (H < RUN, H = RUN: both edges in one full run), W = 1 (every column clamps on both sides) and W = 2"""
+    regime, p = case
+    assert R.UPF_REGIME[regime](p, dtype), (regime, R.upf_launch(*p, dtype), R.upf_runs(p[1]))
+    _run_small(regime, p, dtype, MIXES_REMAP if regime.startswith("several workgroups") else MIXES, _ops().ACT_LRELU_SQRT2)
+
+
+@pytest.mark.parametrize("dtype", R.STORAGES)
+@pytest.mark.parametrize("act", [0, 2, 3])
+def test_fold_activation_arms_on_every_storage(act, dtype):
+    regime, p = R.UPF_CASES[10]                                                 # three runs, remap off
+    assert R.UPF_REGIME[regime](p, dtype)
+    _run_small(regime, p, dtype, [()], act)
+
+
+@functools.lru_cache(maxsize=2)
+def _cap_source(p):
+    return fold_input(p, 620)
+
+
+@pytest.mark.parametrize("dtype", R.STORAGES)
+def test_fold_second_grid_stride_trip(dtype):
+    """more than 2048 x 256 (chunk, hi-res column, run) items in one image: the capped grid makes a second, partial trip, with the XCD remap of the workgroup index
+    (2048 % 8 == 0).  z (151 MB in the 4-byte storages) is encoded and decoded by mnet_convert on the device (its codec has tests of its own:
+    test_tail_kernels_gpu.py::test_convert_second_grid_stride_trip); the fp64 reference is evaluated in column bands (tests/test_tail_regimes.py checks it equal to the whole-map one)"""
+    ops, P = _ops(), _P()
+    regime, shapes = R.UPF_CAP_CASE
+    p = shapes[dtype]
+    assert R.UPF_REGIME[regime](p, dtype), R.upf_launch(*p, dtype)
+    n, h, w, c = p
+    src = _cap_source(p).to(DEV)
+    zd = src if dtype == R.F32 else ops.convert(src, _sdt(dtype))
+    zv = (zd if dtype == R.F32 else ops.convert(zd, torch.float32)).cpu()
+    zbuf, z = _z_guarded(zd, p, dtype)
+    del src, zd
+    sums = fold_ref_banded(_nchw(zv).double().contiguous(), c, 8200)
+    del zv
+    vec = _vectors(n, c, 621)
+    for absent in MIXES:
+        v = dict(zip(ALL3, vec))
+        for k in absent:
+            v[k] = None
+        ybuf, guard, y = _y_guarded(p, dtype)
+        ops.upfold3x3(z, c, act=ops.ACT_LRELU_SQRT2, out=y, **{k: _vec_guarded(None if t is None else t.to(DEV)) for k, t in v.items()})
+        torch.cuda.synchronize()
+        got = (y if dtype == R.F32 else ops.convert(y, torch.float32)).float().cpu()
+        ref = epilogue_ref(sums, v["out_scale"], v["bias"], 3, v["post_scale"])
+        # the second trip's items are the last of the image: hi-res columns first2 ... of both rows of the (only) run
+        first2 = R.UPF_CAP * R.WG // (c // R.vec_n(dtype))
+        e2 = (_nchw(got).double() - ref)[:, :, :, first2:].abs().max().item()
+        assert first2 < 2 * w and e2 <= _tol(DT[dtype]) * ref.abs().max().item(), "second trip (hi-res columns %d ...): %.3e" % (first2, e2)
+        _compare("upfold %s %s %s without %s" % (regime, p, dtype, "+".join(absent) or "nothing"), dtype, _nchw(got), ref, ybuf, guard)
+        del got, ref, y, ybuf
+
+
+BATCH_CASES = [R.UPF_CASES[3], R.UPF_CASES[10]]        # (8, 9, 24, 64): the batch has the remap on, one image alone has it off; (3, 17, 24, 64): off in both, three runs
+
+
+@pytest.mark.parametrize("dtype", R.STORAGES)
+@pytest.mark.parametrize("case", BATCH_CASES, ids=["remap_on_in_the_batch_only", "three_runs"])
+def test_one_glyph_alone_gives_its_batch_bytes_on_every_storage(case, dtype):
+    ops, P = _ops(), _P()
+    regime, p = case
+    n, h, w, c = p
+    assert R.UPF_REGIME[regime](p, dtype) and not R.upf_launch(1, h, w, c, dtype)[3]
+    assert R.upf_launch(*p, dtype)[3] == (case is BATCH_CASES[0])
+    s, _, (os_, bs, ps) = _small_operands(tuple(p), dtype)
+    zd = s.to(DEV)
+    raw = lambda t: P.untag(t).contiguous().cpu().view(torch.uint8)
+    yb = ops.upfold3x3(zd, c, out_scale=os_.to(DEV), bias=bs.to(DEV), act=ops.ACT_LRELU_SQRT2, post_scale=ps.to(DEV))
+    for i in (0, 1, n - 1):
+        y1 = ops.upfold3x3(zd[i:i + 1].contiguous(), c, out_scale=os_[i:i + 1].contiguous().to(DEV), bias=bs.to(DEV), act=ops.ACT_LRELU_SQRT2,
+                           post_scale=ps[i:i + 1].contiguous().to(DEV))
+        torch.cuda.synchronize()
+        assert torch.equal(raw(yb[i:i + 1]), raw(y1)), "image %d of %s in %s" % (i, p, dtype)
 
 
 # ------------------------------------------------------------------------------------------------------------------ (e) refused launches
