@@ -193,7 +193,14 @@ enum { MNET_CONV_ALGO_AUTO = 0, MNET_CONV_ALGO_REG_STAGED = 1, MNET_CONV_ALGO_LD
                                              * MNET_F16M, one source, C % 32 == 0, h, w >= 4, w % 32 == 0, no residual / scale vectors / valid_w,
                                              * and only on the LDS-DMA builds that carry the mode (AUTO picks one; ids 10, 15, 16): MNET_E_ARG
                                              * otherwise, nothing enqueued. */,
-       MNET_CONV_ALGO_FLAGS = 256 | 512 | 1024 };
+       MNET_CONV_ALGO_FLAG_F32_OUT = 2048 /* OR-ed in: fp32 output of an MNET_F16M launch — x0 / x1 / wgt in fp16+8 as always, y is a plain fp32 [n,ho,wo,cout]
+                                            * tensor (128-byte aligned; the same 4 bytes per element) that holds the value the fp16+8 launch would encode, before
+                                            * its rounding: an intermediate with one reader (the tap planes of mnet_upfold3x3_f32z_nhwc, marconet_hip_upfold_f32.h)
+                                            * pays neither the encode nor the decode.  Accepted only with no bias, no out_scale / post_scale, no residual, no
+                                            * gn_partial, no valid_w, no input transform, act = MNET_ACT_NONE, and only where the launch resolves to the one-wave
+                                            * tile (LDS-DMA id 16: AUTO names it whatever the launch size; ho * wo % 32 == 0, <= 512 k-slabs): MNET_E_ARG
+                                            * otherwise, from mnet_conv2d_plan as from the launch, nothing enqueued. */,
+       MNET_CONV_ALGO_FLAGS = 256 | 512 | 1024 | 2048 };
 int mnet_conv2d_nhwc_ex(const mnet_conv_desc* d, int32_t algo, void* stream);
 
 /* split-K form of the skinny kernel for a "patchify" conv (filter == stride, no padding; fp32; <= 512 output pixels) — the

@@ -1,7 +1,7 @@
 /* marconet_hip_upfold.h — the one entry point libmarconet_hip.so exports beside the table of marconet_hip.h (C-ABI version 4, which that header and its
  * 43 entry points define and which stays as it is): an up-sampling 3x3 convolution's second half.  Plain C, like marconet_hip.h; same rules — the caller owns
  * every buffer, a call only enqueues work on the given stream, returns 0 or a negative MNET_E_*, message via mnet_last_error().
- * ctypes binding: marconet_amd/_lib.py, UPFOLD_SYMBOLS. */
+ * ctypes binding: marconet_amd/_lib.py, UPFOLD_SYMBOLS.  (The same fold with its tap planes in fp32: marconet_hip_upfold_f32.h.) */
 #ifndef MARCONET_HIP_UPFOLD_H
 #define MARCONET_HIP_UPFOLD_H
 

@@ -15,6 +15,7 @@ ACT_NONE, ACT_RELU, ACT_LRELU, ACT_LRELU_SQRT2, ACT_TANH, ACT_GELU, ACT_SIGMOID 
 ALGO_AUTO, ALGO_REG_STAGED, ALGO_LDS_DMA, ALGO_SKINNY, ALGO_DMA_CFG0, ALGO_STRIP_CFG0, ALGO_DMA_CFG16, ALGO_FLAG_ONE_TILE = 0, 1, 2, 3, 16, 32, 64, 256
 ALGO_FLAG_X1_CENTER = 512     # x1 contributes through the filter's centre tap only (a 1x1 skip conv folded into the k-loop)
 ALGO_FLAG_SHUFFLE2 = 1024     # pixel-shuffle output mode: conv3x3(bilinear x2) in polyphase form (cout = 4 C phase-major, y = [n,2h,2w,C])
+ALGO_FLAG_F32_OUT = 2048      # fp32 output of an fp16+8 launch (the one-wave tile's plain epilogue only): the tap planes of an up-conv, which only the fold reads
 
 c_int, c_void_p, c_float, c_double, c_i64 = ctypes.c_int32, ctypes.c_void_p, ctypes.c_float, ctypes.c_double, ctypes.c_int64
 
@@ -161,6 +162,11 @@ UPFOLD_SYMBOLS = {
     "mnet_upfold3x3_nhwc": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
 }
 
+# ... and the one include/marconet_hip_upfold_f32.h declares (the fold with its tap planes in fp32)
+UPFOLD_F32Z_SYMBOLS = {
+    "mnet_upfold3x3_f32z_nhwc": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+}
+
 _lib = None
 
 
@@ -178,7 +184,7 @@ def load():
             "marconet_amd: %s not found — build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or marconet_amd/csrc/build.sh (there is no CPU/eager fallback)" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(UPFOLD_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(UPFOLD_SYMBOLS.items()) + list(UPFOLD_F32Z_SYMBOLS.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is absent
         fn.restype = res
         fn.argtypes = args

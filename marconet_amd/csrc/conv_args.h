@@ -15,9 +15,10 @@ struct ConvArgs {
     int split;               // MNET_F16X2 launch: c0 / c1 / cin / K are PHYSICAL (f16 view with twice the channels: per 32-channel block 32 hi
                              // halves then 32 lo halves); cout stays logical; the epilogue multiplies the accumulator by 2^-8 and stores hi/lo
     int mx_fetch_pad;        // fp16+8 launches, A/B knob (env MNET_MX_FETCH_PAD=1): also fetch the padding chunk 7 of every activation block (whole 128-byte lines)
-    // (two host-side values in ONE int, read by the launchers only: the block's layout — to which the 256-VGPR tiles' register allocation is sensitive, see below — is unchanged)
+    // (three host-side values in ONE int, read by the launchers only: the block's layout — to which the 256-VGPR tiles' register allocation is sensitive, see below — is unchanged)
     int one_tile_per_wg : 16;     // A/B knob (MNET_CONV_ALGO_FLAG_ONE_TILE): grid = #tiles instead of a persistent grid
-    int shuffle2 : 16;            // MNET_CONV_ALGO_FLAG_SHUFFLE2: cout = 4 C phase-major, y is [N,2H,2W,C] — which BUILD runs (the pixel-shuffle output mode of the fp16+8 LDS-DMA epilogues)
+    int shuffle2 : 8;             // MNET_CONV_ALGO_FLAG_SHUFFLE2: cout = 4 C phase-major, y is [N,2H,2W,C] — which BUILD runs (the pixel-shuffle output mode of the fp16+8 LDS-DMA epilogues)
+    int f32_out : 8;              // MNET_CONV_ALGO_FLAG_F32_OUT: y is fp32 [N,Ho,Wo,cout] — which BUILD runs (conv_dma_w4_f32.hip, the only one with the mode)
     int x1_center;           // MNET_CONV_ALGO_FLAG_X1_CENTER: the second source is walked at the centre tap only (LDS-DMA kernels: ktiles = taps * c0 / 64 + c1 / 64,
     int center_tap, center_tpx;   //   physical channels); its tap index kh/2 * kw + kw/2 and input-pixel offset kh/2 * w + kw/2 relative to tap 0
     int howo_shift, wo_shift;     // log2 of ho * wo / of wo when they are powers of two, else -1 (LDS-DMA kernels: the per-tile set-up divides by them, set by the launcher)
@@ -36,6 +37,7 @@ int launch_conv_dma(const ConvArgs& a, hipStream_t st, int id);
 // conv_dma_w4.hip (fp16+8 256x256 tile, one wave per SIMD, accumulators in the accumulator file: fp16+8 LDS-DMA id 16)
 int launch_conv_dma_w4(const ConvArgs& a, hipStream_t st);
 int launch_conv_dma_w4_shuf(const ConvArgs& a, hipStream_t st);   // conv_dma_w4_shuf.hip: its builds with the SHUFFLE2 output mode
+int launch_conv_dma_w4_f32(const ConvArgs& a, hipStream_t st);    // conv_dma_w4_f32.hip: its plain build with the F32_OUT output mode
 
 // conv_strip_dma.hip (3x3 / stride 1: one activation strip per filter row)
 int launch_conv_strip(const ConvArgs& a, hipStream_t st, int cfg);

@@ -35,6 +35,12 @@
 #ifndef W4_STAMPS
 #define W4_STAMPS 0
 #endif
+//   W4_F32_DIRECT (0)   A/B, the fp32-output build (conv_dma_w4_f32.hip) only: a step's 32 floats as eight 16-byte stores per lane straight from the registers instead of whole
+//                       half-lines through the wave's LDS scratch.  Measured on the tap convs of the generator's up-convs (1024 glyphs: 16x16x512 -> 4608, 32x32x512 -> 2304):
+//                       3.03 / 5.95 ms against 2.67 / 5.16 ms through the LDS (and 2.78 / 5.29 ms for the fp16+8 build): every store instruction touches 64 lines
+#ifndef W4_F32_DIRECT
+#define W4_F32_DIRECT 0
+#endif
 //   W4_ACT_FIRST (0)    A/B: the activation pieces (HBM / L2) behind the first 8 scaled MFMAs, the weight pieces (L2-resident) behind the last 8
 #ifndef W4_ACT_FIRST
 #define W4_ACT_FIRST 0
@@ -95,7 +101,11 @@ static_assert(FA * FB == NDMA, "one DMA piece behind each scaled MFMA");
 // sums' mask (the low-res border ring instead of valid_w) change.  Every store stays an unconditional raw buffer store: the descriptor's window runs from phase (0,0) of
 // the tile's first pixel to phase (1,1) of its last valid one (a 256-pixel run of low-res pixels and the second hi-res row of its phases: 32-bit offsets); a hi-res index is
 // not monotonic in the low-res pixel across phases, so a pixel >= npix gets the out-of-range offset explicitly.
-template <bool SC, bool RG, bool SHUF = false, typename ACC, typename STAMP>
+// F32: the MNET_CONV_ALGO_FLAG_F32_OUT output mode — a build of its own (conv_dma_w4_f32.hip), plain epilogue only (no vector, no residual, no sums, no activation: the
+// planner refuses everything else).  A step's v[32] — the 32 channels of one block of one pixel, which in fp32 IS one 128-byte line — is stored as it stands, at the byte
+// offset the fp16+8 build gives the block's line: no conversion, no block maximum, no lo bytes.  The stores are whole half-lines through the wave's LDS scratch — the
+// fp16+8 build's two transposition rounds with 16 floats per lane and round in the place of the encoded pieces, 4 lanes per 64 contiguous bytes (W4_F32_DIRECT: the A/B form).
+template <bool SC, bool RG, bool SHUF = false, bool F32 = false, typename ACC, typename STAMP>
 __device__ __forceinline__ void w4_epilogue(const ConvArgs& p_, const ACC& acc, int co0, int pix0, int wc, int wp, int lane, unsigned char* xpose, unsigned char* par, STAMP&& stamp) {
 #pragma clang fp contract(off)      // every product and sum rounded on its own, as in dma_epilogue_mx — whose runtime arms keep hipcc from fusing across them; in this straight-line
                                     // form it fused scale * acc + bias into an fma
@@ -220,7 +230,7 @@ __device__ __forceinline__ void w4_epilogue(const ConvArgs& p_, const ACC& acc, 
         //  a NaN stays a NaN, -inf stays -inf; ReLU keeps act_apply_vec's form, whose relu(-inf) = NaN is wanted)
         //  the launcher hands every other activation to the 8-wave tile: ONE in-place arm here, no second producer of v — hipcc copied all 32 values at the join of two.
         //  v_max_f32 written out: fmaxf() adds a canonicalising v_max v, v, v per value)
-        if (p.act != MNET_ACT_NONE) {
+        if (!F32 && p.act != MNET_ACT_NONE) {
             const float post = p.act == MNET_ACT_LRELU_SQRT2 ? 1.41421356237309515f : 1.f;
 #pragma unroll
             for (int q = 0; q < 32; q += 2) {
@@ -242,6 +252,44 @@ __device__ __forceinline__ void w4_epilogue(const ConvArgs& p_, const ACC& acc, 
         if (GN && gnp) {
 #pragma unroll
             for (int q = 0; q < 32; ++q) { gs1 += v[q]; gs2 = fmaf(v[q], v[q], gs2); }
+        }
+        if constexpr (F32) {
+            static_assert(!F32 || (!SC && !RG && !SHUF), "fp32 output: the plain build only");
+            Step nxt = cur;
+            if (t + 1 < NS) request(t + 1, nxt);                           // (addresses only: this build has no parameter loads)
+            const unsigned L = (unsigned)lane;
+            if constexpr (W4_F32_DIRECT != 0) {
+                const unsigned off = (unsigned)((pix - pix0) * p.cout * 4 + (co[b] >> 5) * 128);      // (pixels >= npix lie beyond the descriptor's num_records)
+                const bool in = co[b] < p.cout;
+#pragma unroll
+                for (int c = 0; c < 8; ++c)
+                    __builtin_amdgcn_raw_buffer_store_b128(bitcast<u32x4>(f32x4{v[4 * c], v[4 * c + 1], v[4 * c + 2], v[4 * c + 3]}), ry, (int)(in ? off + 16u * c : OOB), 0, 0);
+            } else {
+                const unsigned wsw = (L >> 1) & 3u, j = L & 3u;
+#pragma unroll
+                for (int half = 0; half < 2; ++half) {                     // channels 16 half ... 16 half + 15 of the block: bytes [64 half, 64 half + 64) of its line
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+                        *reinterpret_cast<f32x4*>(xpose + ((4u * L + ((unsigned)c ^ wsw)) << 4)) = f32x4{v[16 * half + 4 * c], v[16 * half + 4 * c + 1], v[16 * half + 4 * c + 2], v[16 * half + 4 * c + 3]};
+                    u32x4 piece[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const unsigned P = (L >> 2) + 16u * k;              // the lane whose line this lane helps to write
+                        piece[k] = *reinterpret_cast<const u32x4*>(xpose + ((4u * P + (j ^ ((P >> 1) & 3u))) << 4));
+                    }
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) asm volatile("" : "+v"(piece[k]));   // all four reads in flight
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const unsigned P = (L >> 2) + 16u * k;
+                        const int ppix = pixb + (int)(P & 31u), pco = cob[b] + (int)(P >> 5) * 32;
+                        const unsigned off = (unsigned)((ppix - pix0) * p.cout * 4 + (pco >> 5) * 128 + half * 64) + j * 16u;
+                        __builtin_amdgcn_raw_buffer_store_b128(piece[k], ry, (int)(pco < p.cout ? off : OOB), 0, 0);
+                    }
+                }
+            }
+            cur = nxt;
+            continue;
         }
         f16x8 hh[4];
         float m32 = 0.f;
@@ -321,7 +369,7 @@ __device__ __forceinline__ void w4_epilogue(const ConvArgs& p_, const ACC& acc, 
     }
 }
 
-template <bool SC, bool RG, bool SHUF>
+template <bool SC, bool RG, bool SHUF, bool F32 = false>
 __device__ __forceinline__ void conv_dma_w4_body(const ConvArgs& p) {
     using namespace w4;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -650,7 +698,7 @@ __device__ __forceinline__ void conv_dma_w4_body(const ConvArgs& p) {
         tile_coords(v, co0, pix0);
         mfma_drain();
         // (W4_STAMPS == 2: slots 7-12 = per tile: first request | per step, summed: arithmetic + encode | next step's requests | LDS round + stores 1 | 2 | GroupNorm fold)
-        w4_epilogue<SC, RG, SHUF>(p, AccFile{acc}, co0, pix0, wc, wp, lane, xpose, smem + STAGES * STAGE + NW * XB + wave * PB,
+        w4_epilogue<SC, RG, SHUF, F32>(p, AccFile{acc}, co0, pix0, wc, wp, lane, xpose, smem + STAGES * STAGE + NW * XB + wave * PB,
                           [&](int i) __attribute__((always_inline)) { if constexpr (W4_STAMPS == 2) ph_stamp(i); });
     };
 
@@ -719,7 +767,12 @@ __device__ __forceinline__ void conv_dma_w4_body(const ConvArgs& p) {
     }
 }
 
-#ifndef MNET_W4_SHUF_TU
+#if defined(MNET_W4_F32_TU)
+// conv_dma_w4_f32.hip: the plain build with the MNET_CONV_ALGO_FLAG_F32_OUT output mode (such a launch has no scale vectors, no residual and no sums)
+template <bool SC, bool RG>
+__global__ void __launch_bounds__(256, 1) conv_dma_w4_f32_kernel(const ConvArgs p) { static_assert(!SC && !RG, "fp32 output: the plain build only"); conv_dma_w4_body<SC, RG, false, true>(p); }
+#define W4_KERNEL(SC, RG) conv_dma_w4_f32_kernel<SC, RG>
+#elif !defined(MNET_W4_SHUF_TU)
 template <bool SC, bool RG>
 __global__ void __launch_bounds__(256, 1) conv_dma_w4_kernel(const ConvArgs p) { conv_dma_w4_body<SC, RG, false>(p); }
 #define W4_KERNEL(SC, RG) conv_dma_w4_kernel<SC, RG>
@@ -743,7 +796,9 @@ static int launch_w4(const ConvArgs& b, int grid, hipStream_t st) {
     return MNET_OK;
 }
 
-#ifdef MNET_W4_SHUF_TU
+#if defined(MNET_W4_F32_TU)
+int launch_conv_dma_w4_f32(const ConvArgs& a, hipStream_t st) {
+#elif defined(MNET_W4_SHUF_TU)
 int launch_conv_dma_w4_shuf(const ConvArgs& a, hipStream_t st) {
 #else
 int launch_conv_dma_w4(const ConvArgs& a, hipStream_t st) {
@@ -760,7 +815,11 @@ int launch_conv_dma_w4(const ConvArgs& a, hipStream_t st) {
     if (grid > lim && !a.one_tile_per_wg && !env_one_tile) grid = lim & ~7;
     // (a launch this tile is not built for never gets here: conv_resolve hands it to id 15)
     const bool sc = a.out_scale || a.post_scale, rg = a.res || a.gn_partial;
-#ifdef MNET_W4_SHUF_TU
+#if defined(MNET_W4_F32_TU)
+    if (sc || rg || a.bias || a.valid_w || a.act != MNET_ACT_NONE)      // (conv_prepare refuses it first)
+        return mnet_fail(MNET_E_ARG, "conv: a MNET_CONV_ALGO_FLAG_F32_OUT launch has no bias, scale vector, residual, GroupNorm sums, valid_w or activation");
+    return launch_w4<false, false>(b, grid, st);
+#elif defined(MNET_W4_SHUF_TU)
     if (sc || a.res) return mnet_fail(MNET_E_ARG, "conv: a MNET_CONV_ALGO_FLAG_SHUFFLE2 launch has no scale vectors and no residual");      // (conv_resolve refuses it first)
     return rg ? launch_w4<false, true>(b, grid, st) : launch_w4<false, false>(b, grid, st);
 #else

@@ -514,6 +514,7 @@ static int conv_prepare(const mnet_conv_desc* d, int32_t algo, ConvArgs& a) {
     a.mx_fetch_pad = env_fetch_pad;
     a.x1_center = (algo & MNET_CONV_ALGO_FLAG_X1_CENTER) ? 1 : 0;
     a.shuffle2 = (algo & MNET_CONV_ALGO_FLAG_SHUFFLE2) ? 1 : 0;
+    a.f32_out = (algo & MNET_CONV_ALGO_FLAG_F32_OUT) ? 1 : 0;
     algo &= ~MNET_CONV_ALGO_FLAGS;
     MNET_CHECK_ARG((algo >= 0 && algo <= 3) || (algo >= MNET_CONV_ALGO_DMA_CFG0 && algo < MNET_CONV_ALGO_DMA_CFG0 + 16) ||
                    (algo >= MNET_CONV_ALGO_STRIP_CFG0 && algo < MNET_CONV_ALGO_STRIP_CFG0 + 3) ||
@@ -577,6 +578,13 @@ static int conv_prepare(const mnet_conv_desc* d, int32_t algo, ConvArgs& a) {
         MNET_CHECK_ARG(!d->residual && !d->out_scale && !d->post_scale && !d->valid_w && !d->in_scale,
                        "conv: MNET_CONV_ALGO_FLAG_SHUFFLE2 takes no residual, no scale vectors and no valid_w");
         MNET_CHECK_ARG((1024ll + 2ll * d->w + 2) * d->cout < 0x7fffffffLL, "conv: MNET_CONV_ALGO_FLAG_SHUFFLE2: map too wide");
+    }
+    if (a.f32_out) {
+        // fp32 output of an fp16+8 conv: the accumulator's value as it stands (the tap planes of an up-conv, which only the fold reads) — the plain epilogue only
+        MNET_CHECK_ARG(d->dtype == MNET_F16M && !a.shuffle2, "conv: MNET_CONV_ALGO_FLAG_F32_OUT needs MNET_F16M storage (and not MNET_CONV_ALGO_FLAG_SHUFFLE2)");
+        MNET_CHECK_ARG(!d->bias && !d->out_scale && !d->post_scale && !d->residual && !d->gn_partial && !d->valid_w && !d->in_scale,
+                       "conv: MNET_CONV_ALGO_FLAG_F32_OUT takes no bias, no scale vectors, no residual, no gn_partial and no valid_w");
+        MNET_CHECK_ARG(d->act == MNET_ACT_NONE, "conv: MNET_CONV_ALGO_FLAG_F32_OUT takes no activation (act %d)", d->act);
     }
     if (a.x1_center) {
         MNET_CHECK_ARG(d->x1 && d->c1 > 0 && (d->kh & 1) && (d->kw & 1) && d->stride_h == 1 && d->stride_w == 1 &&
@@ -754,6 +762,12 @@ static int conv_request(const mnet_conv_desc* d, int32_t algo, const ConvArgs& a
             return mnet_fail(MNET_E_ARG, "conv: MNET_CONV_ALGO_FLAG_SHUFFLE2 needs a launch the LDS-DMA kernel takes");
         return algo >= MNET_CONV_ALGO_DMA_CFG0 ? algo : dma_algo(conv_shuffle_pick(a));
     }
+    if (a.f32_out) {            // only the one-wave fp16+8 tile (LDS-DMA id 16) has a build that stores fp32.  AUTO names it whatever the launch size: whether a layer takes the
+                                // form must not depend on the batch (conv_resolve refuses a launch that id 16 hands over)
+        if (!dma_ok || algo == MNET_CONV_ALGO_REG_STAGED || algo == MNET_CONV_ALGO_SKINNY || (algo >= MNET_CONV_ALGO_STRIP_CFG0 && algo < MNET_CONV_ALGO_DMA_CFG16))
+            return mnet_fail(MNET_E_ARG, "conv: MNET_CONV_ALGO_FLAG_F32_OUT needs a launch the LDS-DMA kernel takes");
+        return algo >= MNET_CONV_ALGO_DMA_CFG0 ? algo : dma_algo(16);
+    }
     if (a.x1_center) {          // only the LDS-DMA kernels walk the second source at one tap
         if (!dma_ok || algo == MNET_CONV_ALGO_REG_STAGED || algo == MNET_CONV_ALGO_SKINNY || (algo >= MNET_CONV_ALGO_STRIP_CFG0 && algo < MNET_CONV_ALGO_DMA_CFG16))
             return mnet_fail(MNET_E_ARG, "conv: MNET_CONV_ALGO_FLAG_X1_CENTER needs a launch the LDS-DMA kernel takes");
@@ -792,6 +806,8 @@ static int conv_resolve(const mnet_conv_desc* d, int32_t algo, const ConvArgs& a
     int id = dma_id(k);
     if (id >= 0) {
         id = dma_handover(id, a);
+        if (a.f32_out && id != 16)
+            return mnet_fail(MNET_E_ARG, "conv: MNET_CONV_ALGO_FLAG_F32_OUT needs the one-wave fp16+8 tile (LDS-DMA id 16); this launch resolves to id %d", id);
         if (!conv_dma_launcher(id, a)) return MNET_E_ARG;      // no build of this id for the storage type (message set)
         k = dma_algo(id);
     }

@@ -940,6 +940,11 @@ static DmaLaunchFn no_form(const char* fmt, int id) {
 
 DmaLaunchFn conv_dma_launcher(int id, const ConvArgs& a) {
     static const bool allow_diag = [] { const char* e = getenv("MNET_ALLOW_DIAGNOSTIC_KERNELS"); return e && atoi(e) != 0; }();
+    if (a.f32_out) {    // MNET_CONV_ALGO_FLAG_F32_OUT: one build carries the mode — the one-wave tile's plain epilogue (conv_resolve refuses a launch that resolves elsewhere)
+        if (a.split != 2) return no_form("conv: MNET_CONV_ALGO_FLAG_F32_OUT needs fp16+8 storage (LDS-DMA id %d)", id);
+        if (id != 16) return no_form("conv: LDS-DMA tile configuration %d has no build with the MNET_CONV_ALGO_FLAG_F32_OUT output mode (the one-wave tile, id 16, has)", id);
+        return launch_conv_dma_w4_f32;
+    }
     if (a.shuffle2) {   // MNET_CONV_ALGO_FLAG_SHUFFLE2: the builds that carry the output mode — every id conv_shuffle_pick (conv_igemm.hip) can name, at any batch
         if (a.split != 2) return no_form("conv: MNET_CONV_ALGO_FLAG_SHUFFLE2 needs fp16+8 storage (LDS-DMA id %d)", id);
         switch (id) {

@@ -17,19 +17,46 @@
 //   i = 0:   P = (1/4 H1(0), 1/4 H0(0)), C's even row loses 1/4 H0          i = h-1:   N = (1/4 H2(h-1), 1/4 H1(h-1)), C's odd row loses 1/4 H2
 // Every output is summed as (P + C) + N by the one thread that owns it, in fp32, whatever the batch or the grid: one glyph alone gives the bytes it gives in a batch.
 // Storage: the readers / writers of common.h; a quad of lanes holds the four chunks of one 32-channel block of one pixel (cpp % 4 == 0, linear thread -> chunk map).
+// upfold_kernel<TZ, TY>: z and y in the same storage (mnet_upfold3x3_nhwc, all four), or z in fp32 under a y in fp16+8 (mnet_upfold3x3_f32z_nhwc): Z is an intermediate
+// that only this kernel reads and fp16+8 costs fp32's 4 bytes per element, so the tap conv writes the planes in fp32 (MNET_CONV_ALGO_FLAG_F32_OUT) and a loaded chunk is
+// already the decoded value — the same thread map, the same sums in the same order, one rounding (of Z to the storage) less.
 #include "common.h"
-#include "../../include/marconet_hip_upfold.h"
+#include "../../include/marconet_hip_upfold_f32.h"
 
 #ifndef MNET_UPF_RUN
 #define MNET_UPF_RUN 8
 #endif
 
-template <typename T>
-__global__ void __launch_bounds__(256, 2) upfold_kernel(const T* __restrict__ z, T* __restrict__ y, int H, int W, int C,
+// A tap chunk of the thread's N channels as fp32.  Z in y's storage: the storage's reader.  Z in fp32 under a y of 8-channel chunks (upfold_kernel<float, hm>,
+// mnet_upfold3x3_f32z_nhwc): the same nominal address — 8 channels are 32 bytes in both — holds the values themselves: two plain 16-byte loads, no decode instruction,
+// no quad co-operation and no raw copy of the chunk beside the decoded one.
+template <typename TZ, int N>
+__device__ __forceinline__ void upf_load(const TZ* p, float (&o)[N]) {
+    if constexpr (__is_same(TZ, float) && N == 8) {
+        Vec<float>::unpack(ldg16s(p), o);
+        Vec<float>::unpack(ldg16s(p + 4), o + 4);
+    } else {
+        unpackr<TZ>(ldraw<TZ>(p), o);
+    }
+}
+
+// waves per SIMD the kernel is compiled for.  The fp32-plane form carries no raw chunks, but its walk state (h, the two open pairs, six chunks of a filter row in flight)
+// still fills the file: compiled for 2 waves it takes 256 VGPRs with 20 spilled (fp16+8 planes: 256 with 33), for 3 waves 168 with 85 spilled, for 4 waves 128 with 177
+// — so it stays at 2 like every same-storage form (MNET_UPF_F32Z_WAVES: the A/B build).  Measured at 2: 3.46 / 3.70 TB/s of Z + y bytes on the 16→32 / 32→64 levels of
+// 1024 glyphs against 2.71 / 2.69 with fp16+8 planes (profiles/upfold_f32z_kernel_ab.json).
+#ifndef MNET_UPF_F32Z_WAVES
+#define MNET_UPF_F32Z_WAVES 2
+#endif
+template <typename TZ, typename TY> constexpr int upf_waves = __is_same(TZ, TY) ? 2 : MNET_UPF_F32Z_WAVES;
+
+template <typename TZ, typename TY = TZ>
+__global__ void __launch_bounds__(256, (upf_waves<TZ, TY>)) upfold_kernel(const TZ* __restrict__ z, TY* __restrict__ y, int H, int W, int C,
                                                         const float* __restrict__ out_scale, const float* __restrict__ bias,
                                                         const float* __restrict__ post_scale, int act, unsigned items_per_image) {
     // grid: x strides over the (chunk, hi-res column, row run) items of ONE image (32-bit index math only), y = image — upsample2x_kernel's launch shape
+    using T = TY;                                                           // (the thread's chunk is y's: N channels; z is addressed in the same 4-byte elements)
     constexpr int N = Vec<T>::N;
+    static_assert(sizeof(TZ) == sizeof(TY) || __is_same(TZ, TY), "z and y: the same storage, or two storages of 4 bytes per element");
     constexpr int R = MNET_UPF_RUN;
     const unsigned cpp = (unsigned)C / N;
     // XCD-aware order (see upsample2x_kernel): XCD k takes the k-th eighth of the (image, workgroup) sequence, so the neighbours that re-read a workgroup's halo share its L2
@@ -40,7 +67,7 @@ __global__ void __launch_bounds__(256, 2) upfold_kernel(const T* __restrict__ z,
     }
     const int n = (int)by;
     const size_t zpix = (size_t)9 * C;                                      // elements per low-res pixel of z
-    const T* zbase = z + (size_t)n * H * W * zpix;
+    const TZ* zbase = z + (size_t)n * H * W * zpix;
     T* ybase = y + (size_t)n * 4 * H * W * C;
     const int W2 = 2 * W;
     for (unsigned id = bx * 256u + threadIdx.x; id < items_per_image; id += gridDim.x * 256u) {
@@ -58,18 +85,18 @@ __global__ void __launch_bounds__(256, 2) upfold_kernel(const T* __restrict__ z,
             w0[kx] = in ? (odd ? 0.75f : 0.25f) : 0.f;
             w1[kx] = in ? (odd ? 0.25f : 0.75f) : 0.f;
         }
-        const T* base = zbase + (size_t)ch * N;
+        const TZ* base = zbase + (size_t)ch * N;
         // H_ky of low-res row r at this hi-res column: six chunks per filter row, summed one at a time in this order
         auto hrow = [&](int r, float (&h)[3][N]) __attribute__((always_inline)) {
-            const T* rp = base + (size_t)r * W * zpix;
+            const TZ* rp = base + (size_t)r * W * zpix;
 #pragma unroll
             for (int ky = 0; ky < 3; ++ky) {
 #pragma unroll
                 for (int kx = 0; kx < 3; ++kx) {
-                    const T* tp = rp + (size_t)(3 * ky + kx) * C;
+                    const TZ* tp = rp + (size_t)(3 * ky + kx) * C;
                     float a[N], b[N];
-                    unpackr<T>(ldraw<T>(tp + c0[kx]), a);
-                    unpackr<T>(ldraw<T>(tp + c1[kx]), b);
+                    upf_load<TZ, N>(tp + c0[kx], a);
+                    upf_load<TZ, N>(tp + c1[kx], b);
 #pragma unroll
                     for (int j = 0; j < N; ++j) {
                         const float t = w0[kx] * a[j] + w1[kx] * b[j];
@@ -170,6 +197,26 @@ extern "C" int mnet_upfold3x3_nhwc(const void* z, void* y, int32_t dtype, int32_
         using T = typename decltype(tag)::type;
         hipLaunchKernelGGL((upfold_kernel<T>), dim3(gx, n), dim3(256), 0, st, (const T*)z, (T*)y, h, w, c, out_scale, bias, post_scale, act, (unsigned)per);
     });
+    MNET_LAUNCH_CHECK("upfold3x3");
+    return MNET_OK;
+}
+
+// z in fp32, y in fp16+8: the checks, the items and the grid of mnet_upfold3x3_nhwc at dtype = MNET_F16M (8-channel chunks, a blocked y; z is 128-byte aligned like y, so
+// that the planes are whole lines) — the same launch shape for the same thread map
+extern "C" int mnet_upfold3x3_f32z_nhwc(const float* z, void* y, int32_t ydtype, int32_t n, int32_t h, int32_t w, int32_t c,
+                                        const float* out_scale, const float* bias, int32_t act, const float* post_scale, void* stream) {
+    MNET_CHECK_ARG(ydtype == MNET_F16M, "upfold3x3: fp32 tap planes fold into an MNET_F16M output only (ydtype %d)", ydtype);
+    MNET_CHECK_ARG(z && y && (const void*)z != y, "upfold3x3: null pointer (or y == z: not an in-place kernel)");
+    MNET_CHECK_ARG(n > 0 && n <= 65535 && h > 0 && w > 0 && c > 0, "upfold3x3: bad geometry");
+    MNET_CHECK_ARG(act == MNET_ACT_NONE || act == MNET_ACT_LRELU || act == MNET_ACT_LRELU_SQRT2, "upfold3x3: activation must be NONE, LRELU or LRELU_SQRT2");
+    constexpr int N = Vec<hm>::N;
+    MNET_CHECK_ALIGN(c % 32 == 0 && aligned128(z) && aligned128(y) && aligned16(out_scale) && aligned16(bias) && aligned16(post_scale),
+                     "upfold3x3: fp32 planes under an fp16+8 output need c %% 32 == 0, z and y 128-byte aligned, the vectors 16-byte aligned");
+    MNET_CHECK_ARG((long long)h * w * (c / N) * 4 < (1ll << 31) && (long long)w * 9 * c < (1ll << 29), "upfold3x3: image too large");
+    const long long per = (long long)((h + MNET_UPF_RUN - 1) / MNET_UPF_RUN) * 2 * w * (c / N);
+    const int gx = (int)((per + 255) / 256 < 2048 ? (per + 255) / 256 : 2048);
+    hipLaunchKernelGGL((upfold_kernel<float, hm>), dim3(gx, n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), z, (hm*)y, h, w, c, out_scale, bias, post_scale, act,
+                       (unsigned)per);
     MNET_LAUNCH_CHECK("upfold3x3");
     return MNET_OK;
 }

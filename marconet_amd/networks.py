@@ -26,6 +26,7 @@ _STYLE_NORM = not bool(int(os.environ.get("MNET_NO_STYLE_NORM", "0")))     # A/B
 _FOLD_SKIP = not bool(int(os.environ.get("MNET_NO_FOLD_SKIP", "0")))       # A/B knob: ResTextBlockV2's 1x1 skip conv as extra K of its conv2
 _NO_POLYPHASE = os.environ.get("MNET_NO_POLYPHASE", "0") == "1"             # A/B knob: the SR up-convs keep up-sample + conv (no polyphase form)
 _NO_UPFOLD = os.environ.get("MNET_NO_UPFOLD", "0") == "1"                   # A/B knob: the generator's up-convs keep up-sample + conv (no tap-conv + fold form)
+_UPFOLD_HM_Z = os.environ.get("MNET_UPFOLD_HM_Z", "0") == "1"                # A/B knob: the tap planes of the tap-conv + fold form stay in fp16+8 (not fp32)
 _POLYPHASE_CONV_UP = os.environ.get("MNET_POLYPHASE_CONV_UP", "0") == "1"    # A/B knob: conv_up.1 takes the polyphase form too (default: conv_final.3 only)
 _FUSE_IMG_CONVERT = os.environ.get("MNET_NO_FUSE_IMG_CONVERT", "0") != "1"   # image-only levels: the f16 conversion rides in the up-sample's store (A/B knob)
 _FUSE_CONV1_MOD = os.environ.get("MNET_NO_FUSE_CONV1_MOD", "0") != "1"      # conv1's style multiply in the SelectText gather (A/B knob)
@@ -312,10 +313,13 @@ class TextGenerator(nn.Module):
                 # tap-conv + fold (fp16+8 storage, the levels of ops.UPFOLD_LEVELS): the up-sample commutes with the conv's channel contraction, so the nine taps
                 # run as ONE 1x1 conv on the low-res map (a quarter of the MACs; the 4×-sized up-sampled tensor is never written) and a streaming kernel sums
                 # their up-sampled, shifted planes under the StyledConv's epilogue.  x keeps its other readers (ToRGB, the SR net's prior): ·s_a is its own pass
+                # The planes have one reader and fp16+8 costs fp32's 4 bytes per element: where the planner gives the launch to the one-wave tile they are written in
+                # fp32 (no encode in the conv, no decode in the fold, one rounding less), else — or under MNET_UPFOLD_HM_Z=1 — in fp16+8
+                z32 = not _UPFOLD_HM_Z and ops.upfold_plan(x, La["cout"], out_f32=True) >= 0
                 xs = ops.affine_act(x, sa)
-                z = ops.conv2d(xs, La["w_tap"], 9 * La["cout"], 1, 1)
+                z = ops.conv2d(xs, La["w_tap"], 9 * La["cout"], 1, 1, out_f32=z32)
                 del xs
-                xa = ops.upfold3x3(z, La["cout"], out_scale=da, bias=La["bias"], act=ops.ACT_LRELU_SQRT2, post_scale=sb)
+                xa = ops.upfold3x3(z, La["cout"], out_scale=da, bias=La["bias"], act=ops.ACT_LRELU_SQRT2, post_scale=sb, out_dtype=x.dtype)
                 del z
             else:
                 xu = ops.upsample2x(x, scale=sa, out_dtype=up_dtype if up_dtype != x.dtype else None)   # bilinear ×2 (:293) with ·s_a fused

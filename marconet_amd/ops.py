@@ -170,13 +170,15 @@ def _conv_desc(x0, x1, cout, kh, kw, stride, pad, wgt, y, in_scale=None, in_shif
 @_plumbing
 def conv2d(x0, wgt, cout, kh=1, kw=1, stride=(1, 1), pad=(0, 0), x1=None, in_scale=None, in_shift=None,
            in_swish=False, valid_w=None, out_scale=None, bias=None, residual=None, res_mod=0, act=ACT_NONE,
-           post_scale=None, out=None, algo=0, splitk=0, x1_center=False, gn_partial=None, shuffle2=False):
+           post_scale=None, out=None, algo=0, splitk=0, x1_center=False, gn_partial=None, shuffle2=False, out_f32=False):
     """mnet_conv2d_nhwc(_ex).  x0 [N,H,W,C0] (+ optional x1 [N,H,W,C1]); wgt packed [cout,kh,kw,C0+C1] same dtype.
     ``splitk`` > 0: mnet_conv2d_splitk with that many K-slices (fp32 filter == stride convs over <= 512 output pixels).
     ``x1_center``: x1 enters through the filter's centre tap only (MNET_CONV_ALGO_FLAG_X1_CENTER: a 1x1 skip conv as extra K).
     ``gn_partial``: fp32 [n*ho*wo/32, cout/32, 2] buffer (``gn_partial_buffer``) the epilogue fills with the GroupNorm partial sums of the output
     (fp16+8 launches on the LDS-DMA / strip kernels only: MarconetHipError otherwise, nothing enqueued).
-    ``shuffle2``: MNET_CONV_ALGO_FLAG_SHUFFLE2 — ``cout`` = 4 C phase-major and the output is the [N,2H,2W,C] tensor (see ``upconv3x3_polyphase``)."""
+    ``shuffle2``: MNET_CONV_ALGO_FLAG_SHUFFLE2 — ``cout`` = 4 C phase-major and the output is the [N,2H,2W,C] tensor (see ``upconv3x3_polyphase``).
+    ``out_f32``: MNET_CONV_ALGO_FLAG_F32_OUT — an fp16+8 launch whose output is a plain fp32 tensor (the value before the storage's rounding; plain epilogue,
+    one-wave tile only: MarconetHipError otherwise, nothing enqueued)."""
     lib = _lib.load()
     _need_cuda(x0, x1, wgt, in_scale, in_shift, valid_w, out_scale, bias, residual, post_scale, out)
     n, h, w, c0 = x0.shape
@@ -191,10 +193,13 @@ def conv2d(x0, wgt, cout, kh=1, kw=1, stride=(1, 1), pad=(0, 0), x1=None, in_sca
     oshape = (n, 2 * ho, 2 * wo, cout // 4) if shuffle2 else (n, ho, wo, cout)
     if shuffle2:
         algo |= _lib.ALGO_FLAG_SHUFFLE2
+    if out_f32:
+        algo |= _lib.ALGO_FLAG_F32_OUT
+    odtype = torch.float32 if out_f32 else x0.dtype
     if out is None:
-        out = new_tensor(oshape, x0.dtype, x0.device)
-    elif tuple(out.shape) != oshape or out.dtype != x0.dtype:
-        raise RuntimeError("conv2d: out is %s %s, expected %s %s" % (tuple(out.shape), out.dtype, oshape, x0.dtype))
+        out = new_tensor(oshape, odtype, x0.device)
+    elif tuple(out.shape) != oshape or out.dtype != odtype:
+        raise RuntimeError("conv2d: out is %s %s, expected %s %s" % (tuple(out.shape), out.dtype, oshape, odtype))
     if gn_partial is not None:
         _need_cuda(gn_partial)
         if gn_partial.dtype != torch.float32 or gn_partial.numel() != (n * ho * wo // 32) * (cout // 32) * 2:
@@ -412,28 +417,33 @@ def upconv3x3_polyphase(x, wgt_poly, bias_poly, wgt, bias, c, act=ACT_NONE, algo
 UPFOLD_LEVELS = {(512, 512): 16, (512, 256): 16}
 
 
-def upfold_plan(x, cout, levels=None):
+def upfold_plan(x, cout, levels=None, out_f32=False):
     """the planner's answer for the 1x1 launch of the tap-conv form of conv3x3(bilinear_x2(x)) with ``cout`` output channels (``conv2d(x, w_tap, 9·cout)``,
     then ``upfold3x3``), or a negative value — the caller keeps up-sample + conv.  fp16+8 storage only, the levels of ``UPFOLD_LEVELS`` (``levels``: another
     table), and only when the planner hands the launch to an LDS-DMA tile.  It depends on the per-glyph map shape, the channel counts and the storage type,
-    never on the batch."""
+    never on the batch.  ``out_f32``: the question about the launch that writes the tap planes in fp32 (``conv2d(..., out_f32=True)``, folded by ``upfold3x3``
+    with ``out_dtype=MX_DTYPE``) — accepted only where it resolves to the one-wave tile."""
     if x.dtype != MX_DTYPE:
         return -1
     _, h, _, cin = x.shape
     min_h = (UPFOLD_LEVELS if levels is None else levels).get((cin, cout))
     if min_h is None or h < min_h:
         return -1
-    k = conv_plan(x, 9 * cout, 1, 1)
+    k = conv_plan(x, 9 * cout, 1, 1, algo=_lib.ALGO_FLAG_F32_OUT if out_f32 else 0)
     return k if k >= 0 and plan_is_lds_dma(k) else -1
 
 
 @_plumbing
-def upfold3x3(z, c, out_scale=None, bias=None, act=ACT_NONE, post_scale=None, out=None):
+def upfold3x3(z, c, out_scale=None, bias=None, act=ACT_NONE, post_scale=None, out=None, out_dtype=None):
     """mnet_upfold3x3_nhwc: ``z`` [N,h,w,9·c] (tap-major: channel t·c + o, t = 3·ky + kx; the 1x1 conv of the low-res map with packing.pack_tapconv_weight) →
     y [N,2h,2w,c] = post_scale · act(out_scale · Σ_t (bilinear_x2 z_t) shifted by tap t + bias): conv3x3(bilinear_x2(x)) with the conv epilogue's contract,
-    without the up-sampled tensor"""
+    without the up-sampled tensor.  y has z's storage, except that fp32 ``z`` (``conv2d(..., out_f32=True)``) folds into an fp16+8 y when ``out`` is one or
+    ``out_dtype`` says so (mnet_upfold3x3_f32z_nhwc)"""
     lib = _lib.load()
     _need_cuda(z, out_scale, bias, post_scale, out)
+    ydtype = out.dtype if out is not None and out_dtype is None else (z.dtype if out_dtype is None else out_dtype)
+    if ydtype != z.dtype and not (z.dtype == torch.float32 and ydtype == MX_DTYPE):
+        raise RuntimeError("upfold3x3: z is %s and y %s — y has z's storage, or z is float32 and y fp16+8" % (z.dtype, ydtype))
     n, h, w, c9 = z.shape
     if c9 != 9 * c:
         raise RuntimeError("upfold3x3: z has %d channels, expected 9 x %d" % (c9, c))
@@ -442,9 +452,13 @@ def upfold3x3(z, c, out_scale=None, bias=None, act=ACT_NONE, post_scale=None, ou
             raise TypeError("upfold3x3: %s must be float32" % nm)
     oshape = (n, 2 * h, 2 * w, c)
     if out is None:
-        out = new_tensor(oshape, z.dtype, z.device)
-    elif tuple(out.shape) != oshape or out.dtype != z.dtype:
-        raise RuntimeError("upfold3x3: out is %s %s, expected %s %s" % (tuple(out.shape), out.dtype, oshape, z.dtype))
+        out = new_tensor(oshape, ydtype, z.device)
+    elif tuple(out.shape) != oshape or out.dtype != ydtype:
+        raise RuntimeError("upfold3x3: out is %s %s, expected %s %s" % (tuple(out.shape), out.dtype, oshape, ydtype))
+    if ydtype != z.dtype:
+        stats.tail("upfold", (z, out), lambda: _lib.check(lib.mnet_upfold3x3_f32z_nhwc(_p(z), _p(out), _dt(out), n, h, w, c, _p(out_scale), _p(bias), act,
+                                                                                      _p(post_scale), _stream()), "mnet_upfold3x3_f32z_nhwc"))
+        return out
     stats.tail("upfold", (z, out), lambda: _lib.check(lib.mnet_upfold3x3_nhwc(_p(z), _p(out), _dt(z), n, h, w, c, _p(out_scale), _p(bias), act, _p(post_scale),
                                                                              _stream()), "mnet_upfold3x3_nhwc"))
     return out

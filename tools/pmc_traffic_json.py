@@ -22,7 +22,7 @@ def main():
         # GroupNorm-sum block, conv_dma_swp_gn.hip — the SAME tile id for bench.py, so its launches are folded into the "swp" entry)
         # (DBG = -1: the tile's build with the MNET_CONV_ALGO_FLAG_SHUFFLE2 output mode — the same tile id for bench.py, folded into the same entry)
         m = re.match(r"void conv_dma_kernel<(\d+), (\d+), (\d+), (\d+), (\d+), (\d+), (?:0|-1)(?:, (\w+))?(?:, (\w+))?(?:, (\w+))?(?:, (\w+))?(?:, (\w+))?(?:, (\w+))?>", lines[0])
-        w4 = re.match(r"void conv_dma_w4(?:_shuf)?_kernel<", lines[0])        # round 6: the one-wave-per-SIMD tile (four builds by epilogue features + the two with the SHUFFLE2 output mode, conv_dma_w4_shuf.hip: ONE tile id for bench.py)
+        w4 = re.match(r"void conv_dma_w4(?:_shuf|_f32)?_kernel<", lines[0])   # round 6: the one-wave-per-SIMD tile (four builds by epilogue features + the two with the SHUFFLE2 output mode, conv_dma_w4_shuf.hip, + the fp32-output build, conv_dma_w4_f32.hip: ONE tile id for bench.py)
         if not m and not w4:
             continue
         if m:

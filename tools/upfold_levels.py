@@ -30,6 +30,20 @@ for n in (1024, 16):
         t_fd = timeit(lambda: ops.upfold3x3(z, c, out_scale=d, bias=b, act=3, post_scale=p))
         gb = (z.numel() + n * 4 * h * h * c) * 4 / 1e9
         plan = ops.conv_plan(xs, 9 * c, 1, 1)
+        fl = 2.0 * n * h * h * cin * 9 * c
         print("n=%4d %2d->%2d %d->%d: old %.3f ms (ups %.3f + conv %.3f) | new %.3f ms (scale %.3f + tapconv %.3f [plan %d, %.0f TFLOP/s] + fold %.3f [%.2f GB, %.2f TB/s])"
-              % (n, h, 2 * h, cin, c, t_up + t_cv, t_up, t_cv, t_sc + t_tc + t_fd, t_sc, t_tc, plan, 2.0 * n * h * h * cin * 9 * c / t_tc / 1e9, t_fd, gb, gb / t_fd), flush=True)
-        del z, xs, x
+              % (n, h, 2 * h, cin, c, t_up + t_cv, t_up, t_cv, t_sc + t_tc + t_fd, t_sc, t_tc, plan, fl / t_tc / 1e9, t_fd, gb, gb / t_fd), end="", flush=True)
+        del z
+        # the same with the tap planes in fp32 (conv2d(out_f32=True) + the fold's fp32-plane entry), where the planner accepts it
+        from marconet_amd import _lib
+        plan32 = ops.conv_plan(xs, 9 * c, 1, 1, algo=_lib.ALGO_FLAG_F32_OUT)
+        if plan32 >= 0:
+            t_tc32 = timeit(lambda: ops.conv2d(xs, wt, 9 * c, 1, 1, out_f32=True))
+            z32 = ops.conv2d(xs, wt, 9 * c, 1, 1, out_f32=True)
+            t_fd32 = timeit(lambda: ops.upfold3x3(z32, c, out_scale=d, bias=b, act=3, post_scale=p, out_dtype=P.MX_DTYPE))
+            print(" | fp32 planes %.3f ms (tapconv %.3f [plan %d, %.0f TFLOP/s] + fold %.3f [%.2f TB/s])"
+                  % (t_sc + t_tc32 + t_fd32, t_tc32, plan32, fl / t_tc32 / 1e9, t_fd32, gb / t_fd32), flush=True)
+            del z32
+        else:
+            print(" | fp32 planes: refused (%d)" % plan32, flush=True)
+        del xs, x
