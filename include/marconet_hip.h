@@ -376,15 +376,22 @@ int mnet_fused_bias_act(const float* x, const float* bias, float* y, int64_t tot
  * bilinearly up-sampled (x2, align_corners=False) RGB image of the level below, then tanh — one streaming pass over x.
  *   out[n,y,x,o] = tanh( scale_b[n] * sum_c wgt[o][c] * (x[n,y,x,c] * style[n][c]) + bias[o] + up2(skip)[n,y,x,o] ),  out[..,3] = 0
  * x NHWC [n,h,w,c] in any storage dtype (c in {64,128,256,512}); wgt fp32 [3][c] (the layer's constant scale folded); style fp32 [n][c];
- * scale_b fp32 [n] or NULL (1); bias fp32 [3]; skip fp32 [n,h/2,w/2,4] or NULL; out fp32 [n,h,w,4]. */
+ * scale_b fp32 [n] or NULL (1); bias fp32 [3]; skip fp32 [n,h/2,w/2,4] or NULL (its channel 3 is read and ignored); out fp32 [n,h,w,4].
+ * Overflow rule (every storage dtype): a pre-activation that is not finite — an inf or NaN element of x, a sum that overflowed fp32 — is
+ * stored as NaN, never as tanh's +-1, so that a finiteness check of the image sees it; out[..,3] stays +0 and no other pixel changes. */
 int mnet_torgb(const void* x, int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t c, const float* wgt, const float* style,
                const float* scale_b, const float* bias, const float* skip, float* out, void* stream);
 
 /* 3x3 / stride 1 / pad 1 convolution of a cin = 64 map to 3 output channels + bias (+ tanh): the last layer of TSPSRNet
- * (conv_final.6 + Tanh, models/networks.py:374-375).  x NHWC [n,h,w,64] (f16 or f32); wgt [3][3][3][64] (cout, kh, kw, cin) in
- * the same dtype; bias fp32 [3]; act MNET_ACT_NONE or MNET_ACT_TANH.  Outputs (either may be NULL, not both): y_nhwc
+ * (conv_final.6 + Tanh, models/networks.py:374-375).  x NHWC [n,h,w,64] in any storage dtype; wgt [3][3][3][64] (cout, kh, kw, cin) in
+ * the same dtype for MNET_F16 / MNET_F32; bias fp32 [3]; act MNET_ACT_NONE or MNET_ACT_TANH.  Outputs (either may be NULL, not both): y_nhwc
  * [n,h,w,8] in the input dtype (channels 3..7 zero) and y_nchw fp32 [n,3,h,w] — the tensor the module returns, without a
- * separate layout pass (in f16 mode it holds the same f16-rounded values as y_nhwc). */
+ * separate layout pass (in f16 mode it holds the same f16-rounded values as y_nhwc).
+ * A split-half (MNET_F16X2) or fp16+8 (MNET_F16M) x is decoded to fp32 while it is staged: wgt is then plain fp32 [3][3][3][64] (not the
+ * packed conv-weight layout), y_nhwc is fp32 [n,h,w,8], the arithmetic is the fp32 one, and x must be 128-byte aligned.
+ * Overflow rule (MNET_ACT_TANH): with a half-range input (MNET_F16, MNET_F16X2, MNET_F16M) an infinite or NaN pre-activation is stored as
+ * NaN in both outputs, never as tanh's +-1, so that a finiteness check of the image sees it.  An MNET_F32 input is plain tanhf: +-inf
+ * gives exactly +-1.  MNET_ACT_NONE stores the pre-activation as it is. */
 int mnet_conv3x3_rgb(const void* x, int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t cin, const void* wgt,
                      const float* bias, int32_t act, void* y_nhwc, float* y_nchw, void* stream);
 
