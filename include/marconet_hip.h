@@ -135,7 +135,21 @@ int mnet_conv2d_nhwc(const mnet_conv_desc* d, void* stream);
 /* same with an explicit kernel choice (A/B measurements, tests): AUTO picks the LDS-DMA kernel when the launch is
  * eligible (f16, (c0+c1) % 64 == 0, c0 % 64 == 0, cout >= 64, cout % 8 == 0, no in_scale, act <= LRELU_SQRT2, and a filter of
  * kh * kw <= 32 taps with kh, kw <= 8 — the tap mask of a pixel is one 32-bit word; any stride and any padding >= 0) and the
- * register-staged one otherwise (it takes every filter); MNET_CONV_ALGO_DMA_CFG0 + id pins one LDS-DMA tile configuration
+ * register-staged one otherwise (it takes every filter).
+ * Address range of the LDS-DMA and strip kernels (they address a tile's activations with 31-bit byte offsets from a 64-bit per-tile base and form
+ * pixel x bytes-per-pixel in a 24-bit multiply; the register-staged kernel uses 64-bit offsets throughout and has no such limit).  With
+ *   I = 512 / (h * w) + 2   the images a 512-pixel tile may touch (2 for a map of more than 512 pixels; the batch n does not enter), and
+ *   P = the physical halves per pixel of the wider source: max(c0, c1) for MNET_F16, twice that for MNET_F16X2 / MNET_F16M,
+ *   K = kh * kw * (physical halves of c0 + c1),
+ * a launch is eligible only if all of
+ *   I * h * w < 2^23                 (24-bit pixel index)            2 * P < 2^23
+ *   I * h * w * P * 2 < 2^31 - 1     (31-bit activation offsets)
+ *   cout * K * 2 < 2^31 - 1          (31-bit weight offsets)         256 * K * 2 < 2^30
+ * hold; the strip kernels further need h * w * (physical halves of c0) * 2 < 2^31 - 1 (one image per buffer descriptor).  Beyond them AUTO
+ * answers MNET_CONV_ALGO_REG_STAGED and a pinned LDS-DMA or strip request is MNET_E_ARG.  Every launch needs n * h * w < 2^31 and
+ * n * ho * wo < 2^31 (MNET_E_ARG "too many pixels"); element and byte offsets into x0 / x1 / residual / y are 64-bit in every kernel, so a
+ * tensor may be larger than 2^32 bytes and hold more than 2^31 elements (tests/test_large_tensors_gpu.py).
+ * MNET_CONV_ALGO_DMA_CFG0 + id pins one LDS-DMA tile configuration
  * (cout x pixel tile, waves, LDS stages):
  *   id 0: 256x256 16w 2st   1: 256x128 8w 3st   2: 128x256 8w 3st   3: 64x256 8w 3st   4: 128x512 16w 2st
  *      5: 64x512 8w 2st     6: 256x256 8w 2st (128x64 per wave)      — all on v_mfma_f32_16x16x32_f16 walking k in the
@@ -349,7 +363,7 @@ int mnet_embed_gather(const float* emb, const int64_t* labels, void* out, int32_
 int mnet_embed_gather_scaled(const float* emb, const int64_t* labels, const float* scale, void* out, int32_t dtype, int32_t N,
                              int32_t nc, int32_t C, int32_t num_classes, void* stream);
 /* demod[n,o] = rsqrt( sum_i style[n,i]^2 * wsq_t[i,o] + 1e-8 ),  wsq_t[i,o] = scale^2 * sum_k W[o,i,k]^2
- * (ModulatedConv2d :284-287 rewritten for activation-side modulation) */
+ * (ModulatedConv2d :284-287 rewritten for activation-side modulation); N <= 65535, cin <= 16384 (MNET_E_ARG) */
 int mnet_demod(const float* style, const float* wsq_t, float* demod, int32_t N, int32_t cin,
                int32_t cout, void* stream);
 

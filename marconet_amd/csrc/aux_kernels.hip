@@ -53,9 +53,9 @@ __global__ void __launch_bounds__(256) nhwc_to_nchw_kernel(const T* __restrict__
 extern "C" int mnet_nchw_to_nhwc(const float* src, void* dst, int32_t dst_dtype, int32_t n, int32_t c, int32_t h,
                                  int32_t w, int32_t c_ld, void* stream) {
     MNET_CHECK_ARG(src && dst && n > 0 && c > 0 && h > 0 && w > 0 && c_ld >= c, "nchw_to_nhwc: bad args");
+    MNET_CHECK_ARG(n <= 65535 && (c_ld + 31) / 32 <= 65535, "nchw_to_nhwc: grid too large");
     MNET_CHECK_ARG(is_storage(dst_dtype), "nchw_to_nhwc: bad dtype");
     MNET_CHECK_ALIGN(!is_split4(dst_dtype) || (c_ld % 32 == 0 && aligned128(dst)), "nchw_to_nhwc: split-half output needs c_ld %% 32 == 0 and a 128-byte aligned base");
-    MNET_CHECK_ARG(n <= 65535 && (c_ld + 31) / 32 <= 65535, "nchw_to_nhwc: grid too large");
     const int HW = h * w;
     dim3 grid((HW + 31) / 32, (c_ld + 31) / 32, n), block(32, 8);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -70,9 +70,9 @@ extern "C" int mnet_nchw_to_nhwc(const float* src, void* dst, int32_t dst_dtype,
 extern "C" int mnet_nhwc_to_nchw(const void* src, int32_t src_dtype, float* dst, int32_t n, int32_t c, int32_t h,
                                  int32_t w, int32_t c_ld, void* stream) {
     MNET_CHECK_ARG(src && dst && n > 0 && c > 0 && h > 0 && w > 0 && c_ld >= c, "nhwc_to_nchw: bad args");
+    MNET_CHECK_ARG(n <= 65535 && (c + 31) / 32 <= 65535, "nhwc_to_nchw: grid too large");
     MNET_CHECK_ARG(is_storage(src_dtype), "nhwc_to_nchw: bad dtype");
     MNET_CHECK_ALIGN(!is_split4(src_dtype) || (c_ld % 32 == 0 && aligned128(src)), "nhwc_to_nchw: split-half input needs c_ld %% 32 == 0 and a 128-byte aligned base");
-    MNET_CHECK_ARG(n <= 65535 && (c + 31) / 32 <= 65535, "nhwc_to_nchw: grid too large");
     const int HW = h * w;
     dim3 grid((HW + 31) / 32, (c + 31) / 32, n), block(32, 8);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -206,10 +206,10 @@ extern "C" int mnet_upsample2x_convert_nhwc(const void* src, int32_t dtype, void
     MNET_CHECK_ARG(is_storage(dtype), "upsample2x: bad dtype");
     MNET_CHECK_ARG(dst_dtype == dtype || (dst_dtype == MNET_F16 && is_split4(dtype)), "upsample2x: the output is the input's storage type, or MNET_F16 for a split-half / fp16+8 input");
     const int N = chunk_n(dtype);
+    MNET_CHECK_ARG((long long)h * w * (c / N) * 4 < (1ll << 31), "upsample2x: image too large");
     MNET_CHECK_ALIGN(c % N == 0 && aligned16(src) && aligned16(dst) && aligned16(scale), "upsample2x: c %% %d != 0 or unaligned", N);
     MNET_CHECK_ALIGN(!is_split4(dtype) || (c % 32 == 0 && aligned128(src)), "upsample2x: split-half needs c %% 32 == 0, 128-byte aligned");
     MNET_CHECK_ALIGN(!is_split4(dst_dtype) || aligned128(dst), "upsample2x: split-half output must be 128-byte aligned");
-    MNET_CHECK_ARG((long long)h * w * (c / N) * 4 < (1ll << 31), "upsample2x: image too large");
     const long long per = (long long)((h + MNET_UPS_RUN - 1) / MNET_UPS_RUN) * w * (c / N);      // one thread per (chunk, column, run of MNET_UPS_RUN input rows)
     const int gx = (int)((per + 255) / 256 < 2048 ? (per + 255) / 256 : 2048);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -956,6 +956,7 @@ __global__ void __launch_bounds__(256) demod_kernel(const float* __restrict__ st
 extern "C" int mnet_demod_scaled(const float* style, const float* wsq_t, float* demod, int32_t N_, int32_t cin,
                                  int32_t cout, const float* eps_scale, void* stream) {
     MNET_CHECK_ARG(style && wsq_t && demod && N_ > 0 && cin > 0 && cout > 0 && N_ <= 65535, "demod: bad args");
+    MNET_CHECK_ARG((size_t)cin * sizeof(float) <= 65536, "demod: cin=%d too large (the squared style row is staged in 64 KiB of LDS)", cin);
     hipLaunchKernelGGL(demod_kernel, dim3((cout + 63) / 64, N_), dim3(256), (size_t)cin * sizeof(float), reinterpret_cast<hipStream_t>(stream),
                        style, wsq_t, demod, cin, cout, eps_scale);
     MNET_LAUNCH_CHECK("demod");
@@ -1097,11 +1098,11 @@ extern "C" int mnet_affine_act_nhwc(const void* x, void* y, int32_t dtype, int32
     MNET_CHECK_ARG(x && y && scale && n > 0 && hw > 0 && c > 0 && n <= 65535, "affine_act: bad args");
     MNET_CHECK_ARG(is_storage(dtype), "affine_act: bad dtype");
     const int N = chunk_n(dtype);
+    const long long per = (long long)hw * (c / N);
+    MNET_CHECK_ARG(per < (1ll << 31), "affine_act: image too large");
     MNET_CHECK_ALIGN(!is_split4(dtype) || (c % 32 == 0 && aligned128(x) && aligned128(y)), "affine_act: split-half needs c %% 32 == 0, 128-byte aligned");
     MNET_CHECK_ALIGN(c % N == 0 && 256 % (c / N) == 0 && aligned16(x) && aligned16(y) && aligned16(scale) && aligned16(shift),
                      "affine_act: c=%d unsupported or unaligned", c);
-    const long long per = (long long)hw * (c / N);
-    MNET_CHECK_ARG(per < (1ll << 31), "affine_act: image too large");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     dispatch_storage(dtype, [&](auto tag) { affine_act_launch<typename decltype(tag)::type>(x, y, n, c, per, scale, shift, swish, st); });
     MNET_LAUNCH_CHECK("affine_act");
