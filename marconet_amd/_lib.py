@@ -71,6 +71,17 @@ class PasteRegion(ctypes.Structure):
                 ("scale_x", c_double), ("scale_y", c_double)]
 
 
+class QuadCrop(ctypes.Structure):
+    """mirror of ``mnet_quad_crop`` (include/marconet_hip_quad.h): one rectified window of mnet_quad_crop_u8's device table"""
+    _fields_ = [("offset", c_i64), ("w", c_int), ("h", c_int), ("c0", c_int), ("reserved", c_int), ("m", c_double * 9)]
+
+
+class QuadRegion(ctypes.Structure):
+    """mirror of ``mnet_quad_region`` (include/marconet_hip_quad.h): one quadrilateral region of mnet_quad_paste_u8's device table"""
+    _fields_ = [("ax0", c_int), ("ay0", c_int), ("rw", c_int), ("rh", c_int), ("bx0", c_int), ("by0", c_int), ("bw", c_int), ("bh", c_int),
+                ("feather", c_int), ("reserved", c_int), ("n", c_double * 9)]
+
+
 class CmpStats(ctypes.Structure):
     """mirror of ``mnet_cmp_stats`` (include/marconet_hip.h): one group's record of mnet_compare_stats"""
     _fields_ = [("max_abs_diff", c_float), ("max_abs_ref", c_float), ("max_abs_mode", c_float), ("reserved", c_int),
@@ -167,6 +178,12 @@ UPFOLD_F32Z_SYMBOLS = {
     "mnet_upfold3x3_f32z_nhwc": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
 }
 
+# ... and the two include/marconet_hip_quad.h declares (quadrilateral text regions of a page: the gather in and the gather out)
+QUAD_SYMBOLS = {
+    "mnet_quad_crop_u8": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_i64, c_void_p]),
+    "mnet_quad_paste_u8": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
+}
+
 _lib = None
 
 
@@ -184,7 +201,7 @@ def load():
             "marconet_amd: %s not found — build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or marconet_amd/csrc/build.sh (there is no CPU/eager fallback)" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(UPFOLD_SYMBOLS.items()) + list(UPFOLD_F32Z_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(UPFOLD_SYMBOLS.items()) + list(UPFOLD_F32Z_SYMBOLS.items()) + list(QUAD_SYMBOLS.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is absent
         fn.restype = res
         fn.argtypes = args

@@ -23,7 +23,7 @@ Window = collections.namedtuple("Window", "c0 c1 g0 g1 offset show_w")
 def crop_geometry(h, cw):
     """``lq_device.strip_geometry`` of an h x cw crop (its own arithmetic, on a view that holds no pixels); None where it refuses the crop as too wide"""
     try:
-        return lq_device.strip_geometry(np.broadcast_to(np.zeros((), np.uint8), (int(h), int(cw), 3)))
+        return lq_device.shape_geometry(h, cw)
     except StripTooWide:
         return None
 

@@ -37,6 +37,12 @@ def strip_geometry(img, preview=True):
     h, w, c = (int(v) for v in shape)
     if c != 3:
         raise ValueError("uint8 RGB HxWx3 array expected, got %d channels" % c)
+    return shape_geometry(h, w, preview)
+
+
+def shape_geometry(h, w, preview=True):
+    """``strip_geometry`` of a uint8 RGB strip of h x w pixels, from its size alone (its errors from ``resize_cubic: empty output`` on)"""
+    h, w = int(h), int(w)
     if h < 1 or w < 1:
         raise ValueError("resize_cubic: empty output")
     dw, dh, scale = _axis(h, w, LQ_H)
@@ -88,14 +94,36 @@ def prepare_strips(images, device, preview=False, skip_too_wide=False):
         offsets.append(off)
         flat.append(np.ascontiguousarray(img).reshape(-1))
         off += g.h * g.w * 3
-    B = len(geoms)
-    content_w, show_w = [g.dw for g in geoms], [g.show_w for g in geoms]
-    if not B:
+    if not geoms:
         return Prepared(torch.empty((0, 3, LQ_H, LQ_W), dtype=torch.float32, device=device), [], [], [],
                         torch.empty((0, SHOW_H, 0, 3), dtype=torch.uint8, device=device) if preview else None, skipped)
     src = torch.from_numpy(np.concatenate(flat)).to(device)                            # the one copy of the pixels
-    table = ops.table_to_device(build_table(geoms, offsets, preview), device)           # the one copy of the table (both rows)
+    return _resize_packed(src, geoms, offsets, index, skipped, preview)
+
+
+def _resize_packed(src, geoms, offsets, index, skipped, preview):
+    """the launches of ``prepare_strips`` / ``prepare_packed``: ``src`` uint8 [bytes] on the device holds image k at ``offsets[k]``, ``geoms[k]`` its scalars"""
+    content_w, show_w = [g.dw for g in geoms], [g.show_w for g in geoms]
+    table = ops.table_to_device(build_table(geoms, offsets, preview), src.device)       # the one copy of the table (both rows)
     with ops.on_device(src):
         lq = ops.lq_from_u8(src, table[0], LQ_H, LQ_W)
         show = ops.lq_from_u8(src, table[1], SHOW_H, max(show_w), preview=True) if preview else None
     return Prepared(lq, content_w, show_w, index, show, skipped)
+
+
+def prepare_packed(src_device, shapes, offsets, preview=False):
+    """``prepare_strips`` from pixels that are on the device already: ``src_device`` uint8 [bytes], a ragged batch of tightly packed HxWx3 images
+    (``ops.quad_crop_u8`` writes one); ``shapes[k]`` = (h, w) of image k and ``offsets[k]`` its first byte → ``Prepared`` of all images, the bits
+    ``prepare_strips`` gives for the same pixels.  No pixel is copied; one copy of the table.  Per image, in order: the errors of its size as ``prepare_strips``
+    raises them (``shape_geometry``; a strip too wide raises StripTooWide), then ValueError if it does not lie inside ``src_device`` — all before
+    anything is launched."""
+    if not torch.is_tensor(src_device) or src_device.dtype != torch.uint8 or src_device.dim() != 1:
+        raise TypeError("prepare_packed: uint8 [bytes] device tensor expected")
+    if len(shapes) != len(offsets) or not shapes:
+        raise ValueError("prepare_packed: one offset per image, and at least one image, expected (%d shapes, %d offsets)" % (len(shapes), len(offsets)))
+    geoms = []
+    for k, ((h, w), off) in enumerate(zip(shapes, offsets)):
+        geoms.append(shape_geometry(h, w, preview))
+        if int(off) < 0 or int(off) + 3 * int(h) * int(w) > src_device.numel():
+            raise ValueError("prepare_packed: image %d (%d x %d at byte %d) lies outside the %d bytes given" % (k, int(w), int(h), int(off), src_device.numel()))
+    return _resize_packed(src_device, geoms, [int(o) for o in offsets], list(range(len(geoms))), [], preview)

@@ -10,8 +10,9 @@ same bytes from the device:
                               the device and the background ``ops.lq_from_u8(preview=True)`` makes of the page: ``lq_io.resize_cubic(page, s, s)``
 
 ``MarconetPipeline.restore_page`` ties them to the networks.  A region is an axis-aligned integer box [x1, y1, x2, y2] in page pixels: the reference
-handles regular layouts without perspective only, so rotated, quadrilateral and vertical regions are out of scope, as are overlapping regions (the
-paste blends in place: an overlap has no defined order), detection and recognition (the caller's), and several pages in one launch.
+handles regular layouts without perspective only; rotated and quadrilateral regions are ``quads``' (``MarconetPipeline.restore_page_quads``).  Out of
+scope: vertical text of upright stacked characters, overlapping regions (the paste blends in place: an overlap has no defined order), detection and
+recognition (the caller's), and several pages in one launch.
 """
 import math
 

@@ -422,34 +422,47 @@ class MarconetPipeline:
         """``restore_lines`` up to the joined lines on the device: → (uint8 BGR [L,128,max out_w,3] — ``long_lines.compose_lines`` of the L lines
         that are restored, or None where there is none —, the plan per image (None for a line that is skipped), the positions of the L lines in
         ``images``).  ``who`` / ``what`` name the entry point and its unit ("image", "region") in the errors."""
-        from . import long_lines, lq_device, lq_io
+        from . import lq_device
+        plans, labels, locs_rows, live = self._plan_lines([(int(img.shape[0]), int(img.shape[1])) for img in images], texts, boxes, max_glyphs,
+                                                          overlap_glyphs, who, what)
+        if not live:
+            return None, plans, live
+        crops = [np.ascontiguousarray(images[i][:, p.c0:p.c1]) for i in live for p in plans[i]]
+        prep = lq_device.prepare_strips(crops, next(self.sr.parameters()).device)
+        return self._restore_planned(prep.lq, labels, locs_rows, plans, live), plans, live
+
+    def _plan_lines(self, sizes, texts, boxes, max_glyphs, overlap_glyphs, who, what):
+        """the planning half of ``_joined_lines``, which needs no pixel: ``sizes[i]`` = (h, w) of line i, ``boxes[i]`` its character boxes in its own
+        pixels (or None: evenly spaced ones) → (the plan per line, None for a line that is skipped; per window of the batch, in the plans' order,
+        its label tensor and its ``preds_locs`` row; the positions of the lines that are restored)"""
+        from . import long_lines, lq_io
         if texts is None:
             raise ValueError("%s needs texts: a window is a run of whole characters, and windows cut blind would cut characters in half "
                              "(restore_images(texts=None) reads a strip of at most 512 px at height 32 without them)" % who)
-        if len(texts) != len(images):
-            raise ValueError("%s: one text per %s expected (%d %ss, %d texts)" % (who, what, len(images), what, len(texts)))
+        if len(texts) != len(sizes):
+            raise ValueError("%s: one text per %s expected (%d %ss, %d texts)" % (who, what, len(sizes), what, len(texts)))
         n_cls = self.gan.TextGenerator.class_num
-        plans, crops, labels, locs_rows = [None] * len(images), [], [], []
-        for i, (img, text) in enumerate(zip(images, texts)):
+        plans, labels, locs_rows = [None] * len(sizes), [], []
+        for i, ((h, w), text) in enumerate(zip(sizes, texts)):
             lab = lq_io.label_tensor(text)
             if script_skips(lab, n_cls):
                 continue
-            h, w = int(img.shape[0]), int(img.shape[1])
             bx = boxes[i] if boxes is not None and boxes[i] is not None else lq_io.evenly_spaced_boxes(len(text), w, h)
             try:
                 plans[i] = long_lines.plan_windows(h, w, bx, max_glyphs, overlap_glyphs)
             except ValueError as e:
                 raise ValueError("%s: %s %d: %s" % (who, what, i, e)) from None
             for p in plans[i]:
-                crops.append(np.ascontiguousarray(img[:, p.c0:p.c1]))
                 labels.append(lab[p.g0:p.g1])
                 locs_rows.append(lq_io.locs_from_boxes([[b[0] - p.c0, b[1], b[2] - p.c0, b[3]] for b in bx[p.g0:p.g1]], h))
-        live = [i for i, p in enumerate(plans) if p is not None]
-        if not live:
-            return None, plans, live
-        prep = lq_device.prepare_strips(crops, next(self.sr.parameters()).device)
-        y, _ = self._restore_batch(prep.lq, labels, locs_rows)
-        return long_lines.compose_lines(y, [plans[i] for i in live]), plans, live
+        return plans, labels, locs_rows, [i for i, p in enumerate(plans) if p is not None]
+
+    def _restore_planned(self, lq, labels, locs_rows, plans, live):
+        """the restoring half of ``_joined_lines``: ``lq`` [ΣW,3,32,512] on the device, the encoder input of every window of the lines ``live`` in the
+        plans' order → their joined lines, uint8 BGR [L,128,max out_w,3] on the device"""
+        from . import long_lines
+        y, _ = self._restore_batch(lq, labels, locs_rows)
+        return long_lines.compose_lines(y, [plans[i] for i in live])
 
     @torch.no_grad()
     def restore_page(self, image, boxes, texts, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False):
@@ -468,8 +481,8 @@ class MarconetPipeline:
         page, a rectangle under 8 output rows, and two restored regions that overlap.
         ``texts`` is required, for ``restore_lines``' reason.  ``details=True`` → ``(page, regions)``: per region a dict with ``plan`` (its windows),
         ``out_w`` (the width of its restored line at height 128) and ``rect`` (x0, y0, rw, rh in the result), None where it kept the background.
-        Not covered: overlapping regions; rotated, quadrilateral, perspective or vertical text (the reference handles regular layouts only);
-        detection and recognition (the caller's); several pages in one launch."""
+        Not covered: overlapping regions; vertical text of upright stacked characters and curved text (rotated, quadrilateral and perspective
+        regions: ``restore_page_quads``); detection and recognition (the caller's); several pages in one launch."""
         from . import long_lines, lq_io, pages
         if texts is None:
             raise ValueError("restore_page needs texts: a window is a run of whole characters, and windows cut blind would cut characters in half")
@@ -495,6 +508,68 @@ class MarconetPipeline:
         if not details:
             return page
         return page, [None if p is None else dict(plan=p, out_w=w, rect=r) for p, w, r in zip(plans, out_ws, rects)]
+
+    @torch.no_grad()
+    def restore_page_quads(self, image, quads, texts, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False):
+        """``restore_page`` for text regions that are convex quadrilaterals — rotated rectangles and four-point polygons, what a text detector emits
+        for a sign photographed at an angle, a slanted scan or a line of rotated characters.  ``quads[i]``: region i's four corners [[x, y]] x 4 in
+        page pixels (any numbers), in the text's own reading order: top-left, top-right, bottom-right, bottom-left of the line as it is read (a line
+        rotated by 90 degrees is a quadrilateral whose first corner is elsewhere).  ``texts``, ``scale``, ``feather``, ``max_glyphs``,
+        ``overlap_glyphs`` as in ``restore_page``; ``char_boxes[i]``: the region's character boxes in PAGE pixels, boxes [x1, y1, x2, y2] or four
+        corners each (``quads.char_boxes_in_crop`` takes them into the rectified crop), or evenly spaced ones.
+        → uint8 RGB [s·H, s·W, 3] on the host: the bytes of ``quads.compose_quads_host(image, lines, quads, scale, feather)`` for the lines
+        ``restore_lines`` gives for the rectified crops ``quads.warp_crop_host(image, quads.quad_map(q, cw, ch), cw, ch)``.  For integer axis-aligned
+        boxes given as their corners these are ``restore_page``'s bytes.
+        The page is uploaded once and the crops never exist on the host: ``mnet_lq_from_u8`` makes the background, ONE ``mnet_quad_crop_u8`` launch
+        rectifies every window of every region into the packed batch ``lq_device.prepare_packed`` turns into the encoder's input, all windows are
+        restored as ONE batch and joined on the device as in ``restore_lines``, one ``mnet_paste_u8`` launch brings every line to its upright
+        foreground, ONE ``mnet_quad_paste_u8`` launch pastes every region and ONE device→host copy brings the page back.
+        A region with no character or a character outside the alphabet keeps the background.  ValueError naming the region, before anything is
+        copied or launched: ``quads.check_quads``' refusals.  A quadrilateral partly outside the page is allowed (the crop replicates the page's
+        border, the paste is clipped).  ``details=True`` → ``(page, regions)``: per region a dict with ``plan``, ``out_w``, ``quad`` (the corners
+        in the result) and ``size`` (rw, rh: the upright foreground's size), None where it kept the background.
+        Not covered: overlapping regions; vertical text made of upright stacked characters; curved text; detection and recognition; several pages in
+        one launch."""
+        from . import long_lines, lq_device, lq_io, quads as qd
+        if texts is None:
+            raise ValueError("restore_page_quads needs texts: a window is a run of whole characters, and windows cut blind would cut characters in half")
+        if len(texts) != len(quads) or (char_boxes is not None and len(char_boxes) != len(quads)):
+            raise ValueError("restore_page_quads: one text (and one list of character boxes, or None) per quadrilateral expected (%d quadrilaterals, "
+                             "%d texts)" % (len(quads), len(texts)))
+        image = np.asarray(image)
+        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3 or image.size == 0:
+            raise TypeError("restore_page_quads: uint8 RGB HxWx3 page expected")
+        H, W = int(image.shape[0]), int(image.shape[1])
+        n_cls = self.gan.TextGenerator.class_num
+        restored = [not script_skips(lq_io.label_tensor(t), n_cls) for t in texts]
+        try:
+            regions = qd.check_quads(H, W, quads, restored, scale, feather)
+        except ValueError as e:
+            raise ValueError("restore_page_quads: %s" % e) from None
+        maps = [qd.quad_map(r["quad"], r["cw"], r["ch"]) for r in regions]
+        local = [None] * len(regions)
+        for i, r in enumerate(regions):
+            if char_boxes is not None and char_boxes[i] is not None:
+                try:
+                    local[i] = qd.char_boxes_in_crop(char_boxes[i], maps[i], r["cw"], r["ch"])
+                except ValueError as e:
+                    raise ValueError("restore_page_quads: region %d: %s" % (i, e)) from None
+        plans, labels, locs_rows, live = self._plan_lines([(r["ch"], r["cw"]) for r in regions], texts, local, max_glyphs, overlap_glyphs,
+                                                          "restore_page_quads", "region")
+        out_ws = [None if p is None else long_lines.plan_out_w(p) for p in plans]
+        wins = [(i, p) for i in live for p in plans[i]]
+        page_d = torch.from_numpy(np.ascontiguousarray(image)).to(next(self.sr.parameters()).device)      # the one copy of the pixels
+        out = qd.enlarge(page_d, int(scale))
+        if live:
+            sizes = [(p.c1 - p.c0, regions[i]["ch"]) for i, p in wins]
+            crops, offsets = qd.crop_quads(page_d, [maps[i] for i, _ in wins], sizes, [p.c0 for _, p in wins])
+            prep = lq_device.prepare_packed(crops, [(h, w) for w, h in sizes], offsets)
+            joined = self._restore_planned(prep.lq, labels, locs_rows, plans, live)
+            qd.paste_quads(out, joined, out_ws, regions, int(feather))
+        page = out.cpu().numpy()                                                               # the one device→host copy
+        if not details:
+            return page
+        return page, [None if p is None else dict(plan=p, out_w=w, quad=r["out_quad"], size=(r["rw"], r["rh"])) for p, w, r in zip(plans, out_ws, regions)]
 
     @torch.no_grad()
     def _strips_from_images(self, images, texts, boxes, max_glyphs, preview, host_preview):
