@@ -82,6 +82,18 @@ class QuadRegion(ctypes.Structure):
                 ("feather", c_int), ("reserved", c_int), ("n", c_double * 9)]
 
 
+class ColumnCell(ctypes.Structure):
+    """mirror of ``mnet_column_cell`` (include/marconet_hip_columns.h): one character cell of one window of mnet_column_gather_u8's device table"""
+    _fields_ = [("offset", c_i64), ("win_w", c_int), ("dx", c_int), ("dw", c_int), ("sx", c_int), ("sy", c_int), ("sw", c_int), ("sh", c_int),
+                ("reserved", c_int), ("scale_x", c_double), ("scale_y", c_double)]
+
+
+class ColumnPaste(ctypes.Structure):
+    """mirror of ``mnet_column_paste`` (include/marconet_hip_columns.h): one character cell of mnet_column_paste_u8's device table"""
+    _fields_ = [("line_index", c_int), ("src_x0", c_int), ("src_w", c_int), ("x0", c_int), ("y0", c_int), ("rw", c_int), ("rh", c_int), ("feather", c_int),
+                ("k", c_int), ("fx0", c_int), ("fy0", c_int), ("fw", c_int), ("fh", c_int), ("reserved", c_int), ("scale_x", c_double), ("scale_y", c_double)]
+
+
 class CmpStats(ctypes.Structure):
     """mirror of ``mnet_cmp_stats`` (include/marconet_hip.h): one group's record of mnet_compare_stats"""
     _fields_ = [("max_abs_diff", c_float), ("max_abs_ref", c_float), ("max_abs_mode", c_float), ("reserved", c_int),
@@ -184,6 +196,12 @@ QUAD_SYMBOLS = {
     "mnet_quad_paste_u8": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
 }
 
+# ... and the two include/marconet_hip_columns.h declares (vertical text columns of a page: the gather of the cells and their paste)
+COLUMN_SYMBOLS = {
+    "mnet_column_gather_u8": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_i64, c_void_p]),
+    "mnet_column_paste_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
+}
+
 _lib = None
 
 
@@ -201,7 +219,7 @@ def load():
             "marconet_amd: %s not found — build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or marconet_amd/csrc/build.sh (there is no CPU/eager fallback)" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(UPFOLD_SYMBOLS.items()) + list(UPFOLD_F32Z_SYMBOLS.items()) + list(QUAD_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(UPFOLD_SYMBOLS.items()) + list(UPFOLD_F32Z_SYMBOLS.items()) + list(QUAD_SYMBOLS.items()) + list(COLUMN_SYMBOLS.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is absent
         fn.restype = res
         fn.argtypes = args

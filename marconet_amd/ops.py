@@ -826,6 +826,44 @@ def quad_paste_u8(atlas, regions, max_bw, max_bh, page):
     return page
 
 
+def column_gather_u8(page, cells, max_dw, dst_h, dst):
+    """mnet_column_gather_u8 (the bytes of columns.virtual_strip, cell by cell): ``page`` uint8 [H,W,3] RGB, ``cells`` uint8
+    [n, sizeof(mnet_column_cell)] (``_lib.ColumnCell``), ``dst`` uint8 [bytes], the flat buffer of the ragged batch of window images of height
+    ``dst_h`` — all on the device; ``max_dw``: the largest cell width of the table.  ``dst`` is written inside the cells' columns only and returned; a
+    cell whose descriptor cannot be followed leaves its bytes as they are."""
+    lib = _lib.load()
+    _need_cuda(page, cells, dst)
+    if page.dtype != torch.uint8 or page.dim() != 3 or page.shape[2] != 3:
+        raise TypeError("column_gather_u8: page must be uint8 [H,W,3]")
+    if dst.dtype != torch.uint8 or dst.dim() != 1:
+        raise TypeError("column_gather_u8: dst must be uint8 [bytes]")
+    _check_table("column_gather_u8", "cell table", cells, _lib.ColumnCell, 8)
+    if cells.shape[0] < 1 or page.numel() == 0 or dst.numel() == 0 or int(max_dw) < 1 or int(dst_h) < 1:
+        raise ValueError("column_gather_u8: empty batch (%d cells of at most %d x %d, page %s, %d bytes)"
+                         % (cells.shape[0], int(max_dw), int(dst_h), list(page.shape), dst.numel()))
+    _lib.check(lib.mnet_column_gather_u8(_p(page), int(page.shape[0]), int(page.shape[1]), _p(cells), int(cells.shape[0]), int(max_dw), int(dst_h),
+                                         _p(dst), int(dst.numel()), _stream()), "mnet_column_gather_u8")
+    return dst
+
+
+def column_paste_u8(lines, cells, page):
+    """mnet_column_paste_u8 (the bytes of columns.paste_column_host, cell by cell): ``lines`` uint8 [L,rows,line_w,3] BGR (``stitch_u8``), ``cells``
+    uint8 [n, sizeof(mnet_column_paste)] (``_lib.ColumnPaste``), ``page`` uint8 [H,W,3] RGB holding the background — all on the device.  ``page`` is
+    modified IN PLACE inside the cells' rectangles and returned; a cell whose descriptor cannot be followed keeps the background."""
+    lib = _lib.load()
+    _need_cuda(lines, cells, page)
+    if lines.dtype != torch.uint8 or lines.dim() != 4 or lines.shape[3] != 3:
+        raise TypeError("column_paste_u8: lines must be uint8 [L,rows,W,3]")
+    if page.dtype != torch.uint8 or page.dim() != 3 or page.shape[2] != 3:
+        raise TypeError("column_paste_u8: page must be uint8 [H,W,3]")
+    _check_table("column_paste_u8", "cell table", cells, _lib.ColumnPaste, 8)
+    if cells.shape[0] < 1 or lines.numel() == 0 or page.numel() == 0:
+        raise ValueError("column_paste_u8: empty batch (%d cells, lines %s, page %s)" % (cells.shape[0], list(lines.shape), list(page.shape)))
+    _lib.check(lib.mnet_column_paste_u8(_p(lines), int(lines.shape[0]), int(lines.shape[1]), int(lines.shape[2]), _p(cells), int(cells.shape[0]), _p(page),
+                                        int(page.shape[0]), int(page.shape[1]), _stream()), "mnet_column_paste_u8")
+    return page
+
+
 def nonfinite_flag(x, out=None):
     """mnet_nonfinite_flag: int32 [1] device tensor (``out``: a one-element int32 view to write into), 1 iff the fp32 / fp16 tensor
     ``x`` holds an inf or NaN (no synchronisation here)"""

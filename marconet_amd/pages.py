@@ -11,7 +11,8 @@ same bytes from the device:
 
 ``MarconetPipeline.restore_page`` ties them to the networks.  A region is an axis-aligned integer box [x1, y1, x2, y2] in page pixels: the reference
 handles regular layouts without perspective only; rotated and quadrilateral regions are ``quads``' (``MarconetPipeline.restore_page_quads``).  Out of
-scope: vertical text of upright stacked characters, overlapping regions (the paste blends in place: an overlap has no defined order), detection and
+scope: vertical columns that are rotated or in perspective (upright columns of stacked characters are ``columns``': ``MarconetPipeline.
+restore_page_columns``), overlapping regions (the paste blends in place: an overlap has no defined order), detection and
 recognition (the caller's), and several pages in one launch.
 """
 import math

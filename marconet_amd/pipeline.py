@@ -481,8 +481,8 @@ class MarconetPipeline:
         page, a rectangle under 8 output rows, and two restored regions that overlap.
         ``texts`` is required, for ``restore_lines``' reason.  ``details=True`` → ``(page, regions)``: per region a dict with ``plan`` (its windows),
         ``out_w`` (the width of its restored line at height 128) and ``rect`` (x0, y0, rw, rh in the result), None where it kept the background.
-        Not covered: overlapping regions; vertical text of upright stacked characters and curved text (rotated, quadrilateral and perspective
-        regions: ``restore_page_quads``); detection and recognition (the caller's); several pages in one launch."""
+        Not covered: overlapping regions; vertical columns that are rotated or in perspective (upright columns of stacked characters:
+        ``restore_page_columns``) and curved text (rotated, quadrilateral and perspective regions: ``restore_page_quads``); detection and recognition (the caller's); several pages in one launch."""
         from . import long_lines, lq_io, pages
         if texts is None:
             raise ValueError("restore_page needs texts: a window is a run of whole characters, and windows cut blind would cut characters in half")
@@ -528,8 +528,8 @@ class MarconetPipeline:
         copied or launched: ``quads.check_quads``' refusals.  A quadrilateral partly outside the page is allowed (the crop replicates the page's
         border, the paste is clipped).  ``details=True`` → ``(page, regions)``: per region a dict with ``plan``, ``out_w``, ``quad`` (the corners
         in the result) and ``size`` (rw, rh: the upright foreground's size), None where it kept the background.
-        Not covered: overlapping regions; vertical text made of upright stacked characters; curved text; detection and recognition; several pages in
-        one launch."""
+        Not covered: overlapping regions; vertical columns that are rotated or in perspective (upright columns: ``restore_page_columns``); curved
+        text; detection and recognition; several pages in one launch."""
         from . import long_lines, lq_device, lq_io, quads as qd
         if texts is None:
             raise ValueError("restore_page_quads needs texts: a window is a run of whole characters, and windows cut blind would cut characters in half")
@@ -570,6 +570,98 @@ class MarconetPipeline:
         if not details:
             return page
         return page, [None if p is None else dict(plan=p, out_w=w, quad=r["out_quad"], size=(r["rw"], r["rh"])) for p, w, r in zip(plans, out_ws, regions)]
+
+    @torch.no_grad()
+    def restore_page_columns(self, image, boxes, texts, vertical=None, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False):
+        """``restore_page`` for pages with vertical text: columns of upright characters stacked top to bottom (shop signs, couplets, book spines,
+        traditional typesetting).  ``boxes[i]``: region i's box [x1, y1, x2, y2] in page pixels, rounded outward as in ``restore_page``;
+        ``vertical[i]``: region i is a column, read top to bottom (None: every region is); a region with ``vertical[i]`` false is a horizontal line,
+        handled exactly as in ``restore_page`` — real pages mix both.  ``texts``, ``scale``, ``feather``, ``max_glyphs``, ``overlap_glyphs`` as there;
+        ``char_boxes[i]``: the region's character boxes in PAGE pixels (a column's top to bottom), or evenly spaced ones.
+        A column's cells (``columns.cell_cuts``) are each resized on their own to height 32 and laid side by side: the virtual strip
+        ``columns.virtual_strip``, an ordinary line from there on, so the networks see upright characters.  → uint8 RGB [s·H, s·W, 3] on the host: the
+        bytes of ``columns.compose_columns_host(image, lines, boxes, cuts, scale, feather)`` for the lines ``restore_lines`` gives for the virtual
+        strips (with ``columns.virtual_boxes``) and the horizontal crops.  With ``vertical`` all false these are ``restore_page``'s bytes.
+        The page is uploaded once and the virtual strips never exist on the host: ``mnet_lq_from_u8`` makes the background, ONE
+        ``mnet_column_gather_u8`` launch makes every window of every column (the horizontal crops travel beside them as in ``restore_page``), ALL
+        windows of ALL regions are restored as ONE batch and joined on the device, one ``mnet_paste_u8`` launch pastes the horizontal regions, ONE
+        ``mnet_column_paste_u8`` launch brings every restored character back to its cell — blended by one ramp along the column's outer edge, none
+        between cells — and ONE device→host copy brings the page back.
+        A region with no character or a character outside the alphabet keeps the background.  ValueError naming the region (and the character),
+        before anything is copied or launched: ``restore_page``'s refusals across both kinds of region, a count of character boxes other than the
+        text's length, an empty cell, a cell under 8 output rows, ``plan_windows``' refusals (a cell wider than 512 px at height 32).
+        ``details=True`` → ``(page, regions)``: per region ``restore_page``'s dict, for a column with ``cuts`` (page rows) and ``widths`` (its cells'
+        widths in the virtual strip) added; None where it kept the background.
+        Not covered: overlapping regions; vertical columns that are rotated or in perspective; right-to-left ordering of columns (the caller's);
+        curved text; detection and recognition; several pages in one launch."""
+        from . import columns as cl, long_lines, lq_device, lq_io, pages, quads as qd
+        who = "restore_page_columns"
+        if texts is None:
+            raise ValueError("%s needs texts: a window is a run of whole characters, and windows cut blind would cut characters in half" % who)
+        n = len(boxes)
+        if len(texts) != n or (char_boxes is not None and len(char_boxes) != n) or (vertical is not None and len(vertical) != n):
+            raise ValueError("%s: one text (one flag, and one list of character boxes, or None) per box expected (%d boxes, %d texts)" % (who, n, len(texts)))
+        image = np.asarray(image)
+        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3 or image.size == 0:
+            raise TypeError("%s: uint8 RGB HxWx3 page expected" % who)
+        H, W = int(image.shape[0]), int(image.shape[1])
+        n_cls = self.gan.TextGenerator.class_num
+        vertical = [True] * n if vertical is None else [bool(v) for v in vertical]
+        boxes = [pages.round_box(b, H, W) for b in boxes]
+        restored = [not script_skips(lq_io.label_tensor(t), n_cls) for t in texts]
+        cb = [None if char_boxes is None else char_boxes[i] for i in range(n)]
+        try:
+            pages.region_rects(H, W, boxes, restored, scale, feather)
+            cuts = [cl.cell_cuts(boxes[i], len(texts[i]), cb[i], region=i) if vertical[i] and restored[i] else None for i in range(n)]
+            rects = cl.check_columns(H, W, boxes, restored, cuts, scale, feather)
+        except ValueError as e:
+            raise ValueError("%s: %s" % (who, e)) from None
+        widths = [None if c is None else cl.cell_widths(b, c) for b, c in zip(boxes, cuts)]
+        sizes = [(b[3] - b[1], b[2] - b[0]) if w is None else (cl.LQ_H, sum(w)) for b, w in zip(boxes, widths)]
+        local = [cl.virtual_boxes(widths[i]) if widths[i] is not None else
+                 None if cb[i] is None else [[c[0] - b[0], c[1] - b[1], c[2] - b[0], c[3] - b[1]] for c in cb[i]] for i, b in enumerate(boxes)]
+        plans, labels, locs_rows, live = self._plan_lines(sizes, texts, local, max_glyphs, overlap_glyphs, who, "region")
+        out_ws = [None if p is None else long_lines.plan_out_w(p) for p in plans]
+        cols = [i for i in live if cuts[i] is not None]
+        columns = [(boxes[i], cuts[i], widths[i], plans[i]) for i in cols]
+        flat, where, head = [], {}, 0                                   # the horizontal windows' crops, at the head of the packed batch
+        for i in live:
+            if cuts[i] is None:
+                x1, y1, x2, y2 = boxes[i]
+                for k, p in enumerate(plans[i]):
+                    where[(i, k)] = ((y2 - y1, p.c1 - p.c0), head)
+                    flat.append(np.ascontiguousarray(image[y1:y2, x1 + p.c0:x1 + p.c1]).reshape(-1))
+                    head += flat[-1].size
+        cell_tab, shapes, offsets, nbytes = cl.gather_table(columns, head)                        # its refusals, before anything is copied
+        for (i, k), h_w, off in zip([(i, k) for i in cols for k in range(len(plans[i]))], shapes, offsets):
+            where[(i, k)] = (h_w, off)
+        page_d = torch.from_numpy(np.ascontiguousarray(image)).to(next(self.sr.parameters()).device)      # the one copy of the page
+        out = qd.enlarge(page_d, int(scale))
+        if live:
+            packed = torch.empty((nbytes,), dtype=torch.uint8, device=page_d.device)             # the ragged batch: the crops, then the columns' windows
+            if cols:
+                with ops.on_device(page_d):
+                    ops.column_gather_u8(page_d, ops.table_to_device(cell_tab, page_d.device), int(cell_tab["dw"].max()), cl.LQ_H, packed)
+            if head:
+                packed[:head].copy_(torch.from_numpy(np.concatenate(flat)))                   # the horizontal crops, as restore_page uploads them
+            order = [where[(i, k)] for i in live for k in range(len(plans[i]))]
+            prep = lq_device.prepare_packed(packed, [o[0] for o in order], [o[1] for o in order])
+            joined = self._restore_planned(prep.lq, labels, locs_rows, plans, live)
+            line_of = {i: l for l, i in enumerate(live)}
+            rows_ = [i for i in live if cuts[i] is None]
+            if rows_:
+                tab = pages.build_table(rects, [out_ws[i] if i in rows_ else None for i in range(n)], int(feather))
+                tab["line_index"] = [line_of[i] for i in rows_]
+                with ops.on_device(out):
+                    ops.paste_u8(joined, ops.table_to_device(tab, out.device), out)
+            cl.paste_columns(out, joined, [line_of[i] for i in cols], columns, [rects[i] for i in cols], int(feather))
+        page = out.cpu().numpy()                                                               # the one device→host copy
+        if not details:
+            return page
+        info = [None if p is None else dict(plan=p, out_w=w, rect=r) for p, w, r in zip(plans, out_ws, rects)]
+        for i in cols:
+            info[i].update(cuts=cuts[i], widths=widths[i])
+        return page, info
 
     @torch.no_grad()
     def _strips_from_images(self, images, texts, boxes, max_glyphs, preview, host_preview):
