@@ -6,10 +6,9 @@
 // translation unit — the expansion of the division keeps its own fused operations, which is what makes it correctly rounded), a bilinear mix in
 // integers, and for the paste the integer feather of page_blend.h.
 //
-// Launch shape (as paste_u8_kernel): 256 threads, a 64-column x 16-row tile of one descriptor's output, one thread per output pixel with 4 rows
-// each, x fastest.  The launcher does not see the device table, so the grid is n descriptors x the tiles of the largest one, whose size the
-// caller passes; a workgroup whose tile lies outside its descriptor returns before it loads anything.  The descriptor is read uniformly per
-// workgroup; sources are read with byte loads (3-byte pixels at any offset), no LDS is needed.
+// Launch shape: page_tile.h's tile over one descriptor's output; the grid is n descriptors x the tiles of the largest one, whose size the caller
+// passes; a workgroup whose tile lies outside its descriptor returns before it loads anything.  The descriptor is read uniformly per workgroup;
+// sources are read with byte loads (3-byte pixels at any offset), no LDS is needed.
 // Bounds: a descriptor is followed only if it passes the checks below (the list: include/marconet_hip_quad.h) — every workgroup of a descriptor
 // takes the same decision from the same bytes.  Crop: every page index is clamped into [0, page_h) x [0, page_w), every store lies in
 // [offset, offset + 3 w h) of dst, which lies inside [0, dst_bytes).  Paste: every atlas index is clamped into the foreground's rectangle, which
@@ -18,10 +17,9 @@
 #include "../../include/marconet_hip_quad.h"
 #include "quad_map.h"
 #include "page_blend.h"
+#include "page_tile.h"
 
 namespace {
-
-constexpr int QD_TX = 64, QD_TY = 16;      // tile: 64 columns x 16 rows, 256 threads x 4 rows each
 
 __device__ inline bool quad_finite9(const double* m) {
     bool ok = true;
@@ -33,21 +31,20 @@ __device__ inline bool quad_finite9(const double* m) {
 __global__ void __launch_bounds__(256) quad_crop_u8_kernel(const unsigned char* __restrict__ page, int page_h, int page_w,
                                                            const mnet_quad_crop* __restrict__ crops, int tiles_x, int tiles_y,
                                                            unsigned char* __restrict__ dst, long long dst_bytes) {
-    const int bid = (int)blockIdx.x;
-    const int tile_x = bid % tiles_x, tile_y = (bid / tiles_x) % tiles_y;
-    const mnet_quad_crop C = crops[bid / (tiles_x * tiles_y)];
+    const PtTile T = pt_tile(tiles_x, tiles_y);
+    const mnet_quad_crop C = crops[T.desc];
     const int w = C.w, h = C.h;
     const bool ok = w >= 1 && h >= 1 && C.c0 >= 0 && C.offset >= 0 && C.offset <= dst_bytes && (long long)w * h <= (dst_bytes - C.offset) / 3 &&
                     quad_finite9(C.m);
-    const int i0 = tile_x * QD_TX, j0 = tile_y * QD_TY;
+    const int i0 = T.x0, j0 = T.y0;
     if (!ok || i0 >= w || j0 >= h) return;               // uniform over the workgroup
-    const int t = (int)threadIdx.x, i = i0 + (t & (QD_TX - 1)), ty = t / QD_TX;
+    const int t = (int)threadIdx.x, i = i0 + (t & (PT_TX - 1)), ty = t / PT_TX;
     if (i >= w) return;
     const double x = LQ_DADD((double)((long long)C.c0 + i), 0.5);
     const size_t row_bytes = (size_t)page_w * 3;
     unsigned char* out = dst + C.offset;
 #pragma unroll
-    for (int r = 0; r < QD_TY / 4; ++r) {
+    for (int r = 0; r < PT_TY / 4; ++r) {
         const int j = j0 + ty + 4 * r;
         if (j >= h) break;
         const QuadPos p = quad_pos(C.m, x, LQ_DADD((double)j, 0.5));
@@ -68,16 +65,15 @@ __global__ void __launch_bounds__(256) quad_crop_u8_kernel(const unsigned char* 
 __global__ void __launch_bounds__(256) quad_paste_u8_kernel(const unsigned char* __restrict__ atlas, int atlas_h, int atlas_w,
                                                             const mnet_quad_region* __restrict__ regions, int tiles_x, int tiles_y,
                                                             unsigned char* page, int page_h, int page_w) {
-    const int bid = (int)blockIdx.x;
-    const int tile_x = bid % tiles_x, tile_y = (bid / tiles_x) % tiles_y;
-    const mnet_quad_region R = regions[bid / (tiles_x * tiles_y)];
+    const PtTile T = pt_tile(tiles_x, tiles_y);
+    const mnet_quad_region R = regions[T.desc];
     const int rw = R.rw, rh = R.rh, bw = R.bw, bh = R.bh;
     const bool ok = rw >= 1 && rh >= 1 && bw >= 1 && bh >= 1 && R.ax0 >= 0 && R.ay0 >= 0 && R.bx0 >= 0 && R.by0 >= 0 &&
                     (long long)R.ax0 + rw <= atlas_w && (long long)R.ay0 + rh <= atlas_h && (long long)R.bx0 + bw <= page_w &&
                     (long long)R.by0 + bh <= page_h && R.feather >= 0 && R.feather <= PAGE_MAX_FEATHER && quad_finite9(R.n);
-    const int i0 = tile_x * QD_TX, j0 = tile_y * QD_TY;
+    const int i0 = T.x0, j0 = T.y0;
     if (!ok || i0 >= bw || j0 >= bh) return;             // uniform over the workgroup
-    const int t = (int)threadIdx.x, i = i0 + (t & (QD_TX - 1)), ty = t / QD_TX;
+    const int t = (int)threadIdx.x, i = i0 + (t & (PT_TX - 1)), ty = t / PT_TX;
     if (i >= bw) return;
     const int X = R.bx0 + i;
     const double x = LQ_DADD((double)X, 0.5), frw = (double)rw, frh = (double)rh;
@@ -85,7 +81,7 @@ __global__ void __launch_bounds__(256) quad_paste_u8_kernel(const unsigned char*
     const size_t row_bytes = (size_t)atlas_w * 3;
     const unsigned char* fg0 = atlas + ((size_t)R.ay0 * atlas_w + (size_t)R.ax0) * 3;
 #pragma unroll
-    for (int r = 0; r < QD_TY / 4; ++r) {
+    for (int r = 0; r < PT_TY / 4; ++r) {
         const int j = j0 + ty + 4 * r;
         if (j >= bh) break;
         const int Y = R.by0 + j;
@@ -116,11 +112,10 @@ extern "C" int mnet_quad_crop_u8(const uint8_t* page, int32_t page_h, int32_t pa
     MNET_CHECK_ARG(page_h >= 1 && page_w >= 1 && n >= 1 && max_w >= 1 && max_h >= 1 && dst_bytes >= 1,
                    "quad_crop_u8: bad shape (page_h=%d, page_w=%d, n=%d, max_w=%d, max_h=%d, dst_bytes=%lld)", page_h, page_w, n, max_w, max_h, (long long)dst_bytes);
     MNET_CHECK_ALIGN((reinterpret_cast<uintptr_t>(crops) & 7) == 0, "quad_crop_u8: crops must be 8-byte aligned");
-    const long long tiles_x = ((long long)max_w + QD_TX - 1) / QD_TX, tiles_y = ((long long)max_h + QD_TY - 1) / QD_TY;
-    MNET_CHECK_ARG(tiles_x * tiles_y <= 0x7fffffffll && (long long)n * tiles_x * tiles_y <= 0x7fffffffll, "quad_crop_u8: batch too large (%d crops of %lld x %lld tiles)", n, tiles_x, tiles_y);
-    const long long grid = (long long)n * tiles_x * tiles_y;
-    hipLaunchKernelGGL(quad_crop_u8_kernel, dim3((unsigned)grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), page, page_h, page_w, crops,
-                       (int)tiles_x, (int)tiles_y, dst, (long long)dst_bytes);
+    const PtGrid g = pt_grid(n, max_w, max_h);
+    MNET_CHECK_ARG(g.blocks <= PT_MAX_BLOCKS, "quad_crop_u8: batch too large (%d crops of %lld x %lld tiles)", n, g.tiles_x, g.tiles_y);
+    hipLaunchKernelGGL(quad_crop_u8_kernel, dim3((unsigned)g.blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), page, page_h, page_w, crops,
+                       (int)g.tiles_x, (int)g.tiles_y, dst, (long long)dst_bytes);
     MNET_LAUNCH_CHECK("quad_crop_u8");
     return MNET_OK;
 }
@@ -131,11 +126,10 @@ extern "C" int mnet_quad_paste_u8(const uint8_t* atlas, int32_t atlas_h, int32_t
     MNET_CHECK_ARG(atlas_h >= 1 && atlas_w >= 1 && n >= 1 && max_bw >= 1 && max_bh >= 1 && page_h >= 1 && page_w >= 1,
                    "quad_paste_u8: bad shape (atlas_h=%d, atlas_w=%d, n=%d, max_bw=%d, max_bh=%d, page_h=%d, page_w=%d)", atlas_h, atlas_w, n, max_bw, max_bh, page_h, page_w);
     MNET_CHECK_ALIGN((reinterpret_cast<uintptr_t>(regions) & 7) == 0, "quad_paste_u8: regions must be 8-byte aligned");
-    const long long tiles_x = ((long long)max_bw + QD_TX - 1) / QD_TX, tiles_y = ((long long)max_bh + QD_TY - 1) / QD_TY;
-    MNET_CHECK_ARG(tiles_x * tiles_y <= 0x7fffffffll && (long long)n * tiles_x * tiles_y <= 0x7fffffffll, "quad_paste_u8: batch too large (%d regions of %lld x %lld tiles)", n, tiles_x, tiles_y);
-    const long long grid = (long long)n * tiles_x * tiles_y;
-    hipLaunchKernelGGL(quad_paste_u8_kernel, dim3((unsigned)grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), atlas, atlas_h, atlas_w, regions,
-                       (int)tiles_x, (int)tiles_y, page, page_h, page_w);
+    const PtGrid g = pt_grid(n, max_bw, max_bh);
+    MNET_CHECK_ARG(g.blocks <= PT_MAX_BLOCKS, "quad_paste_u8: batch too large (%d regions of %lld x %lld tiles)", n, g.tiles_x, g.tiles_y);
+    hipLaunchKernelGGL(quad_paste_u8_kernel, dim3((unsigned)g.blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), atlas, atlas_h, atlas_w, regions,
+                       (int)g.tiles_x, (int)g.tiles_y, page, page_h, page_w);
     MNET_LAUNCH_CHECK("quad_paste_u8");
     return MNET_OK;
 }

@@ -769,16 +769,23 @@ def stitch_u8(sr, lines, windows, out_w, out=None):
     return out
 
 
+_U8_FORMS = {1: "[bytes]", 3: "[H,W,3]", 4: "[L,rows,W,3]"}
+
+
+def _need_u8(who, name, t, dims):
+    """``t`` is a uint8 tensor of ``dims`` dimensions, the last of them 3 channels where there are several (TypeError)"""
+    if t.dtype != torch.uint8 or t.dim() != dims or (dims > 1 and t.shape[-1] != 3):
+        raise TypeError("%s: %s must be uint8 %s" % (who, name, _U8_FORMS[dims]))
+
+
 def paste_u8(lines, regions, page):
     """mnet_paste_u8 (the bytes of pages.paste_host, region by region): ``lines`` uint8 [L,rows,line_w,3] BGR (``stitch_u8``), ``regions`` uint8
     [R, sizeof(mnet_paste_region)] (``_lib.PasteRegion``), ``page`` uint8 [H,W,3] RGB holding the background — all on the device.  ``page`` is
     modified IN PLACE inside the regions' rectangles and returned; a region whose descriptor cannot be followed keeps the background."""
     lib = _lib.load()
     _need_cuda(lines, regions, page)
-    if lines.dtype != torch.uint8 or lines.dim() != 4 or lines.shape[3] != 3:
-        raise TypeError("paste_u8: lines must be uint8 [L,rows,W,3]")
-    if page.dtype != torch.uint8 or page.dim() != 3 or page.shape[2] != 3:
-        raise TypeError("paste_u8: page must be uint8 [H,W,3]")
+    _need_u8("paste_u8", "lines", lines, 4)
+    _need_u8("paste_u8", "page", page, 3)
     _check_table("paste_u8", "region table", regions, _lib.PasteRegion, 8)
     if regions.shape[0] < 1 or lines.numel() == 0 or page.numel() == 0:
         raise ValueError("paste_u8: empty batch (%d regions, lines %s, page %s)" % (regions.shape[0], list(lines.shape), list(page.shape)))
@@ -793,10 +800,8 @@ def quad_crop_u8(page, crops, max_w, max_h, dst):
     of the table.  ``dst`` is written inside the crops only and returned; a crop whose descriptor cannot be followed leaves its bytes as they are."""
     lib = _lib.load()
     _need_cuda(page, crops, dst)
-    if page.dtype != torch.uint8 or page.dim() != 3 or page.shape[2] != 3:
-        raise TypeError("quad_crop_u8: page must be uint8 [H,W,3]")
-    if dst.dtype != torch.uint8 or dst.dim() != 1:
-        raise TypeError("quad_crop_u8: dst must be uint8 [bytes]")
+    _need_u8("quad_crop_u8", "page", page, 3)
+    _need_u8("quad_crop_u8", "dst", dst, 1)
     _check_table("quad_crop_u8", "crop table", crops, _lib.QuadCrop, 8)
     if crops.shape[0] < 1 or page.numel() == 0 or dst.numel() == 0 or int(max_w) < 1 or int(max_h) < 1:
         raise ValueError("quad_crop_u8: empty batch (%d crops of at most %d x %d, page %s, %d bytes)"
@@ -813,10 +818,8 @@ def quad_paste_u8(atlas, regions, max_bw, max_bh, page):
     returned; a region whose descriptor cannot be followed keeps the background."""
     lib = _lib.load()
     _need_cuda(atlas, regions, page)
-    if atlas.dtype != torch.uint8 or atlas.dim() != 3 or atlas.shape[2] != 3:
-        raise TypeError("quad_paste_u8: atlas must be uint8 [H,W,3]")
-    if page.dtype != torch.uint8 or page.dim() != 3 or page.shape[2] != 3:
-        raise TypeError("quad_paste_u8: page must be uint8 [H,W,3]")
+    _need_u8("quad_paste_u8", "atlas", atlas, 3)
+    _need_u8("quad_paste_u8", "page", page, 3)
     _check_table("quad_paste_u8", "region table", regions, _lib.QuadRegion, 8)
     if regions.shape[0] < 1 or atlas.numel() == 0 or page.numel() == 0 or int(max_bw) < 1 or int(max_bh) < 1:
         raise ValueError("quad_paste_u8: empty batch (%d regions of at most %d x %d, atlas %s, page %s)"
@@ -833,10 +836,8 @@ def column_gather_u8(page, cells, max_dw, dst_h, dst):
     cell whose descriptor cannot be followed leaves its bytes as they are."""
     lib = _lib.load()
     _need_cuda(page, cells, dst)
-    if page.dtype != torch.uint8 or page.dim() != 3 or page.shape[2] != 3:
-        raise TypeError("column_gather_u8: page must be uint8 [H,W,3]")
-    if dst.dtype != torch.uint8 or dst.dim() != 1:
-        raise TypeError("column_gather_u8: dst must be uint8 [bytes]")
+    _need_u8("column_gather_u8", "page", page, 3)
+    _need_u8("column_gather_u8", "dst", dst, 1)
     _check_table("column_gather_u8", "cell table", cells, _lib.ColumnCell, 8)
     if cells.shape[0] < 1 or page.numel() == 0 or dst.numel() == 0 or int(max_dw) < 1 or int(dst_h) < 1:
         raise ValueError("column_gather_u8: empty batch (%d cells of at most %d x %d, page %s, %d bytes)"
@@ -852,10 +853,8 @@ def column_paste_u8(lines, cells, page):
     modified IN PLACE inside the cells' rectangles and returned; a cell whose descriptor cannot be followed keeps the background."""
     lib = _lib.load()
     _need_cuda(lines, cells, page)
-    if lines.dtype != torch.uint8 or lines.dim() != 4 or lines.shape[3] != 3:
-        raise TypeError("column_paste_u8: lines must be uint8 [L,rows,W,3]")
-    if page.dtype != torch.uint8 or page.dim() != 3 or page.shape[2] != 3:
-        raise TypeError("column_paste_u8: page must be uint8 [H,W,3]")
+    _need_u8("column_paste_u8", "lines", lines, 4)
+    _need_u8("column_paste_u8", "page", page, 3)
     _check_table("column_paste_u8", "cell table", cells, _lib.ColumnPaste, 8)
     if cells.shape[0] < 1 or lines.numel() == 0 or page.numel() == 0:
         raise ValueError("column_paste_u8: empty batch (%d cells, lines %s, page %s)" % (cells.shape[0], list(lines.shape), list(page.shape)))

@@ -6,8 +6,10 @@ same bytes from the device:
     resize_cubic_to           ``lq_io.resize_cubic``'s arithmetic to a GIVEN size: the intermediate → exactly the region's rectangle
     feather_blend             the integer blend of the line into the background near the rectangle's edge
     paste_host, compose_host  the pure-host definition of one region and of a page
-    build_table, compose_page the same bytes with one kernel launch (``mnet_paste_u8``) from the joined lines ``long_lines.compose_lines`` leaves on
-                              the device and the background ``ops.lq_from_u8(preview=True)`` makes of the page: ``lq_io.resize_cubic(page, s, s)``
+    build_table, paste_rects, the same bytes with one kernel launch (``mnet_paste_u8``) from the joined lines ``long_lines.compose_lines`` leaves on
+    enlarge, compose_page     the device and the background ``ops.lq_from_u8(preview=True)`` makes of the page: ``lq_io.resize_cubic(page, s, s)``
+    check_request,            what ``quads`` and ``columns`` share with this module: the refusals of scale and feather, and the intake of a host or
+    page_to_device            device page with its joined lines
 
 ``MarconetPipeline.restore_page`` ties them to the networks.  A region is an axis-aligned integer box [x1, y1, x2, y2] in page pixels: the reference
 handles regular layouts without perspective only; rotated and quadrilateral regions are ``quads``' (``MarconetPipeline.restore_page_quads``).  Out of
@@ -123,17 +125,23 @@ def round_box(box, page_h, page_w):
             min(max(int(math.ceil(x2)), 0), int(page_w)), min(max(int(math.ceil(y2)), 0), int(page_h))]
 
 
+def check_request(scale, feather, n_regions, n_lines, unit, units):
+    """the refusals every kind of region shares (ValueError): ``scale`` outside [1, 8] or ``feather`` outside [0, 1024] (integers), and a count of
+    lines other than that of the regions, which the message calls ``unit`` / ``units``"""
+    if int(scale) != scale or not 1 <= int(scale) <= MAX_SCALE:
+        raise ValueError("scale must be an integer in [1, %d], got %r" % (MAX_SCALE, scale))
+    if int(feather) != feather or not 0 <= int(feather) <= MAX_FEATHER:
+        raise ValueError("feather must be an integer in [0, %d], got %r" % (MAX_FEATHER, feather))
+    if n_lines != n_regions:
+        raise ValueError("one line (or None) per %s expected (%d %s, %d lines)" % (unit, n_regions, units, n_lines))
+
+
 def region_rects(page_h, page_w, boxes, restored, scale, feather, rows=ROW_H):
     """the refusals, all ValueError naming the region, and the regions' rectangles (x0, y0, rw, rh) in the enlarged page.  ``restored[i]``: region i
     has a line to paste (the others keep the background: only their box is checked).  Refused: ``scale`` outside [1, 8] or ``feather`` outside
     [0, 1024] (integers); a box that is not four integers with 0 ≤ x1 < x2 ≤ W and 0 ≤ y1 < y2 ≤ H; a restored region's rectangle under rows / 16
     rows; two restored regions whose rectangles overlap."""
-    if int(scale) != scale or not 1 <= int(scale) <= MAX_SCALE:
-        raise ValueError("scale must be an integer in [1, %d], got %r" % (MAX_SCALE, scale))
-    if int(feather) != feather or not 0 <= int(feather) <= MAX_FEATHER:
-        raise ValueError("feather must be an integer in [0, %d], got %r" % (MAX_FEATHER, feather))
-    if len(restored) != len(boxes):
-        raise ValueError("one line (or None) per box expected (%d boxes, %d lines)" % (len(boxes), len(restored)))
+    check_request(scale, feather, len(boxes), len(restored), "box", "boxes")
     s, rects = int(scale), []
     for i, b in enumerate(boxes):
         if len(b) != 4 or any(int(v) != v for v in b):
@@ -176,16 +184,66 @@ def compose_host(page, lines, boxes, scale=4, feather=8):
     return out
 
 
-def build_table(rects, out_ws, feather, rows=ROW_H):
-    """→ numpy record array of ``mnet_paste_region``, one per region with a line (``out_ws[i]`` is not None), in order: region i reads line number
-    (count of such regions before it), ``out_ws[i]`` columns wide, into ``rects[i]``"""
+def build_table(rects, out_ws, feather, rows=ROW_H, line_index=None):
+    """→ numpy record array of ``mnet_paste_region``, one per region with a line (``out_ws[i]`` is not None), in order: the l-th such region reads
+    line ``line_index[l]`` (default l: the count of such regions before it), ``out_ws[i]`` columns wide, into ``rects[i]``"""
     live = [i for i, w in enumerate(out_ws) if w is not None]
     tab = np.zeros((len(live),), dtype=np.dtype(_lib.PasteRegion))
     for l, i in enumerate(live):
         x0, y0, rw, rh = rects[i]
         k = box_factor(rh, rows)
-        tab[l] = (l, int(out_ws[i]), x0, y0, rw, rh, int(feather), k, axis_scale(rw, -(-int(out_ws[i]) // k)), axis_scale(rh, rows // k))
+        tab[l] = (l if line_index is None else int(line_index[l]), int(out_ws[i]), x0, y0, rw, rh, int(feather), k,
+                  axis_scale(rw, -(-int(out_ws[i]) // k)), axis_scale(rh, rows // k))
     return tab
+
+
+def paste_rects(out, joined, rects, out_ws, feather, line_index=None):
+    """``out``: the enlarged page on the device, changed IN PLACE; ``joined``: uint8 BGR [L, rows, line_w, 3] on the device; the regions of
+    ``build_table(rects, out_ws, feather, rows, line_index)``: ``paste_host``'s bytes.  One copy of the table, one launch for all regions."""
+    if any(w is not None for w in out_ws):
+        with ops.on_device(out):
+            ops.paste_u8(joined, ops.table_to_device(build_table(rects, out_ws, feather, int(joined.shape[1]), line_index), out.device), out)
+    return out
+
+
+def enlarge(page_d, s):
+    """``lq_io.resize_cubic(page, s, s)`` of a page on the device, bit for bit (``mnet_lq_from_u8``'s preview form) → uint8 RGB [s·H, s·W, 3]: one copy
+    of the descriptor, one launch"""
+    H, W = int(page_d.shape[0]), int(page_d.shape[1])
+    desc = np.zeros((1,), dtype=np.dtype(_lib.LqImage))
+    desc[0] = (0, H, W, s * W, 0, 1.0 / s)
+    with ops.on_device(page_d):
+        return ops.lq_from_u8(page_d.reshape(-1), ops.table_to_device(desc, page_d.device), s * H, s * W, preview=True)[0]
+
+
+def page_to_device(who, page, joined, out_ws, device, check):
+    """the intake of ``compose_page`` and ``quads.compose_page_quads``, which ``who`` names in the messages.  ``page``: uint8 RGB [H, W, 3], a host
+    array (copied once) or a device tensor (TypeError otherwise); ``joined`` / ``out_ws`` as ``compose_page`` takes them; ``check(H, W, rows)``: the
+    caller's own refusals → (its records of the regions, their heights in the enlarged page).  ValueError for lines that do not match the widths, a
+    width outside its line, rows the region's box factor does not divide, and a host page without lines or device — every refusal before anything
+    is copied.  → (the page on the device, rows, the records)"""
+    host = not torch.is_tensor(page)
+    if host:
+        page = torch.from_numpy(np.ascontiguousarray(_page_array(page)))
+    elif page.dtype != torch.uint8 or page.dim() != 3 or page.shape[2] != 3 or page.numel() == 0:
+        raise TypeError("uint8 RGB HxWx3 page expected")
+    n_live = sum(w is not None for w in out_ws)
+    if n_live and (joined is None or joined.dim() != 4 or joined.shape[0] != n_live or joined.dtype != torch.uint8):
+        raise ValueError("%s: one joined line per region with a width expected (%d widths, lines %s)"
+                         % (who, n_live, None if joined is None else list(joined.shape)))
+    rows = int(joined.shape[1]) if n_live else ROW_H
+    records, heights = check(int(page.shape[0]), int(page.shape[1]), rows)
+    for i, w in enumerate(out_ws):
+        if w is not None and not 1 <= int(w) <= joined.shape[2]:
+            raise ValueError("%s: region %d: line width %d outside [1, %d]" % (who, i, int(w), joined.shape[2]))
+        if w is not None and rows % box_factor(heights[i], rows):
+            raise ValueError("%s: region %d: lines of %d rows cannot be box-reduced by %d" % (who, i, rows, box_factor(heights[i], rows)))
+    if host:
+        device = torch.device(device) if device is not None else joined.device if n_live else None
+        if device is None:
+            raise ValueError("%s: a device is needed for a host page without lines" % who)
+        page = page.to(device)                                                             # the one copy of the pixels
+    return page, rows, records
 
 
 def compose_page(page, joined, out_ws, boxes, scale=4, feather=8, device=None):
@@ -194,35 +252,8 @@ def compose_page(page, joined, out_ws, boxes, scale=4, feather=8, device=None):
     no region has one; ``out_ws[i]``: the width of region i's line, None for a region that keeps the background; ``boxes[i]``: its integer box.
     → uint8 RGB [s·H, s·W, 3] on the device.  Every refusal of ``compose_host`` is raised before anything is copied or launched; then one copy of
     the page and one of each small table (the background's descriptor, the regions), one launch for the background and one for all regions."""
-    host = not torch.is_tensor(page)
-    if host:
-        page = torch.from_numpy(np.ascontiguousarray(_page_array(page)))
-    elif page.dtype != torch.uint8 or page.dim() != 3 or page.shape[2] != 3 or page.numel() == 0:
-        raise TypeError("uint8 RGB HxWx3 page expected")
-    H, W = int(page.shape[0]), int(page.shape[1])
-    n_live = sum(w is not None for w in out_ws)
-    if n_live and (joined is None or joined.dim() != 4 or joined.shape[0] != n_live or joined.dtype != torch.uint8):
-        raise ValueError("compose_page: one joined line per region with a width expected (%d widths, lines %s)"
-                         % (n_live, None if joined is None else list(joined.shape)))
-    rows = int(joined.shape[1]) if n_live else ROW_H
-    rects = region_rects(H, W, boxes, [w is not None for w in out_ws], scale, feather, rows)
-    for i, w in enumerate(out_ws):
-        if w is not None and not 1 <= int(w) <= joined.shape[2]:
-            raise ValueError("compose_page: region %d: line width %d outside [1, %d]" % (i, int(w), joined.shape[2]))
-        if w is not None and rows % box_factor(rects[i][3], rows):
-            raise ValueError("compose_page: region %d: lines of %d rows cannot be box-reduced by %d" % (i, rows, box_factor(rects[i][3], rows)))
-    s = int(scale)
-    if host:
-        device = torch.device(device) if device is not None else joined.device if n_live else None
-        if device is None:
-            raise ValueError("compose_page: a device is needed for a host page without lines")
-        page = page.to(device)                                                             # the one copy of the pixels
-    desc = np.zeros((1,), dtype=np.dtype(_lib.LqImage))
-    desc[0] = (0, H, W, s * W, 0, 1.0 / s)
-    desc_d = ops.table_to_device(desc, page.device)
-    regions_d = ops.table_to_device(build_table(rects, out_ws, feather, rows), page.device) if n_live else None
-    with ops.on_device(page):
-        out = ops.lq_from_u8(page.reshape(-1), desc_d, s * H, s * W, preview=True)[0]      # lq_io.resize_cubic(page, s, s), bit for bit
-        if n_live:
-            ops.paste_u8(joined, regions_d, out)
-    return out
+    def check(H, W, rows):
+        rects = region_rects(H, W, boxes, [w is not None for w in out_ws], scale, feather, rows)
+        return rects, [r[3] for r in rects]
+    page, _, rects = page_to_device("compose_page", page, joined, out_ws, device, check)
+    return paste_rects(enlarge(page, int(scale)), joined, rects, out_ws, feather)

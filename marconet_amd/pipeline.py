@@ -464,6 +464,38 @@ class MarconetPipeline:
         y, _ = self._restore_batch(lq, labels, locs_rows)
         return long_lines.compose_lines(y, [plans[i] for i in live])
 
+    def _page_front(self, who, image, n, texts, per_region, expected, units):
+        """the intake of the three ``restore_page*`` entry points, ``who``: the ``texts`` refusal, one text — and one entry of every list of
+        ``per_region`` that is not None — per region (``n`` of them; the message says ``expected`` of ``units``), a uint8 RGB HxWx3 page (TypeError)
+        → (the page as an array, per region whether it is restored: it has a character and none outside the alphabet)"""
+        from . import lq_io
+        if texts is None:
+            raise ValueError("%s needs texts: a window is a run of whole characters, and windows cut blind would cut characters in half" % who)
+        if len(texts) != n or any(l is not None and len(l) != n for l in per_region):
+            raise ValueError("%s: %s expected (%d %s, %d texts)" % (who, expected, n, units, len(texts)))
+        image = np.asarray(image)
+        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3 or image.size == 0:
+            raise TypeError("%s: uint8 RGB HxWx3 page expected" % who)
+        n_cls = self.gan.TextGenerator.class_num
+        return image, [not script_skips(lq_io.label_tensor(t), n_cls) for t in texts]
+
+    @staticmethod
+    def _page_finish(plans, compose, details, extra):
+        """the end of the three ``restore_page*`` entry points: ``compose(out_ws)`` → the finished page on the device, ``out_ws[i]`` the width of
+        region i's restored line (None where it keeps the background) → the page on the host, by ONE device→host copy; with ``details`` also per
+        restored region a dict with ``plan``, ``out_w`` and the keys of ``extra[i]``"""
+        from . import long_lines
+        out_ws = [None if p is None else long_lines.plan_out_w(p) for p in plans]
+        page = compose(out_ws).cpu().numpy()                                                  # the one device→host copy
+        if not details:
+            return page
+        return page, [None if p is None else dict(plan=p, out_w=w, **e) for p, w, e in zip(plans, out_ws, extra)]
+
+    @staticmethod
+    def _boxes_in_crop(char_boxes, box):
+        """character boxes in page pixels → in the crop of ``box`` (None stays None)"""
+        return None if char_boxes is None else [[c[0] - box[0], c[1] - box[1], c[2] - box[0], c[3] - box[1]] for c in char_boxes]
+
     @torch.no_grad()
     def restore_page(self, image, boxes, texts, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False):
         """A page and its text regions → the page enlarged ``scale`` times with every text line restored in place: uint8 RGB [s·H, s·W, 3] on the
@@ -483,31 +515,21 @@ class MarconetPipeline:
         ``out_w`` (the width of its restored line at height 128) and ``rect`` (x0, y0, rw, rh in the result), None where it kept the background.
         Not covered: overlapping regions; vertical columns that are rotated or in perspective (upright columns of stacked characters:
         ``restore_page_columns``) and curved text (rotated, quadrilateral and perspective regions: ``restore_page_quads``); detection and recognition (the caller's); several pages in one launch."""
-        from . import long_lines, lq_io, pages
-        if texts is None:
-            raise ValueError("restore_page needs texts: a window is a run of whole characters, and windows cut blind would cut characters in half")
-        if len(texts) != len(boxes) or (char_boxes is not None and len(char_boxes) != len(boxes)):
-            raise ValueError("restore_page: one text (and one list of character boxes, or None) per box expected (%d boxes, %d texts)" % (len(boxes), len(texts)))
-        image = np.asarray(image)
-        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3 or image.size == 0:
-            raise TypeError("restore_page: uint8 RGB HxWx3 page expected")
+        from . import pages
+        image, restored = self._page_front("restore_page", image, len(boxes), texts, [char_boxes],
+                                           "one text (and one list of character boxes, or None) per box", "boxes")
         H, W = int(image.shape[0]), int(image.shape[1])
-        n_cls = self.gan.TextGenerator.class_num
         boxes = [pages.round_box(b, H, W) for b in boxes]
-        restored = [not script_skips(lq_io.label_tensor(t), n_cls) for t in texts]
         try:
             rects = pages.region_rects(H, W, boxes, restored, scale, feather)
         except ValueError as e:
             raise ValueError("restore_page: %s" % e) from None
         crops = [image[b[1]:b[3], b[0]:b[2]] for b in boxes]
-        local = [None if char_boxes is None or char_boxes[i] is None else [[c[0] - b[0], c[1] - b[1], c[2] - b[0], c[3] - b[1]] for c in char_boxes[i]]
-                 for i, b in enumerate(boxes)]
+        local = [self._boxes_in_crop(None if char_boxes is None else char_boxes[i], b) for i, b in enumerate(boxes)]
         joined, plans, live = self._joined_lines(crops, texts, local, max_glyphs, overlap_glyphs, "restore_page", "region")
-        out_ws = [None if p is None else long_lines.plan_out_w(p) for p in plans]
-        page = pages.compose_page(image, joined, out_ws, boxes, scale, feather, device=next(self.sr.parameters()).device).cpu().numpy()   # the one device→host copy
-        if not details:
-            return page
-        return page, [None if p is None else dict(plan=p, out_w=w, rect=r) for p, w, r in zip(plans, out_ws, rects)]
+        dev = next(self.sr.parameters()).device
+        return self._page_finish(plans, lambda out_ws: pages.compose_page(image, joined, out_ws, boxes, scale, feather, device=dev), details,
+                                 [dict(rect=r) for r in rects])
 
     @torch.no_grad()
     def restore_page_quads(self, image, quads, texts, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False):
@@ -530,20 +552,11 @@ class MarconetPipeline:
         in the result) and ``size`` (rw, rh: the upright foreground's size), None where it kept the background.
         Not covered: overlapping regions; vertical columns that are rotated or in perspective (upright columns: ``restore_page_columns``); curved
         text; detection and recognition; several pages in one launch."""
-        from . import long_lines, lq_device, lq_io, quads as qd
-        if texts is None:
-            raise ValueError("restore_page_quads needs texts: a window is a run of whole characters, and windows cut blind would cut characters in half")
-        if len(texts) != len(quads) or (char_boxes is not None and len(char_boxes) != len(quads)):
-            raise ValueError("restore_page_quads: one text (and one list of character boxes, or None) per quadrilateral expected (%d quadrilaterals, "
-                             "%d texts)" % (len(quads), len(texts)))
-        image = np.asarray(image)
-        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3 or image.size == 0:
-            raise TypeError("restore_page_quads: uint8 RGB HxWx3 page expected")
-        H, W = int(image.shape[0]), int(image.shape[1])
-        n_cls = self.gan.TextGenerator.class_num
-        restored = [not script_skips(lq_io.label_tensor(t), n_cls) for t in texts]
+        from . import lq_device, quads as qd
+        image, restored = self._page_front("restore_page_quads", image, len(quads), texts, [char_boxes],
+                                           "one text (and one list of character boxes, or None) per quadrilateral", "quadrilaterals")
         try:
-            regions = qd.check_quads(H, W, quads, restored, scale, feather)
+            regions = qd.check_quads(int(image.shape[0]), int(image.shape[1]), quads, restored, scale, feather)
         except ValueError as e:
             raise ValueError("restore_page_quads: %s" % e) from None
         maps = [qd.quad_map(r["quad"], r["cw"], r["ch"]) for r in regions]
@@ -556,20 +569,19 @@ class MarconetPipeline:
                     raise ValueError("restore_page_quads: region %d: %s" % (i, e)) from None
         plans, labels, locs_rows, live = self._plan_lines([(r["ch"], r["cw"]) for r in regions], texts, local, max_glyphs, overlap_glyphs,
                                                           "restore_page_quads", "region")
-        out_ws = [None if p is None else long_lines.plan_out_w(p) for p in plans]
         wins = [(i, p) for i in live for p in plans[i]]
-        page_d = torch.from_numpy(np.ascontiguousarray(image)).to(next(self.sr.parameters()).device)      # the one copy of the pixels
-        out = qd.enlarge(page_d, int(scale))
-        if live:
-            sizes = [(p.c1 - p.c0, regions[i]["ch"]) for i, p in wins]
-            crops, offsets = qd.crop_quads(page_d, [maps[i] for i, _ in wins], sizes, [p.c0 for _, p in wins])
-            prep = lq_device.prepare_packed(crops, [(h, w) for w, h in sizes], offsets)
-            joined = self._restore_planned(prep.lq, labels, locs_rows, plans, live)
-            qd.paste_quads(out, joined, out_ws, regions, int(feather))
-        page = out.cpu().numpy()                                                               # the one device→host copy
-        if not details:
-            return page
-        return page, [None if p is None else dict(plan=p, out_w=w, quad=r["out_quad"], size=(r["rw"], r["rh"])) for p, w, r in zip(plans, out_ws, regions)]
+
+        def compose(out_ws):
+            page_d = torch.from_numpy(np.ascontiguousarray(image)).to(next(self.sr.parameters()).device)      # the one copy of the pixels
+            out = qd.enlarge(page_d, int(scale))
+            if live:
+                sizes = [(p.c1 - p.c0, regions[i]["ch"]) for i, p in wins]
+                crops, offsets = qd.crop_quads(page_d, [maps[i] for i, _ in wins], sizes, [p.c0 for _, p in wins])
+                prep = lq_device.prepare_packed(crops, [(h, w) for w, h in sizes], offsets)
+                joined = self._restore_planned(prep.lq, labels, locs_rows, plans, live)
+                qd.paste_quads(out, joined, out_ws, regions, int(feather))
+            return out
+        return self._page_finish(plans, compose, details, [dict(quad=r["out_quad"], size=(r["rw"], r["rh"])) for r in regions])
 
     @torch.no_grad()
     def restore_page_columns(self, image, boxes, texts, vertical=None, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False):
@@ -594,21 +606,13 @@ class MarconetPipeline:
         widths in the virtual strip) added; None where it kept the background.
         Not covered: overlapping regions; vertical columns that are rotated or in perspective; right-to-left ordering of columns (the caller's);
         curved text; detection and recognition; several pages in one launch."""
-        from . import columns as cl, long_lines, lq_device, lq_io, pages, quads as qd
-        who = "restore_page_columns"
-        if texts is None:
-            raise ValueError("%s needs texts: a window is a run of whole characters, and windows cut blind would cut characters in half" % who)
-        n = len(boxes)
-        if len(texts) != n or (char_boxes is not None and len(char_boxes) != n) or (vertical is not None and len(vertical) != n):
-            raise ValueError("%s: one text (one flag, and one list of character boxes, or None) per box expected (%d boxes, %d texts)" % (who, n, len(texts)))
-        image = np.asarray(image)
-        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3 or image.size == 0:
-            raise TypeError("%s: uint8 RGB HxWx3 page expected" % who)
+        from . import columns as cl, lq_device, pages
+        who, n = "restore_page_columns", len(boxes)
+        image, restored = self._page_front(who, image, n, texts, [char_boxes, vertical],
+                                           "one text (one flag, and one list of character boxes, or None) per box", "boxes")
         H, W = int(image.shape[0]), int(image.shape[1])
-        n_cls = self.gan.TextGenerator.class_num
         vertical = [True] * n if vertical is None else [bool(v) for v in vertical]
         boxes = [pages.round_box(b, H, W) for b in boxes]
-        restored = [not script_skips(lq_io.label_tensor(t), n_cls) for t in texts]
         cb = [None if char_boxes is None else char_boxes[i] for i in range(n)]
         try:
             pages.region_rects(H, W, boxes, restored, scale, feather)
@@ -618,50 +622,40 @@ class MarconetPipeline:
             raise ValueError("%s: %s" % (who, e)) from None
         widths = [None if c is None else cl.cell_widths(b, c) for b, c in zip(boxes, cuts)]
         sizes = [(b[3] - b[1], b[2] - b[0]) if w is None else (cl.LQ_H, sum(w)) for b, w in zip(boxes, widths)]
-        local = [cl.virtual_boxes(widths[i]) if widths[i] is not None else
-                 None if cb[i] is None else [[c[0] - b[0], c[1] - b[1], c[2] - b[0], c[3] - b[1]] for c in cb[i]] for i, b in enumerate(boxes)]
+        local = [cl.virtual_boxes(widths[i]) if widths[i] is not None else self._boxes_in_crop(cb[i], b) for i, b in enumerate(boxes)]
         plans, labels, locs_rows, live = self._plan_lines(sizes, texts, local, max_glyphs, overlap_glyphs, who, "region")
-        out_ws = [None if p is None else long_lines.plan_out_w(p) for p in plans]
-        cols = [i for i in live if cuts[i] is not None]
+        cols, lines_ = [i for i in live if cuts[i] is not None], [i for i in live if cuts[i] is None]
         columns = [(boxes[i], cuts[i], widths[i], plans[i]) for i in cols]
         flat, where, head = [], {}, 0                                   # the horizontal windows' crops, at the head of the packed batch
-        for i in live:
-            if cuts[i] is None:
-                x1, y1, x2, y2 = boxes[i]
-                for k, p in enumerate(plans[i]):
-                    where[(i, k)] = ((y2 - y1, p.c1 - p.c0), head)
-                    flat.append(np.ascontiguousarray(image[y1:y2, x1 + p.c0:x1 + p.c1]).reshape(-1))
-                    head += flat[-1].size
+        for i in lines_:
+            x1, y1, x2, y2 = boxes[i]
+            for k, p in enumerate(plans[i]):
+                where[(i, k)] = ((y2 - y1, p.c1 - p.c0), head)
+                flat.append(np.ascontiguousarray(image[y1:y2, x1 + p.c0:x1 + p.c1]).reshape(-1))
+                head += flat[-1].size
         cell_tab, shapes, offsets, nbytes = cl.gather_table(columns, head)                        # its refusals, before anything is copied
         for (i, k), h_w, off in zip([(i, k) for i in cols for k in range(len(plans[i]))], shapes, offsets):
             where[(i, k)] = (h_w, off)
-        page_d = torch.from_numpy(np.ascontiguousarray(image)).to(next(self.sr.parameters()).device)      # the one copy of the page
-        out = qd.enlarge(page_d, int(scale))
-        if live:
-            packed = torch.empty((nbytes,), dtype=torch.uint8, device=page_d.device)             # the ragged batch: the crops, then the columns' windows
-            if cols:
-                with ops.on_device(page_d):
-                    ops.column_gather_u8(page_d, ops.table_to_device(cell_tab, page_d.device), int(cell_tab["dw"].max()), cl.LQ_H, packed)
-            if head:
-                packed[:head].copy_(torch.from_numpy(np.concatenate(flat)))                   # the horizontal crops, as restore_page uploads them
-            order = [where[(i, k)] for i in live for k in range(len(plans[i]))]
-            prep = lq_device.prepare_packed(packed, [o[0] for o in order], [o[1] for o in order])
-            joined = self._restore_planned(prep.lq, labels, locs_rows, plans, live)
-            line_of = {i: l for l, i in enumerate(live)}
-            rows_ = [i for i in live if cuts[i] is None]
-            if rows_:
-                tab = pages.build_table(rects, [out_ws[i] if i in rows_ else None for i in range(n)], int(feather))
-                tab["line_index"] = [line_of[i] for i in rows_]
-                with ops.on_device(out):
-                    ops.paste_u8(joined, ops.table_to_device(tab, out.device), out)
-            cl.paste_columns(out, joined, [line_of[i] for i in cols], columns, [rects[i] for i in cols], int(feather))
-        page = out.cpu().numpy()                                                               # the one device→host copy
-        if not details:
-            return page
-        info = [None if p is None else dict(plan=p, out_w=w, rect=r) for p, w, r in zip(plans, out_ws, rects)]
-        for i in cols:
-            info[i].update(cuts=cuts[i], widths=widths[i])
-        return page, info
+
+        def compose(out_ws):
+            page_d = torch.from_numpy(np.ascontiguousarray(image)).to(next(self.sr.parameters()).device)      # the one copy of the page
+            out = pages.enlarge(page_d, int(scale))
+            if live:
+                packed = torch.empty((nbytes,), dtype=torch.uint8, device=page_d.device)         # the ragged batch: the crops, then the columns' windows
+                if cols:
+                    with ops.on_device(page_d):
+                        ops.column_gather_u8(page_d, ops.table_to_device(cell_tab, page_d.device), int(cell_tab["dw"].max()), cl.LQ_H, packed)
+                if head:
+                    packed[:head].copy_(torch.from_numpy(np.concatenate(flat)))               # the horizontal crops, as restore_page uploads them
+                order = [where[(i, k)] for i in live for k in range(len(plans[i]))]
+                prep = lq_device.prepare_packed(packed, [o[0] for o in order], [o[1] for o in order])
+                joined = self._restore_planned(prep.lq, labels, locs_rows, plans, live)
+                line_of = {i: l for l, i in enumerate(live)}
+                pages.paste_rects(out, joined, rects, [out_ws[i] if i in lines_ else None for i in range(n)], int(feather), [line_of[i] for i in lines_])
+                cl.paste_columns(out, joined, [line_of[i] for i in cols], columns, [rects[i] for i in cols], int(feather))
+            return out
+        return self._page_finish(plans, compose, details,
+                                 [dict(rect=r) if c is None else dict(rect=r, cuts=c, widths=w) for r, c, w in zip(rects, cuts, widths)])
 
     @torch.no_grad()
     def _strips_from_images(self, images, texts, boxes, max_glyphs, preview, host_preview):

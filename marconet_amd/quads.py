@@ -179,12 +179,7 @@ def check_quads(page_h, page_w, quads, restored, scale, feather, rows=ROW_H):
     cross product of successive edges > 0; a mirrored, counter-clockwise quadrilateral is named as such); a bounding box that misses the page; a
     restored region's foreground under rows / 16 rows; two restored regions whose interiors intersect.  A quadrilateral partly outside the page
     is allowed: the crop replicates the page's border and the paste is clipped."""
-    if int(scale) != scale or not 1 <= int(scale) <= pages.MAX_SCALE:
-        raise ValueError("scale must be an integer in [1, %d], got %r" % (pages.MAX_SCALE, scale))
-    if int(feather) != feather or not 0 <= int(feather) <= pages.MAX_FEATHER:
-        raise ValueError("feather must be an integer in [0, %d], got %r" % (pages.MAX_FEATHER, feather))
-    if len(restored) != len(quads):
-        raise ValueError("one line (or None) per quadrilateral expected (%d quadrilaterals, %d lines)" % (len(quads), len(restored)))
+    pages.check_request(scale, feather, len(quads), len(restored), "quadrilateral", "quadrilaterals")
     s, page_h, page_w, out = int(scale), int(page_h), int(page_w), []
     for i, q in enumerate(quads):
         try:
@@ -307,38 +302,14 @@ def compose_page_quads(page, joined, out_ws, quads, scale=4, feather=8, device=N
     """the device path of ``compose_quads_host``; the arguments are ``pages.compose_page``'s, with ``quads[i]`` in the place of the boxes.
     → uint8 RGB [s·H, s·W, 3] on the device.  Every refusal of ``compose_quads_host`` is raised before anything is copied or launched; then one
     copy of the page and one of each small table, one launch for the background, one for the foregrounds and one for all regions."""
-    host = not torch.is_tensor(page)
-    if host:
-        page = torch.from_numpy(np.ascontiguousarray(pages._page_array(page)))
-    elif page.dtype != torch.uint8 or page.dim() != 3 or page.shape[2] != 3 or page.numel() == 0:
-        raise TypeError("uint8 RGB HxWx3 page expected")
-    H, W = int(page.shape[0]), int(page.shape[1])
-    n_live = sum(w is not None for w in out_ws)
-    if n_live and (joined is None or joined.dim() != 4 or joined.shape[0] != n_live or joined.dtype != torch.uint8):
-        raise ValueError("compose_page_quads: one joined line per region with a width expected (%d widths, lines %s)"
-                         % (n_live, None if joined is None else list(joined.shape)))
-    rows = int(joined.shape[1]) if n_live else ROW_H
-    regions = check_quads(H, W, quads, [w is not None for w in out_ws], scale, feather, rows)
-    for i, w in enumerate(out_ws):
-        if w is not None and not 1 <= int(w) <= joined.shape[2]:
-            raise ValueError("compose_page_quads: region %d: line width %d outside [1, %d]" % (i, int(w), joined.shape[2]))
-        if w is not None and rows % pages.box_factor(regions[i]["rh"], rows):
-            raise ValueError("compose_page_quads: region %d: lines of %d rows cannot be box-reduced by %d" % (i, rows, pages.box_factor(regions[i]["rh"], rows)))
-    if host:
-        device = torch.device(device) if device is not None else joined.device if n_live else None
-        if device is None:
-            raise ValueError("compose_page_quads: a device is needed for a host page without lines")
-        page = page.to(device)                                                             # the one copy of the pixels
+    def check(H, W, rows):
+        regions = check_quads(H, W, quads, [w is not None for w in out_ws], scale, feather, rows)
+        return regions, [r["rh"] for r in regions]
+    page, rows, regions = pages.page_to_device("compose_page_quads", page, joined, out_ws, device, check)
     return paste_quads(enlarge(page, int(scale)), joined, out_ws, regions, int(feather), rows)
 
 
-def enlarge(page_d, s):
-    """``lq_io.resize_cubic(page, s, s)`` of a page on the device, bit for bit (``mnet_lq_from_u8``'s preview form) → uint8 RGB [s·H, s·W, 3]"""
-    H, W = int(page_d.shape[0]), int(page_d.shape[1])
-    desc = np.zeros((1,), dtype=np.dtype(_lib.LqImage))
-    desc[0] = (0, H, W, s * W, 0, 1.0 / s)
-    with ops.on_device(page_d):
-        return ops.lq_from_u8(page_d.reshape(-1), ops.table_to_device(desc, page_d.device), s * H, s * W, preview=True)[0]
+enlarge = pages.enlarge       # the background step is ``pages``'; the name stays here for its callers
 
 
 def char_boxes_in_crop(boxes, M, cw, ch):

@@ -344,9 +344,16 @@ def test_build_script_compiles_and_stamps_the_kernels():
     sh = open(os.path.join(CSRC, "build.sh")).read()
     assert re.search(r'^SRCS="[^"]*\bcolumn_kernels\b[^"]*"', sh, flags=re.M)
     assert 'column_kernels) echo "-ffp-contract=off" ;;' in sh
-    assert '[ "$1" = column_kernels ] && cat "$HERE/lq_taps.h" "$HERE/page_blend.h" "$HERE/../../include/marconet_hip_columns.h"' in sh
+    assert '[ "$1" = column_kernels ] && cat "$HERE/lq_taps.h" "$HERE/page_tile.h" "$HERE/../../include/marconet_hip_columns.h"' in sh
     src = open(os.path.join(CSRC, "column_kernels.hip")).read()
-    assert '#include "lq_taps.h"' in src and '#include "page_blend.h"' in src and "marconet_hip_columns.h" in src and src.count("lq_cubic_taps(") == 4
+    assert '#include "page_tile.h"' in src and "marconet_hip_columns.h" in src and src.count("pt_stage_taps(") == 1 and "mnet_column_gather_u8" in src
+    # the paste stands beside its twin in page_kernels.hip, which is built and stamped with the taps, the blend, the tile and this header
+    assert 'page_kernels) echo "-ffp-contract=off" ;;' in sh
+    assert '[ "$1" = page_kernels ] && cat "$HERE/lq_taps.h" "$HERE/page_blend.h" "$HERE/page_tile.h" "$HERE/../../include/marconet_hip_columns.h"' in sh
+    src = open(os.path.join(CSRC, "page_kernels.hip")).read()
+    assert '#include "page_tile.h"' in src and '#include "page_blend.h"' in src and "marconet_hip_columns.h" in src and "mnet_column_paste_u8" in src
+    tile = open(os.path.join(CSRC, "page_tile.h")).read()
+    assert '#include "lq_taps.h"' in tile and tile.count("lq_cubic_taps(") == 2
     lib = _lib.load()
     assert all(hasattr(lib, name) for name in _lib.COLUMN_SYMBOLS)
 

@@ -273,6 +273,57 @@ def test_unfollowable_paste_cell_keeps_the_background_and_its_neighbours_stand(p
     assert all((g == 0xCD).all() for g in guards)
 
 
+# ------------------------------------------------------------------------------------------------- the kernels and their twins
+# (rectangle (x0, y0, rw, rh) in the 150-row x 200-column page, src_w, line): disjoint.  Heights 70 / 30 / 16 take k = 1 / 4 / 8; 73 and 70 columns
+# are ragged under k = 4 and 8; widths 70 / 64 / 9: two x tiles, an exact tile edge, a sliver
+TWIN_REGIONS = (((3, 5, 70, 70), 75, 0), ((100, 10, 64, 30), 73, 1), ((180, 100, 9, 16), 70, 0))
+
+
+@pytest.mark.parametrize("feather", (0, 3, 40))                                                   # 40: more than half of every rectangle
+def test_a_paste_region_is_a_column_cell_with_a_trivial_slice_and_its_own_feather_rectangle(feather):
+    """mnet_paste_u8 and mnet_column_paste_u8 share one body: a ``PasteRegion`` table and the ``ColumnPaste`` table with src_x0 = 0 and the feather
+    rectangle = the cell's own give identical pages, and both give ``pages.paste_host``'s"""
+    from marconet_amd import _lib
+    rng = np.random.default_rng(20251022)
+    page = rng.integers(0, 256, (150, 200, 3), dtype=np.uint8)
+    lines = rng.integers(0, 256, (2, 128, 75, 3), dtype=np.uint8)
+    rects = [r for r, _, _ in TWIN_REGIONS]
+    reg = pages.build_table(rects, [w for _, w, _ in TWIN_REGIONS], feather, 128, line_index=[l for _, _, l in TWIN_REGIONS])
+    assert reg["k"].tolist() == [1, 4, 8] and reg["line_index"].tolist() == [0, 1, 0] and reg["src_w"].tolist() == [75, 73, 70]
+    cells = np.zeros((len(reg),), dtype=np.dtype(_lib.ColumnPaste))
+    for n, (r, (x0, y0, rw, rh)) in enumerate(zip(reg, rects)):
+        cells[n] = (int(r["line_index"]), 0, int(r["src_w"]), x0, y0, rw, rh, feather, int(r["k"]), x0, y0, rw, rh, 0, float(r["scale_x"]), float(r["scale_y"]))
+    want = page.copy()
+    for (rect, src_w, l) in TWIN_REGIONS:
+        pages.paste_host(want, lines[l, :, :src_w], rect, feather)
+    lines_d = torch.from_numpy(lines).to(DEV)
+    as_regions = ops.paste_u8(lines_d, ops.table_to_device(reg, DEV), torch.from_numpy(page).to(DEV)).cpu().numpy()
+    as_cells = ops.column_paste_u8(lines_d, ops.table_to_device(cells, DEV), torch.from_numpy(page).to(DEV)).cpu().numpy()
+    assert np.array_equal(as_regions, as_cells)
+    assert np.array_equal(as_regions, want) and np.array_equal(as_cells, want)
+    for x0, y0, rw, rh in rects:
+        assert not np.array_equal(want[y0:y0 + rh, x0:x0 + rw], page[y0:y0 + rh, x0:x0 + rw])
+
+
+def test_a_gather_cell_over_a_whole_image_at_one_step_is_the_preview_resize():
+    """mnet_column_gather_u8 and mnet_lq_from_u8 share one cubic: one cell that covers a 20 x 70 image at the step 1 / 2 on both axes gives the
+    preview form's bytes, and both give ``lq_io.resize_cubic(img, 2, 2)`` (= ``pages.resize_cubic_to(img, 140, 40)``: checked first, on the host)"""
+    from marconet_amd import _lib
+    img = np.random.default_rng(20251023).integers(0, 256, (20, 70, 3), dtype=np.uint8)
+    want = lq_io.resize_cubic(img, 2, 2)
+    assert want.shape == (40, 140, 3) and np.array_equal(pages.resize_cubic_to(img, 140, 40), want)
+    img_d = torch.from_numpy(img).to(DEV)
+    cell = np.zeros((1,), dtype=np.dtype(_lib.ColumnCell))
+    cell[0] = (0, 140, 0, 140, 0, 0, 70, 20, 0, 1.0 / 2, 1.0 / 2)
+    dst = torch.full((3 * 40 * 140,), 0xCD, dtype=torch.uint8, device=DEV)
+    gathered = ops.column_gather_u8(img_d, ops.table_to_device(cell, DEV), 140, 40, dst).cpu().numpy().reshape(40, 140, 3)
+    desc = np.zeros((1,), dtype=np.dtype(_lib.LqImage))
+    desc[0] = (0, 20, 70, 140, 0, 0.5)
+    preview = ops.lq_from_u8(img_d.reshape(-1), ops.table_to_device(desc, DEV), 40, 140, preview=True)[0].cpu().numpy()
+    assert np.array_equal(gathered, preview)
+    assert np.array_equal(gathered, want) and np.array_equal(preview, want)
+
+
 # ---------------------------------------------------------------------------------------------------------------- through the networks
 @pytest.fixture(scope="module")
 def pipe(ckpts):

@@ -349,9 +349,14 @@ def test_build_script_compiles_and_stamps_the_kernel():
     sh = open(os.path.join(CSRC, "build.sh")).read()
     assert re.search(r'^SRCS="[^"]*\bpage_kernels\b[^"]*"', sh, flags=re.M)
     assert 'panel_kernels) echo "-ffp-contract=off" ;; page_kernels) echo "-ffp-contract=off" ;;' in sh
-    assert '[ "$1" = page_kernels ] && cat "$HERE/lq_taps.h" "$HERE/page_blend.h"' in sh
+    assert '[ "$1" = page_kernels ] && cat "$HERE/lq_taps.h" "$HERE/page_blend.h" "$HERE/page_tile.h" "$HERE/../../include/marconet_hip_columns.h"' in sh
+    assert '[ "$1" = lq_kernels ] && cat "$HERE/lq_taps.h" "$HERE/page_tile.h"' in sh
     src = open(os.path.join(CSRC, "page_kernels.hip")).read()
-    assert '#include "lq_taps.h"' in src and '#include "page_blend.h"' in src and "lq_cubic_taps(" in src
+    assert '#include "page_tile.h"' in src and '#include "page_blend.h"' in src and "marconet_hip_columns.h" in src and "pt_stage_taps(" in src
+    # the taps are staged once, in the shared header, for this unit, lq_kernels and column_kernels
+    tile = open(os.path.join(CSRC, "page_tile.h")).read()
+    assert '#include "lq_taps.h"' in tile and tile.count("lq_cubic_taps(") == 2
+    assert '#include "page_tile.h"' in open(os.path.join(CSRC, "lq_kernels.hip")).read()
 
 
 def test_device_build_of_the_page_kernel_is_not_contracted(tmp_path):

@@ -479,9 +479,10 @@ def test_build_script_compiles_and_stamps_the_kernels():
     sh = open(os.path.join(CSRC, "build.sh")).read()
     assert re.search(r'^SRCS="[^"]*\bquad_kernels\b[^"]*"', sh, flags=re.M)
     assert 'quad_kernels) echo "-ffp-contract=off" ;;' in sh
-    assert ('[ "$1" = quad_kernels ] && cat "$HERE/quad_map.h" "$HERE/lq_taps.h" "$HERE/page_blend.h" "$HERE/../../include/marconet_hip_quad.h"') in sh
+    assert ('[ "$1" = quad_kernels ] && cat "$HERE/quad_map.h" "$HERE/lq_taps.h" "$HERE/page_blend.h" "$HERE/page_tile.h" '
+            '"$HERE/../../include/marconet_hip_quad.h"') in sh
     src = open(os.path.join(CSRC, "quad_kernels.hip")).read()
-    assert '#include "quad_map.h"' in src and '#include "page_blend.h"' in src and "marconet_hip_quad.h" in src
+    assert '#include "quad_map.h"' in src and '#include "page_blend.h"' in src and '#include "page_tile.h"' in src and "marconet_hip_quad.h" in src
     assert '#include "lq_taps.h"' in open(os.path.join(CSRC, "quad_map.h")).read()
     lib = _lib.load()
     assert all(hasattr(lib, name) for name in _lib.QUAD_SYMBOLS)
