@@ -13,7 +13,11 @@ reading order (top-left, top-right, bottom-right, bottom-left as the line is rea
 A region with a ``"box"`` may carry ``"vertical": true``: a column of upright characters stacked top to bottom (a shop sign, a couplet, a book
 spine), its ``"char_boxes"`` listed top to bottom.  If any region does, all regions go through ``MarconetPipeline.restore_page_columns``, the others as
 horizontal lines — ``restore_page``'s bytes for them.  A file that holds both a ``"vertical"`` region and a ``"quad"`` is refused: no entry point takes both.
-Not covered: overlapping regions (refused), vertical columns that are rotated or in perspective, curved text, several pages per call.
+A region may carry ``"polygon": [[x, y], ...]`` instead: the 2K points (4 to 66) of a curved line — the top side left to right in reading order, then the
+bottom side right to left, what a detector of curved text emits.  If any region does, all regions go through ``MarconetPipeline.restore_page_curves``,
+each box or quadrilateral as its four points — the same bytes for an integer box.  A file that holds both a ``"vertical"`` region and a ``"polygon"`` is
+refused, as with ``"quad"``.
+Not covered: overlapping regions (refused), vertical columns that are rotated, in perspective or curved, several pages per call.
 
 All regions are restored as one batch; the page is enlarged (cv2's INTER_CUBIC arithmetic) and every line resized, pasted and feathered on the GPU —
 only the PNG decode and encode run on the host.  Weights: ``$MARCONET_CKPT_DIR`` as in examples/restore_strips.py; without them the seeded
@@ -32,34 +36,45 @@ from marconet_amd.pipeline import MarconetPipeline                              
 
 
 def load_regions(path):
-    """→ (boxes, texts, char_boxes or None, quads or None, vertical or None): ``quads`` where any region carries "quad" — then every region's four
-    corners, a box turned into its own; ``vertical`` where any region carries "vertical": true — then one flag per region"""
+    """→ (boxes, texts, char_boxes or None, quads or None, vertical or None, polygons or None): ``quads`` where any region carries "quad" — then every
+    region's four corners, a box turned into its own; ``vertical`` where any region carries "vertical": true — then one flag per region; ``polygons``
+    where any region carries "polygon" — then every region's points, a box or a quadrilateral turned into its four"""
     with open(path, encoding="utf8") as f:
         regions = json.load(f)
     def well_formed(r):
-        if not isinstance(r, dict) or "text" not in r or ("box" in r) == ("quad" in r):
+        if not isinstance(r, dict) or "text" not in r or ("box" in r) + ("quad" in r) + ("polygon" in r) != 1:
             return False
         if not isinstance(r.get("vertical", False), bool) or ("vertical" in r and "box" not in r):
             return False
         if "box" in r:
             return isinstance(r["box"], list) and len(r["box"]) == 4 and all(isinstance(v, (int, float)) for v in r["box"])
-        return isinstance(r["quad"], list) and len(r["quad"]) == 4 and all(isinstance(p, list) and len(p) == 2 and all(isinstance(v, (int, float)) for v in p)
-                                                                           for p in r["quad"])
+        pts = r["quad"] if "quad" in r else r["polygon"]
+        return isinstance(pts, list) and (len(pts) == 4 if "quad" in r else len(pts) >= 4) and all(
+            isinstance(p, list) and len(p) == 2 and all(isinstance(v, (int, float)) for v in p) for p in pts)
 
     if not isinstance(regions, list) or not all(well_formed(r) for r in regions):
         raise SystemExit('restore_page.py: %s must hold a list of {"box": [x1, y1, x2, y2], "text": "..."} or {"quad": [[x, y], [x, y], [x, y], [x, y]], '
-                         '"text": "..."} objects (numbers; one of "box" and "quad" per region; "vertical": true or false beside a "box" only)' % path)
+                         '"text": "..."} or {"polygon": [[x, y], ...], "text": "..."} objects (numbers; one of "box", "quad" and "polygon" per region; '
+                         '"vertical": true or false beside a "box" only)' % path)
     vertical = [bool(r.get("vertical", False)) for r in regions] if any(r.get("vertical", False) for r in regions) else None
     if vertical is not None and any("quad" in r for r in regions):
         raise SystemExit('restore_page.py: %s holds a "vertical" region (%d) and a "quad" region (%d): vertical columns go through restore_page_columns, '
                          'which takes axis-aligned boxes only, and restore_page_quads has no vertical columns — give the quadrilateral as a "box", or restore '
                          'the two kinds in two calls' % (path, vertical.index(True), next(i for i, r in enumerate(regions) if "quad" in r)))
+    if vertical is not None and any("polygon" in r for r in regions):
+        raise SystemExit('restore_page.py: %s holds a "vertical" region (%d) and a "polygon" region (%d): vertical columns go through restore_page_columns, '
+                         'which takes axis-aligned boxes only, and restore_page_curves has no vertical columns — restore the two kinds in two calls'
+                         % (path, vertical.index(True), next(i for i, r in enumerate(regions) if "polygon" in r)))
     char_boxes = [r.get("char_boxes") for r in regions]
     quads = None
-    if any("quad" in r for r in regions):
-        quads = [r["quad"] if "quad" in r else [[r["box"][0], r["box"][1]], [r["box"][2], r["box"][1]], [r["box"][2], r["box"][3]], [r["box"][0], r["box"][3]]]
-                 for r in regions]
-    return [r.get("box") for r in regions], [r["text"] for r in regions], char_boxes if any(c is not None for c in char_boxes) else None, quads, vertical
+    if any("quad" in r or "polygon" in r for r in regions):
+        quads = [r["quad"] if "quad" in r else None if "polygon" in r else [[r["box"][0], r["box"][1]], [r["box"][2], r["box"][1]], [r["box"][2], r["box"][3]],
+                                                                     [r["box"][0], r["box"][3]]] for r in regions]
+    polygons = None
+    if any("polygon" in r for r in regions):
+        polygons = [r["polygon"] if "polygon" in r else q for r, q in zip(regions, quads)]
+    return ([r.get("box") for r in regions], [r["text"] for r in regions], char_boxes if any(c is not None for c in char_boxes) else None, quads, vertical,
+            polygons)
 
 
 def main():
@@ -71,7 +86,7 @@ def main():
     ap.add_argument("--feather", type=int, default=8, help="width in output pixels of the blend at a region's edge, 0..1024 (0: none)")
     ap.add_argument("--precision", default="fp16x2", choices=["fp16x2", "fp16x3", "fp16", "fp32"])
     a = ap.parse_args()
-    boxes, texts, char_boxes, quads, vertical = load_regions(a.regions)
+    boxes, texts, char_boxes, quads, vertical, polygons = load_regions(a.regions)
     if not torch.cuda.is_available():
         raise SystemExit("restore_page.py: no GPU visible — this package has no CPU path")
     from PIL import Image
@@ -81,6 +96,8 @@ def main():
     if vertical is not None:
         page, regions = pipe.restore_page_columns(lq_io.load_png(a.image), boxes, texts, vertical=vertical, char_boxes=char_boxes, scale=a.scale, feather=a.feather,
                                                   details=True)
+    elif polygons is not None:
+        page, regions = pipe.restore_page_curves(lq_io.load_png(a.image), polygons, texts, char_boxes=char_boxes, scale=a.scale, feather=a.feather, details=True)
     elif quads is not None:
         page, regions = pipe.restore_page_quads(lq_io.load_png(a.image), quads, texts, char_boxes=char_boxes, scale=a.scale, feather=a.feather, details=True)
     else:
@@ -91,6 +108,9 @@ def main():
         elif "cuts" in r:
             print("Region %d: a column of %d cell(s) in %d window(s), restored line %d px wide -> rectangle %s: %s"
                   % (i, len(r["widths"]), len(r["plan"]), r["out_w"], r["rect"], text))
+        elif polygons is not None:
+            print("Region %d: %d window(s), restored line %d px wide -> %d x %d along the %d-point polygon %s: %s"
+                  % (i, len(r["plan"]), r["out_w"], r["size"][0], r["size"][1], len(r["polygon"]), [list(p) for p in r["polygon"]], text))
         elif quads is not None:
             print("Region %d: %d window(s), restored line %d px wide -> %d x %d in quadrilateral %s: %s"
                   % (i, len(r["plan"]), r["out_w"], r["size"][0], r["size"][1], [list(p) for p in r["quad"]], text))

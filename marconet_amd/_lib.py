@@ -94,6 +94,22 @@ class ColumnPaste(ctypes.Structure):
                 ("k", c_int), ("fx0", c_int), ("fy0", c_int), ("fw", c_int), ("fh", c_int), ("reserved", c_int), ("scale_x", c_double), ("scale_y", c_double)]
 
 
+class CurveSeg(ctypes.Structure):
+    """mirror of ``mnet_curve_seg`` (include/marconet_hip_curve.h): one bilinear segment of a curved region"""
+    _fields_ = [("c", c_double * 8), ("u0", c_int), ("w", c_int), ("bx0", c_int), ("by0", c_int), ("bw", c_int), ("bh", c_int)]
+
+
+class CurveCrop(ctypes.Structure):
+    """mirror of ``mnet_curve_crop`` (include/marconet_hip_curve.h): one rectified window of mnet_curve_crop_u8's device table"""
+    _fields_ = [("offset", c_i64), ("w", c_int), ("h", c_int), ("c0", c_int), ("seg0", c_int), ("nseg", c_int), ("reserved", c_int)]
+
+
+class CurveRegion(ctypes.Structure):
+    """mirror of ``mnet_curve_region`` (include/marconet_hip_curve.h): one curved region of mnet_curve_paste_u8's device table"""
+    _fields_ = [("ax0", c_int), ("ay0", c_int), ("rw", c_int), ("rh", c_int), ("bx0", c_int), ("by0", c_int), ("bw", c_int), ("bh", c_int),
+                ("feather", c_int), ("seg0", c_int), ("nseg", c_int), ("reserved", c_int)]
+
+
 class CmpStats(ctypes.Structure):
     """mirror of ``mnet_cmp_stats`` (include/marconet_hip.h): one group's record of mnet_compare_stats"""
     _fields_ = [("max_abs_diff", c_float), ("max_abs_ref", c_float), ("max_abs_mode", c_float), ("reserved", c_int),
@@ -202,6 +218,12 @@ COLUMN_SYMBOLS = {
     "mnet_column_paste_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
 }
 
+# ... and the two include/marconet_hip_curve.h declares (curved text regions of a page, polygon strips: the gather in and the gather out)
+CURVE_SYMBOLS = {
+    "mnet_curve_crop_u8": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_i64, c_void_p]),
+    "mnet_curve_paste_u8": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
+}
+
 _lib = None
 
 
@@ -219,7 +241,7 @@ def load():
             "marconet_amd: %s not found — build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or marconet_amd/csrc/build.sh (there is no CPU/eager fallback)" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(UPFOLD_SYMBOLS.items()) + list(UPFOLD_F32Z_SYMBOLS.items()) + list(QUAD_SYMBOLS.items()) + list(COLUMN_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(UPFOLD_SYMBOLS.items()) + list(UPFOLD_F32Z_SYMBOLS.items()) + list(QUAD_SYMBOLS.items()) + list(COLUMN_SYMBOLS.items()) + list(CURVE_SYMBOLS.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is absent
         fn.restype = res
         fn.argtypes = args

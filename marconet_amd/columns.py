@@ -16,7 +16,7 @@ networks see an ordinary line.  Everything is stated in integers, with arithmeti
 
 A column is an integer axis-aligned box [x1, y1, x2, y2] in page pixels (``pages.round_box`` rounds a detector's box outward) whose text is read top
 to bottom.  ``MarconetPipeline.restore_page_columns`` ties it to the networks.  Out of scope: vertical columns that are rotated or in perspective,
-right-to-left ordering of the columns (the caller's), curved text, detection and recognition, several pages per launch.
+right-to-left ordering of the columns (the caller's), curved vertical columns (curved horizontal text: ``curves``), detection and recognition, several pages per launch.
 """
 import numpy as np
 import torch

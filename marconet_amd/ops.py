@@ -18,7 +18,7 @@ from .packing import MX_DTYPE, SPLIT_DTYPE, is_split, mx_weight_rows, new_tensor
 
 __all__ = ["conv2d", "linear", "nchw_to_nhwc", "nhwc_to_nchw", "upsample2x", "affine_act", "groupnorm_affine",
            "adain_crop_concat", "adain_crop_concat_gn", "glyph_scatter_affine", "layernorm", "token_mix", "attention", "pixelnorm",
-           "embed_gather", "demod", "argmax_rows", "convert", "fused_bias_act", "sr_postprocess", "lq_from_u8", "panel_u8", "paste_u8", "quad_crop_u8", "quad_paste_u8", "conv3x3_rgb", "torgb", "stats",
+           "embed_gather", "demod", "argmax_rows", "convert", "fused_bias_act", "sr_postprocess", "lq_from_u8", "panel_u8", "paste_u8", "quad_crop_u8", "quad_paste_u8", "curve_crop_u8", "curve_paste_u8", "conv3x3_rgb", "torgb", "stats",
            "pack_weights", "pack_wsq", "gather_rows", "style_rows", "nonfinite_flag", "compare_stats", "gn_partial_buffer", "can_emit_gn_partial", "groupnorm_affine_from_partial",
            "polyphase_plan", "upconv3x3_polyphase", "polyphase_ring_fix", "groupnorm_affine_from_partial_ring", "upfold_plan", "upfold3x3",
            "ACT_NONE", "ACT_RELU", "ACT_LRELU", "ACT_LRELU_SQRT2", "ACT_TANH", "ACT_GELU", "ACT_SIGMOID"]
@@ -826,6 +826,45 @@ def quad_paste_u8(atlas, regions, max_bw, max_bh, page):
                          % (regions.shape[0], int(max_bw), int(max_bh), list(atlas.shape), list(page.shape)))
     _lib.check(lib.mnet_quad_paste_u8(_p(atlas), int(atlas.shape[0]), int(atlas.shape[1]), _p(regions), int(regions.shape[0]), int(max_bw), int(max_bh),
                                       _p(page), int(page.shape[0]), int(page.shape[1]), _stream()), "mnet_quad_paste_u8")
+    return page
+
+
+def curve_crop_u8(page, crops, segs, max_w, max_h, dst):
+    """mnet_curve_crop_u8 (the bytes of curves.warp_crop_host, crop by crop): ``page`` uint8 [H,W,3] RGB, ``crops`` uint8 [n, sizeof(mnet_curve_crop)]
+    (``_lib.CurveCrop``), ``segs`` uint8 [S, sizeof(mnet_curve_seg)] (``_lib.CurveSeg``), ``dst`` uint8 [bytes], the flat buffer of the ragged batch —
+    all on the device; ``max_w`` / ``max_h``: the largest crop size of the table.  ``dst`` is written inside the crops only and returned; a crop whose
+    descriptor cannot be followed leaves its bytes as they are."""
+    lib = _lib.load()
+    _need_cuda(page, crops, segs, dst)
+    _need_u8("curve_crop_u8", "page", page, 3)
+    _need_u8("curve_crop_u8", "dst", dst, 1)
+    _check_table("curve_crop_u8", "crop table", crops, _lib.CurveCrop, 8)
+    _check_table("curve_crop_u8", "segment table", segs, _lib.CurveSeg, 8)
+    if crops.shape[0] < 1 or segs.shape[0] < 1 or page.numel() == 0 or dst.numel() == 0 or int(max_w) < 1 or int(max_h) < 1:
+        raise ValueError("curve_crop_u8: empty batch (%d crops of at most %d x %d, %d segments, page %s, %d bytes)"
+                         % (crops.shape[0], int(max_w), int(max_h), segs.shape[0], list(page.shape), dst.numel()))
+    _lib.check(lib.mnet_curve_crop_u8(_p(page), int(page.shape[0]), int(page.shape[1]), _p(crops), int(crops.shape[0]), _p(segs), int(segs.shape[0]),
+                                      int(max_w), int(max_h), _p(dst), int(dst.numel()), _stream()), "mnet_curve_crop_u8")
+    return dst
+
+
+def curve_paste_u8(atlas, regions, segs, max_bw, max_bh, page):
+    """mnet_curve_paste_u8 (the bytes of curves.warp_paste_host, region by region): ``atlas`` uint8 [AH,AW,3] RGB holding the regions' upright
+    foregrounds, ``regions`` uint8 [R, sizeof(mnet_curve_region)] (``_lib.CurveRegion``), ``segs`` uint8 [S, sizeof(mnet_curve_seg)]
+    (``_lib.CurveSeg``), ``page`` uint8 [H,W,3] RGB holding the background — all on the device; ``max_bw`` / ``max_bh``: the largest bounding box of
+    the table.  ``page`` is modified IN PLACE inside the regions and returned; a region whose descriptor cannot be followed keeps the background."""
+    lib = _lib.load()
+    _need_cuda(atlas, regions, segs, page)
+    _need_u8("curve_paste_u8", "atlas", atlas, 3)
+    _need_u8("curve_paste_u8", "page", page, 3)
+    _check_table("curve_paste_u8", "region table", regions, _lib.CurveRegion, 8)
+    _check_table("curve_paste_u8", "segment table", segs, _lib.CurveSeg, 8)
+    if regions.shape[0] < 1 or segs.shape[0] < 1 or atlas.numel() == 0 or page.numel() == 0 or int(max_bw) < 1 or int(max_bh) < 1:
+        raise ValueError("curve_paste_u8: empty batch (%d regions of at most %d x %d, %d segments, atlas %s, page %s)"
+                         % (regions.shape[0], int(max_bw), int(max_bh), segs.shape[0], list(atlas.shape), list(page.shape)))
+    _lib.check(lib.mnet_curve_paste_u8(_p(atlas), int(atlas.shape[0]), int(atlas.shape[1]), _p(regions), int(regions.shape[0]), _p(segs),
+                                       int(segs.shape[0]), int(max_bw), int(max_bh), _p(page), int(page.shape[0]), int(page.shape[1]), _stream()),
+               "mnet_curve_paste_u8")
     return page
 
 

@@ -514,7 +514,7 @@ class MarconetPipeline:
         ``texts`` is required, for ``restore_lines``' reason.  ``details=True`` → ``(page, regions)``: per region a dict with ``plan`` (its windows),
         ``out_w`` (the width of its restored line at height 128) and ``rect`` (x0, y0, rw, rh in the result), None where it kept the background.
         Not covered: overlapping regions; vertical columns that are rotated or in perspective (upright columns of stacked characters:
-        ``restore_page_columns``) and curved text (rotated, quadrilateral and perspective regions: ``restore_page_quads``); detection and recognition (the caller's); several pages in one launch."""
+        ``restore_page_columns``; rotated, quadrilateral and perspective regions: ``restore_page_quads``; curved text: ``restore_page_curves``); detection and recognition (the caller's); several pages in one launch."""
         from . import pages
         image, restored = self._page_front("restore_page", image, len(boxes), texts, [char_boxes],
                                            "one text (and one list of character boxes, or None) per box", "boxes")
@@ -551,7 +551,7 @@ class MarconetPipeline:
         border, the paste is clipped).  ``details=True`` → ``(page, regions)``: per region a dict with ``plan``, ``out_w``, ``quad`` (the corners
         in the result) and ``size`` (rw, rh: the upright foreground's size), None where it kept the background.
         Not covered: overlapping regions; vertical columns that are rotated or in perspective (upright columns: ``restore_page_columns``); curved
-        text; detection and recognition; several pages in one launch."""
+        vertical columns (curved text: ``restore_page_curves``); detection and recognition; several pages in one launch."""
         from . import lq_device, quads as qd
         image, restored = self._page_front("restore_page_quads", image, len(quads), texts, [char_boxes],
                                            "one text (and one list of character boxes, or None) per quadrilateral", "quadrilaterals")
@@ -584,6 +584,59 @@ class MarconetPipeline:
         return self._page_finish(plans, compose, details, [dict(quad=r["out_quad"], size=(r["rw"], r["rh"])) for r in regions])
 
     @torch.no_grad()
+    def restore_page_curves(self, image, polygons, texts, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False):
+        """``restore_page_quads`` for text regions that are curved strips — seals and round stamps, arched shop signs, logos, text on bottles and
+        banners: what a text detector emits as a polygon of 2K points (CTW1500, Total-Text and ArT style).  ``polygons[i]``: region i's 2K points
+        [[x, y]] in page pixels (any numbers), 2 <= K <= 33: the K top points left to right in reading order, then the K bottom points right to
+        left — clockwise with y down; for K = 2 exactly ``restore_page_quads``' corner order.  ``texts``, ``scale``, ``feather``, ``max_glyphs``,
+        ``overlap_glyphs`` as in ``restore_page``; ``char_boxes[i]``: the region's character boxes in PAGE pixels, boxes [x1, y1, x2, y2] or four
+        corners each (``curves.char_boxes_in_crop`` takes them into the rectified strip), or evenly spaced ones.
+        The region is the chain of the K - 1 quadrilaterals between facing points, each mapped bilinearly (the ruled surface between the two
+        polylines: ``curves``' head states the geometry), so the encoder sees a straight line and the restored line is bent back along the curve.
+        → uint8 RGB [s·H, s·W, 3] on the host: the bytes of ``curves.compose_curves_host(image, lines, polygons, scale, feather)`` for the lines
+        ``restore_lines`` gives for the rectified strips ``curves.warp_crop_host(image, segs, cw, ch)``.  For 4-point polygons that are
+        parallelograms, integer axis-aligned boxes included, these are ``restore_page_quads``' bytes.
+        The page is uploaded once and the strips never exist on the host: ``mnet_lq_from_u8`` makes the background, ONE ``mnet_curve_crop_u8``
+        launch rectifies every window of every region into the packed batch ``lq_device.prepare_packed`` turns into the encoder's input, all
+        windows are restored as ONE batch and joined on the device as in ``restore_lines``, one ``mnet_paste_u8`` launch brings every line to its
+        upright foreground, ONE ``mnet_curve_paste_u8`` launch pastes every region back along its curve and ONE device→host copy brings the page
+        back.  A region with no character or a character outside the alphabet keeps the background.  ValueError naming the region, before
+        anything is copied or launched: ``curves.check_curves``' refusals.  A region partly outside the page is allowed (the crop replicates the
+        page's border, the paste is clipped).  ``details=True`` → ``(page, regions)``: per region a dict with ``plan``, ``out_w``, ``polygon``
+        (the points in the result) and ``size`` (rw, rh: the upright foreground's size), None where it kept the background.
+        Not covered: overlapping regions; curved vertical columns (upright ones: ``restore_page_columns``); detection and recognition; several
+        pages in one launch."""
+        from . import curves as cv, lq_device
+        image, restored = self._page_front("restore_page_curves", image, len(polygons), texts, [char_boxes],
+                                           "one text (and one list of character boxes, or None) per polygon", "polygons")
+        try:
+            regions = cv.check_curves(int(image.shape[0]), int(image.shape[1]), polygons, restored, scale, feather)
+        except ValueError as e:
+            raise ValueError("restore_page_curves: %s" % e) from None
+        local = [None] * len(regions)
+        for i, r in enumerate(regions):
+            if char_boxes is not None and char_boxes[i] is not None:
+                try:
+                    local[i] = cv.char_boxes_in_crop(char_boxes[i], r["segs"], r["cw"], r["ch"])
+                except ValueError as e:
+                    raise ValueError("restore_page_curves: region %d: %s" % (i, e)) from None
+        plans, labels, locs_rows, live = self._plan_lines([(r["ch"], r["cw"]) for r in regions], texts, local, max_glyphs, overlap_glyphs,
+                                                          "restore_page_curves", "region")
+        wins = [(i, p) for i in live for p in plans[i]]
+
+        def compose(out_ws):
+            page_d = torch.from_numpy(np.ascontiguousarray(image)).to(next(self.sr.parameters()).device)      # the one copy of the pixels
+            out = cv.enlarge(page_d, int(scale))
+            if live:
+                sizes = [(p.c1 - p.c0, regions[i]["ch"]) for i, p in wins]
+                crops, offsets = cv.crop_curves(page_d, [regions[i]["segs"] for i, _ in wins], sizes, [p.c0 for _, p in wins])
+                prep = lq_device.prepare_packed(crops, [(h, w) for w, h in sizes], offsets)
+                joined = self._restore_planned(prep.lq, labels, locs_rows, plans, live)
+                cv.paste_curves(out, joined, out_ws, regions, int(feather))
+            return out
+        return self._page_finish(plans, compose, details, [dict(polygon=r["out_polygon"], size=(r["rw"], r["rh"])) for r in regions])
+
+    @torch.no_grad()
     def restore_page_columns(self, image, boxes, texts, vertical=None, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False):
         """``restore_page`` for pages with vertical text: columns of upright characters stacked top to bottom (shop signs, couplets, book spines,
         traditional typesetting).  ``boxes[i]``: region i's box [x1, y1, x2, y2] in page pixels, rounded outward as in ``restore_page``;
@@ -605,7 +658,7 @@ class MarconetPipeline:
         ``details=True`` → ``(page, regions)``: per region ``restore_page``'s dict, for a column with ``cuts`` (page rows) and ``widths`` (its cells'
         widths in the virtual strip) added; None where it kept the background.
         Not covered: overlapping regions; vertical columns that are rotated or in perspective; right-to-left ordering of columns (the caller's);
-        curved text; detection and recognition; several pages in one launch."""
+        curved vertical columns (curved horizontal text: ``restore_page_curves``); detection and recognition; several pages in one launch."""
         from . import columns as cl, lq_device, pages
         who, n = "restore_page_columns", len(boxes)
         image, restored = self._page_front(who, image, n, texts, [char_boxes, vertical],

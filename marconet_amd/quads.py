@@ -14,7 +14,7 @@ fp64, what "the crop of a quadrilateral" and "the line pasted into a quadrilater
 A region is four corners [[x, y]] x 4 in page pixels (pixel i covers [i, i + 1)), in the text's own reading order: top-left, top-right,
 bottom-right, bottom-left of the line as it is read — a line rotated by 90 degrees is a quadrilateral whose first corner is elsewhere.  For an
 integer axis-aligned box all of this is ``pages``' own bytes; for its right-angle rotations it is ``np.rot90`` of them.  ``MarconetPipeline.
-restore_page_quads`` ties it to the networks.  Out of scope: vertical columns that are rotated or in perspective (upright ones: ``columns``), curved text, detection and
+restore_page_quads`` ties it to the networks.  Out of scope: vertical columns that are rotated or in perspective (upright ones: ``columns``), curved vertical columns (curved text: ``curves``), detection and
 recognition, several pages per launch.
 """
 import math
