@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """A page and its text-line boxes in, the enlarged page with every text line restored in place out (MarconetPipeline.restore_page).
 
-    python examples/restore_page.py -i page.png -r regions.json -o out.png [--scale 4] [--feather 8] [--precision fp16x2]
+    python examples/restore_page.py -i page.png -r regions.json -o out.png [--scale 4] [--feather 8] [--overlap refuse] [--precision fp16x2]
 
 ``regions.json`` is a list of ``{"box": [x1, y1, x2, y2], "text": "...", "char_boxes": [[x1, y1, x2, y2], ...]}``: a text line's box in page pixels
 (axis-aligned; numbers that are not integers are rounded outward), its characters, and — optionally — its character boxes in page pixels (evenly
@@ -17,7 +17,11 @@ A region may carry ``"polygon": [[x, y], ...]`` instead: the 2K points (4 to 66)
 bottom side right to left, what a detector of curved text emits.  If any region does, all regions go through ``MarconetPipeline.restore_page_curves``,
 each box or quadrilateral as its four points — the same bytes for an integer box.  A file that holds both a ``"vertical"`` region and a ``"polygon"`` is
 refused, as with ``"quad"``.
-Not covered: overlapping regions (refused), vertical columns that are rotated, in perspective or curved, several pages per call.
+Two regions that share a pixel are refused by default.  ``--overlap order`` pastes overlapping regions in the file's order instead (painter's order: a later
+region is blended, under its own feather ramp, over the earlier ones) — stacked lines whose outward-rounded boxes share a row, a sign's column over the
+line next to it.  It applies to ``"box"`` regions, ``"vertical"`` ones included; a file with a ``"quad"`` or a ``"polygon"`` is refused with it: those kinds
+still refuse overlaps.
+Not covered: overlapping quadrilateral and curved regions, vertical columns that are rotated, in perspective or curved, several pages per call.
 
 All regions are restored as one batch; the page is enlarged (cv2's INTER_CUBIC arithmetic) and every line resized, pasted and feathered on the GPU —
 only the PNG decode and encode run on the host.  Weights: ``$MARCONET_CKPT_DIR`` as in examples/restore_strips.py; without them the seeded
@@ -84,9 +88,14 @@ def main():
     ap.add_argument("-o", "--output", type=str, required=True)
     ap.add_argument("--scale", type=int, default=4, help="integer enlargement of the page, 1..8")
     ap.add_argument("--feather", type=int, default=8, help="width in output pixels of the blend at a region's edge, 0..1024 (0: none)")
+    ap.add_argument("--overlap", default="refuse", choices=["refuse", "order"],
+                    help="order: overlapping box regions are pasted in the file's order (a later one over the earlier ones); refuse: they are an error")
     ap.add_argument("--precision", default="fp16x2", choices=["fp16x2", "fp16x3", "fp16", "fp32"])
     a = ap.parse_args()
     boxes, texts, char_boxes, quads, vertical, polygons = load_regions(a.regions)
+    if a.overlap == "order" and (quads is not None or polygons is not None):
+        raise SystemExit('restore_page.py: --overlap order applies to "box" regions ("vertical" ones included); %s holds a "quad" or a "polygon", and '
+                         'quadrilateral and curved regions still refuse overlaps' % a.regions)
     if not torch.cuda.is_available():
         raise SystemExit("restore_page.py: no GPU visible — this package has no CPU path")
     from PIL import Image
@@ -95,13 +104,14 @@ def main():
     pipe = MarconetPipeline(*checkpoints.build_networks(sde, sdg, sds, "cuda"), precision=a.precision)
     if vertical is not None:
         page, regions = pipe.restore_page_columns(lq_io.load_png(a.image), boxes, texts, vertical=vertical, char_boxes=char_boxes, scale=a.scale, feather=a.feather,
-                                                  details=True)
+                                                  details=True, overlap=a.overlap)
     elif polygons is not None:
         page, regions = pipe.restore_page_curves(lq_io.load_png(a.image), polygons, texts, char_boxes=char_boxes, scale=a.scale, feather=a.feather, details=True)
     elif quads is not None:
         page, regions = pipe.restore_page_quads(lq_io.load_png(a.image), quads, texts, char_boxes=char_boxes, scale=a.scale, feather=a.feather, details=True)
     else:
-        page, regions = pipe.restore_page(lq_io.load_png(a.image), boxes, texts, char_boxes=char_boxes, scale=a.scale, feather=a.feather, details=True)
+        page, regions = pipe.restore_page(lq_io.load_png(a.image), boxes, texts, char_boxes=char_boxes, scale=a.scale, feather=a.feather, details=True,
+                                          overlap=a.overlap)
     for i, (r, text) in enumerate(zip(regions, texts)):
         if r is None:
             print("Region %d keeps the page's pixels (no character, or a character outside the alphabet): %r" % (i, text))

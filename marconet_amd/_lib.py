@@ -94,6 +94,11 @@ class ColumnPaste(ctypes.Structure):
                 ("k", c_int), ("fx0", c_int), ("fy0", c_int), ("fw", c_int), ("fh", c_int), ("reserved", c_int), ("scale_x", c_double), ("scale_y", c_double)]
 
 
+class TileSpan(ctypes.Structure):
+    """mirror of ``mnet_tile_span`` (include/marconet_hip_ordered.h): one 64 x 16 tile of the page in mnet_paste_ordered_u8's span array"""
+    _fields_ = [("first", c_int), ("count", c_int)]
+
+
 class CurveSeg(ctypes.Structure):
     """mirror of ``mnet_curve_seg`` (include/marconet_hip_curve.h): one bilinear segment of a curved region"""
     _fields_ = [("c", c_double * 8), ("u0", c_int), ("w", c_int), ("bx0", c_int), ("by0", c_int), ("bw", c_int), ("bh", c_int)]
@@ -224,6 +229,11 @@ CURVE_SYMBOLS = {
     "mnet_curve_paste_u8": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
 }
 
+# ... and the one include/marconet_hip_ordered.h declares (overlapping regions and cells of a page pasted in the caller's order, by page tile)
+ORDERED_SYMBOLS = {
+    "mnet_paste_ordered_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
+}
+
 _lib = None
 
 
@@ -241,7 +251,7 @@ def load():
             "marconet_amd: %s not found — build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or marconet_amd/csrc/build.sh (there is no CPU/eager fallback)" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(UPFOLD_SYMBOLS.items()) + list(UPFOLD_F32Z_SYMBOLS.items()) + list(QUAD_SYMBOLS.items()) + list(COLUMN_SYMBOLS.items()) + list(CURVE_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(UPFOLD_SYMBOLS.items()) + list(UPFOLD_F32Z_SYMBOLS.items()) + list(QUAD_SYMBOLS.items()) + list(COLUMN_SYMBOLS.items()) + list(CURVE_SYMBOLS.items()) + list(ORDERED_SYMBOLS.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is absent
         fn.restype = res
         fn.argtypes = args

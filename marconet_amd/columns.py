@@ -121,15 +121,15 @@ def paste_column_host(page_up, line_bgr, rect, cuts, widths, feather):
 
 
 # ------------------------------------------------------------------------------------------------------------------------- the refusals
-def check_columns(page_h, page_w, boxes, restored, cuts_per_region, scale, feather, rows=ROW_H):
+def check_columns(page_h, page_w, boxes, restored, cuts_per_region, scale, feather, rows=ROW_H, overlap="refuse"):
     """the refusals, all ValueError naming the region (and the character where there is one), and the regions' rectangles (x0, y0, rw, rh) in the
     enlarged page.  ``cuts_per_region[i]``: the cuts of region i where it is a column, None where it is a horizontal line.  Refused: everything
     ``pages.region_rects`` refuses (scale, feather, a box that is empty or outside the page, a rectangle under rows / 16 rows, two restored regions
-    that overlap — across both kinds of region); for a restored column, cuts that do not run from y1 to y2 or do not increase strictly, and a cell
+    that overlap — across both kinds of region, unless ``overlap="order"``: ``pages``' head); for a restored column, cuts that do not run from y1 to y2 or do not increase strictly, and a cell
     under rows / 16 output rows (16 s h_j < rows: the box reduction stops at 8)."""
     if len(cuts_per_region) != len(boxes):
         raise ValueError("one list of cuts (or None) per box expected (%d boxes, %d lists)" % (len(boxes), len(cuts_per_region)))
-    rects = pages.region_rects(page_h, page_w, boxes, restored, scale, feather, rows)
+    rects = pages.region_rects(page_h, page_w, boxes, restored, scale, feather, rows, overlap)
     s = int(scale)
     for i, cuts in enumerate(cuts_per_region):
         if cuts is None or not restored[i]:
@@ -146,15 +146,15 @@ def check_columns(page_h, page_w, boxes, restored, cuts_per_region, scale, feath
 
 
 # ------------------------------------------------------------------------------------------------------------------- the definition
-def compose_columns_host(page, lines, boxes, cuts_per_region, scale=4, feather=8):
+def compose_columns_host(page, lines, boxes, cuts_per_region, scale=4, feather=8, overlap="refuse"):
     """the definition of a page: ``page`` uint8 RGB [H, W, 3]; ``boxes[i]`` region i's integer box; ``cuts_per_region[i]`` its cuts where it is a
     column (``cell_cuts``), None where it is a horizontal line; ``lines[i]``: its restored line, uint8 BGR [rows, w, 3] — for a column
     ``MarconetPipeline.restore_lines`` of ``virtual_strip(page, box, cuts)`` with ``virtual_boxes``, for a line that of the crop — or None for a
     region that keeps the background → uint8 RGB [s·H, s·W, 3]: ``lq_io.resize_cubic(page, s, s)`` with ``paste_column_host`` of every column and
-    ``pages.paste_host`` of every line."""
+    ``pages.paste_host`` of every line, in list order — which only shows where ``overlap="order"`` lets regions overlap (``pages``' head)."""
     page = pages._page_array(page)
     rows = next((int(np.shape(l)[0]) for l in lines if l is not None), ROW_H)
-    rects = check_columns(page.shape[0], page.shape[1], boxes, [l is not None for l in lines], cuts_per_region, scale, feather, rows)
+    rects = check_columns(page.shape[0], page.shape[1], boxes, [l is not None for l in lines], cuts_per_region, scale, feather, rows, overlap)
     out = lq_io.resize_cubic(page, int(scale), int(scale))
     for line, rect, box, cuts in zip(lines, rects, boxes, cuts_per_region):
         if line is None:
@@ -227,10 +227,29 @@ def paste_columns(out, joined, line_index, columns, rects, feather):
     if not columns:
         return out
     rows = int(joined.shape[1])
-    for c, (_, _, widths, _) in enumerate(columns):
-        if not 0 <= int(line_index[c]) < joined.shape[0] or (rows // LQ_H) * cell_offsets(widths)[-1] > joined.shape[2]:
-            raise ValueError("paste_columns: column %d: line %d of %d columns does not lie inside the lines %s" % (c, int(line_index[c]), (rows // LQ_H) * cell_offsets(widths)[-1], list(joined.shape)))
+    _check_lines("paste_columns", joined, line_index, columns)
     tab = paste_table(columns, line_index, rects, feather, rows)
     with ops.on_device(out):
         ops.column_paste_u8(joined, ops.table_to_device(tab, out.device), out)
     return out
+
+
+def _check_lines(who, joined, line_index, columns):
+    rows = int(joined.shape[1])
+    for c, (_, _, widths, _) in enumerate(columns):
+        if not 0 <= int(line_index[c]) < joined.shape[0] or (rows // LQ_H) * cell_offsets(widths)[-1] > joined.shape[2]:
+            raise ValueError("%s: column %d: line %d of %d columns does not lie inside the lines %s" % (who, c, int(line_index[c]), (rows // LQ_H) * cell_offsets(widths)[-1], list(joined.shape)))
+
+
+def mixed_table(joined, regions, feather):
+    """one table for ``pages.paste_ordered``: ``regions`` in paste order, region r = (its line's index in ``joined``, its rectangle in the enlarged
+    page, the width of its line — a horizontal line — or its column as ``gather_table`` takes it) → record array of ``mnet_column_paste``: a line as
+    ``pages.as_cell`` of ``pages.build_table``'s record, a column as ``paste_table``'s cells, consecutive.  ``paste_columns``' refusals."""
+    rows, parts = int(joined.shape[1]), []
+    for l, rect, what in regions:
+        if isinstance(what, tuple):
+            _check_lines("mixed_table", joined, [l], [what])
+            parts.append(paste_table([what], [l], [rect], feather, rows))
+        else:
+            parts.append(pages.as_cell(pages.build_table([rect], [int(what)], feather, rows, [l])))
+    return np.concatenate(parts) if parts else np.zeros((0,), dtype=np.dtype(_lib.ColumnPaste))

@@ -18,7 +18,7 @@ from .packing import MX_DTYPE, SPLIT_DTYPE, is_split, mx_weight_rows, new_tensor
 
 __all__ = ["conv2d", "linear", "nchw_to_nhwc", "nhwc_to_nchw", "upsample2x", "affine_act", "groupnorm_affine",
            "adain_crop_concat", "adain_crop_concat_gn", "glyph_scatter_affine", "layernorm", "token_mix", "attention", "pixelnorm",
-           "embed_gather", "demod", "argmax_rows", "convert", "fused_bias_act", "sr_postprocess", "lq_from_u8", "panel_u8", "paste_u8", "quad_crop_u8", "quad_paste_u8", "curve_crop_u8", "curve_paste_u8", "conv3x3_rgb", "torgb", "stats",
+           "embed_gather", "demod", "argmax_rows", "convert", "fused_bias_act", "sr_postprocess", "lq_from_u8", "panel_u8", "paste_u8", "quad_crop_u8", "quad_paste_u8", "curve_crop_u8", "curve_paste_u8", "paste_ordered_u8", "conv3x3_rgb", "torgb", "stats",
            "pack_weights", "pack_wsq", "gather_rows", "style_rows", "nonfinite_flag", "compare_stats", "gn_partial_buffer", "can_emit_gn_partial", "groupnorm_affine_from_partial",
            "polyphase_plan", "upconv3x3_polyphase", "polyphase_ring_fix", "groupnorm_affine_from_partial_ring", "upfold_plan", "upfold3x3",
            "ACT_NONE", "ACT_RELU", "ACT_LRELU", "ACT_LRELU_SQRT2", "ACT_TANH", "ACT_GELU", "ACT_SIGMOID"]
@@ -899,6 +899,39 @@ def column_paste_u8(lines, cells, page):
         raise ValueError("column_paste_u8: empty batch (%d cells, lines %s, page %s)" % (cells.shape[0], list(lines.shape), list(page.shape)))
     _lib.check(lib.mnet_column_paste_u8(_p(lines), int(lines.shape[0]), int(lines.shape[1]), int(lines.shape[2]), _p(cells), int(cells.shape[0]), _p(page),
                                         int(page.shape[0]), int(page.shape[1]), _stream()), "mnet_column_paste_u8")
+    return page
+
+
+def page_tiles(page_h, page_w):
+    """the count of 64 x 16 tiles of a page, row-major from its origin (csrc/page_tile.h's pt_grid(1, page_w, page_h)) → (tiles_x, tiles_y)"""
+    return -(-int(page_w) // 64), -(-int(page_h) // 16)
+
+
+def paste_ordered_u8(lines, cells, spans, order, page):
+    """mnet_paste_ordered_u8 (the bytes of pages.paste_host / columns.paste_column_host applied cell after cell in the table's order, overlaps
+    included): ``lines`` uint8 [L,rows,line_w,3] BGR (``stitch_u8``), ``cells`` uint8 [n, sizeof(mnet_column_paste)] (``_lib.ColumnPaste``; a plain
+    region as ``pages.as_cell`` states it), ``spans`` uint8 [tiles, sizeof(mnet_tile_span)] (``_lib.TileSpan``), one per 64 x 16 tile of the page,
+    ``order`` int32 [n_order], indices into ``cells`` (``pages.bin_tiles`` makes both), ``page`` uint8 [H,W,3] RGB holding the background — all on the
+    device.  ``page`` is modified IN PLACE inside the cells' rectangles and returned; a span, an entry or a cell that cannot be followed is skipped."""
+    lib = _lib.load()
+    _need_cuda(lines, cells, spans, order, page)
+    _need_u8("paste_ordered_u8", "lines", lines, 4)
+    _need_u8("paste_ordered_u8", "page", page, 3)
+    _check_table("paste_ordered_u8", "cell table", cells, _lib.ColumnPaste, 8)
+    _check_table("paste_ordered_u8", "span table", spans, _lib.TileSpan, 4)
+    if order.dtype != torch.int32 or order.dim() != 1:
+        raise TypeError("paste_ordered_u8: order must be int32 [n]")
+    if not spans.is_contiguous() or not order.is_contiguous():
+        raise ValueError("paste_ordered_u8: spans and order must be contiguous")
+    if cells.shape[0] < 1 or order.shape[0] < 1 or lines.numel() == 0 or page.numel() == 0:
+        raise ValueError("paste_ordered_u8: empty batch (%d cells, %d order entries, lines %s, page %s)"
+                         % (cells.shape[0], order.shape[0], list(lines.shape), list(page.shape)))
+    tiles_x, tiles_y = page_tiles(page.shape[0], page.shape[1])
+    if spans.shape[0] != tiles_x * tiles_y:
+        raise ValueError("paste_ordered_u8: %d spans for a page of %d x %d tiles" % (spans.shape[0], tiles_x, tiles_y))
+    _lib.check(lib.mnet_paste_ordered_u8(_p(lines), int(lines.shape[0]), int(lines.shape[1]), int(lines.shape[2]), _p(cells), int(cells.shape[0]),
+                                         _p(spans), int(spans.shape[0]), _p(order), int(order.shape[0]), _p(page), int(page.shape[0]),
+                                         int(page.shape[1]), _stream()), "mnet_paste_ordered_u8")
     return page
 
 

@@ -10,12 +10,21 @@ same bytes from the device:
     enlarge, compose_page     the device and the background ``ops.lq_from_u8(preview=True)`` makes of the page: ``lq_io.resize_cubic(page, s, s)``
     check_request,            what ``quads`` and ``columns`` share with this module: the refusals of scale and feather, and the intake of a host or
     page_to_device            device page with its joined lines
+    as_cell, bin_tiles,       overlapping regions in the caller's order: one table of cells, the cells of every 64 x 16 tile of the page, and ONE
+    paste_ordered             ``mnet_paste_ordered_u8`` launch whose workgroups own page tiles
+
+Overlap.  Two regions that share a pixel are refused by default (``overlap="refuse"``): the per-descriptor kernels blend in place, so an overlap has
+no order there.  ``overlap="order"`` is painter's order, and this is its one statement: the regions are pasted one after another in list order by
+``paste_host`` (a column by ``columns.paste_column_host``); a later region is blended, under its own feather ramp, into what the page holds at that
+moment, earlier regions included.  The loops of ``compose_host`` and ``columns.compose_columns_host`` do exactly that; ``"order"`` only drops the
+pairwise refusal, every other refusal stands, and the crops the networks read are taken from the original page, so they do not depend on the order.
+The device reproduces it byte for byte (``mnet_paste_ordered_u8``: one thread does all blends of a pixel, in that order).
 
 ``MarconetPipeline.restore_page`` ties them to the networks.  A region is an axis-aligned integer box [x1, y1, x2, y2] in page pixels: the reference
 handles regular layouts without perspective only; rotated and quadrilateral regions are ``quads``' (``MarconetPipeline.restore_page_quads``).  Out of
 scope: vertical columns that are rotated or in perspective (upright columns of stacked characters are ``columns``': ``MarconetPipeline.
-restore_page_columns``), overlapping regions (the paste blends in place: an overlap has no defined order), detection and
-recognition (the caller's), and several pages in one launch.
+restore_page_columns``), any blend of overlapping regions other than painter's order, detection and recognition (the caller's), and several pages
+in one launch.
 """
 import math
 
@@ -27,6 +36,16 @@ from . import _lib, lq_device, lq_io, ops
 ROW_H = lq_device.SHOW_H      # the height of a restored line (``restore_lines``)
 MAX_SCALE, MAX_FEATHER, MAX_K = 8, 1024, 8
 MIN_RECT_H_DIV = 16           # a rectangle under ROW_H / 16 = 8 rows is refused: the box reduction stops at 8, the cubic would skip rows
+TILE_W, TILE_H = 64, 16       # csrc/page_tile.h's tile, which mnet_paste_ordered_u8 counts from the page's origin
+MAX_TILES = 2 ** 31 - 1       # PT_MAX_BLOCKS; the span's fields are int32 too
+OVERLAP_MODES = ("refuse", "order")
+
+
+def check_overlap(overlap):
+    """``overlap`` is "refuse" or "order" (ValueError otherwise) → whether overlapping regions are pasted in list order"""
+    if overlap not in OVERLAP_MODES:
+        raise ValueError('overlap must be "refuse" or "order", got %r' % (overlap,))
+    return overlap == "order"
 
 
 def box_factor(rh, rows=ROW_H):
@@ -136,11 +155,12 @@ def check_request(scale, feather, n_regions, n_lines, unit, units):
         raise ValueError("one line (or None) per %s expected (%d %s, %d lines)" % (unit, n_regions, units, n_lines))
 
 
-def region_rects(page_h, page_w, boxes, restored, scale, feather, rows=ROW_H):
+def region_rects(page_h, page_w, boxes, restored, scale, feather, rows=ROW_H, overlap="refuse"):
     """the refusals, all ValueError naming the region, and the regions' rectangles (x0, y0, rw, rh) in the enlarged page.  ``restored[i]``: region i
     has a line to paste (the others keep the background: only their box is checked).  Refused: ``scale`` outside [1, 8] or ``feather`` outside
     [0, 1024] (integers); a box that is not four integers with 0 ≤ x1 < x2 ≤ W and 0 ≤ y1 < y2 ≤ H; a restored region's rectangle under rows / 16
-    rows; two restored regions whose rectangles overlap."""
+    rows; two restored regions whose rectangles overlap, unless ``overlap="order"`` (the head of this module: list order is paste order)."""
+    ordered = check_overlap(overlap)
     check_request(scale, feather, len(boxes), len(restored), "box", "boxes")
     s, rects = int(scale), []
     for i, b in enumerate(boxes):
@@ -153,7 +173,7 @@ def region_rects(page_h, page_w, boxes, restored, scale, feather, rows=ROW_H):
         if restored[i] and rects[i][3] * MIN_RECT_H_DIV < rows:
             raise ValueError("region %d: its rectangle is %d rows high at scale %d, under the %d a %d-row line can be reduced to"
                              % (i, rects[i][3], s, rows // MIN_RECT_H_DIV, rows))
-    live = [i for i in range(len(boxes)) if restored[i]]
+    live = [] if ordered else [i for i in range(len(boxes)) if restored[i]]
     for n, i in enumerate(live):
         for j in live[:n]:
             a, b = rects[i], rects[j]
@@ -169,14 +189,14 @@ def _page_array(page):
     return page
 
 
-def compose_host(page, lines, boxes, scale=4, feather=8):
+def compose_host(page, lines, boxes, scale=4, feather=8, overlap="refuse"):
     """the definition of a page: ``page`` uint8 RGB [H, W, 3]; ``lines[i]``: region i's restored line, uint8 BGR [rows, src_w, 3]
     (``MarconetPipeline.restore_lines`` of the crop ``page[y1:y2, x1:x2]``), or None for a region that keeps the background; ``boxes[i]`` its
     integer box → uint8 RGB [s·H, s·W, 3]: ``lq_io.resize_cubic(page, s, s)`` with ``paste_host`` of every line in its rectangle
-    (s·x1, s·y1, s·(x2 − x1), s·(y2 − y1))."""
+    (s·x1, s·y1, s·(x2 − x1), s·(y2 − y1)), in list order — which only shows where ``overlap="order"`` lets rectangles overlap."""
     page = _page_array(page)
     rows = next((int(np.shape(l)[0]) for l in lines if l is not None), ROW_H)
-    rects = region_rects(page.shape[0], page.shape[1], boxes, [l is not None for l in lines], scale, feather, rows)
+    rects = region_rects(page.shape[0], page.shape[1], boxes, [l is not None for l in lines], scale, feather, rows, overlap)
     out = lq_io.resize_cubic(page, int(scale), int(scale))
     for line, rect in zip(lines, rects):
         if line is not None:
@@ -203,6 +223,66 @@ def paste_rects(out, joined, rects, out_ws, feather, line_index=None):
     if any(w is not None for w in out_ws):
         with ops.on_device(out):
             ops.paste_u8(joined, ops.table_to_device(build_table(rects, out_ws, feather, int(joined.shape[1]), line_index), out.device), out)
+    return out
+
+
+def as_cell(regions):
+    """record array of ``mnet_paste_region`` → the same regions as ``mnet_column_paste`` records: the slice starts at column 0 and the feather
+    rectangle is the region's own (csrc/page_kernels.hip's as_cell), so that one table holds lines and column cells together"""
+    regions = np.asarray(regions)
+    if regions.dtype != np.dtype(_lib.PasteRegion):
+        raise TypeError("as_cell: a record array of mnet_paste_region expected")
+    cells = np.zeros(regions.shape, dtype=np.dtype(_lib.ColumnPaste))
+    for name in ("line_index", "src_w", "x0", "y0", "rw", "rh", "feather", "k", "scale_x", "scale_y"):
+        cells[name] = regions[name]
+    for name, src in (("fx0", "x0"), ("fy0", "y0"), ("fw", "rw"), ("fh", "rh")):
+        cells[name] = regions[src]
+    return cells
+
+
+def bin_tiles(cells, page_h, page_w):
+    """the cells of every 64 x 16 tile of a ``page_w`` x ``page_h`` page (tiles row-major from the page's origin) → (spans, order): ``spans`` a
+    record array of ``mnet_tile_span``, one per tile; ``order`` int32, for tile t at ``order[first : first + count]`` the indices of the cells
+    whose rectangle (x0, y0, rw, rh) intersects it, ascending — the table's order is the paste order; ``first`` is the exclusive prefix sum of
+    ``count``.  An empty rectangle touches no tile; a rectangle is clipped to the page.  ValueError for a page of more than 2^31 − 1 tiles and for
+    an order longer than that.  The (tile, cell) pairs are generated cell by cell and sorted by tile with a stable sort: no loop over tiles."""
+    cells = np.asarray(cells)
+    page_h, page_w = int(page_h), int(page_w)
+    if page_h < 1 or page_w < 1:
+        raise ValueError("bin_tiles: empty page (%d x %d)" % (page_w, page_h))
+    tiles_x, tiles_y = -(-page_w // TILE_W), -(-page_h // TILE_H)
+    n_tiles = tiles_x * tiles_y
+    if n_tiles > MAX_TILES:
+        raise ValueError("bin_tiles: a %d x %d page has %d tiles, more than %d" % (page_w, page_h, n_tiles, MAX_TILES))
+    x0, y0 = cells["x0"].astype(np.int64), cells["y0"].astype(np.int64)
+    x1, y1 = np.minimum(x0 + cells["rw"], page_w), np.minimum(y0 + cells["rh"], page_h)
+    x0, y0 = np.maximum(x0, 0), np.maximum(y0, 0)
+    tx0, ty0, tx1, ty1 = x0 // TILE_W, y0 // TILE_H, -(-x1 // TILE_W), -(-y1 // TILE_H)       # the tiles [tx0, tx1) x [ty0, ty1)
+    per_cell = np.where((x1 > x0) & (y1 > y0), (tx1 - tx0) * (ty1 - ty0), 0)
+    total = int(per_cell.sum())
+    if total > MAX_TILES:
+        raise ValueError("bin_tiles: the cells touch %d tiles in all, an order longer than %d" % (total, MAX_TILES))
+    tiles = [(np.arange(ty0[c], ty1[c])[:, None] * tiles_x + np.arange(tx0[c], tx1[c])[None, :]).reshape(-1) for c in np.flatnonzero(per_cell)]
+    tile = np.concatenate(tiles) if tiles else np.zeros((0,), np.int64)
+    cell = np.repeat(np.arange(len(cells), dtype=np.int32), per_cell)                             # the pairs, in cell order
+    order = np.ascontiguousarray(cell[np.argsort(tile, kind="stable")])
+    count = np.bincount(tile, minlength=n_tiles)
+    spans = np.zeros((n_tiles,), dtype=np.dtype(_lib.TileSpan))
+    spans["count"] = count
+    spans["first"] = np.cumsum(count) - count
+    return spans, order
+
+
+def paste_ordered(out, joined, cells):
+    """``out``: the enlarged page on the device, changed IN PLACE; ``joined``: uint8 BGR [L, rows, line_w, 3] on the device; ``cells``: a record
+    array of ``mnet_column_paste`` (``as_cell`` of ``build_table``'s regions, ``columns.paste_table``'s cells), pasted in the table's order wherever
+    they overlap: the bytes of ``paste_host`` / ``columns.paste_column_host`` applied one after another.  One copy each of the table, the spans and
+    the order, and ONE launch whose workgroups are the page's tiles."""
+    if len(cells):
+        spans, order = bin_tiles(cells, int(out.shape[0]), int(out.shape[1]))
+        with ops.on_device(out):
+            ops.paste_ordered_u8(joined, ops.table_to_device(cells, out.device), ops.table_to_device(spans, out.device),
+                                 torch.from_numpy(order).to(out.device), out)
     return out
 
 
@@ -246,14 +326,20 @@ def page_to_device(who, page, joined, out_ws, device, check):
     return page, rows, records
 
 
-def compose_page(page, joined, out_ws, boxes, scale=4, feather=8, device=None):
+def compose_page(page, joined, out_ws, boxes, scale=4, feather=8, device=None, overlap="refuse"):
     """the device path of ``compose_host``.  ``page``: uint8 RGB [H, W, 3], a host array (copied once) or a device tensor; ``joined``: uint8 BGR
     [L, rows, line_w, 3] on the device, the lines of the regions that have one, in the regions' order (``long_lines.compose_lines``), or None where
     no region has one; ``out_ws[i]``: the width of region i's line, None for a region that keeps the background; ``boxes[i]``: its integer box.
     → uint8 RGB [s·H, s·W, 3] on the device.  Every refusal of ``compose_host`` is raised before anything is copied or launched; then one copy of
-    the page and one of each small table (the background's descriptor, the regions), one launch for the background and one for all regions."""
+    the page and one of each small table (the background's descriptor, the regions), one launch for the background and one for all regions.
+    ``overlap="order"``: overlapping regions are pasted in list order, by one ``mnet_paste_ordered_u8`` launch over the same regions as cells
+    (``paste_ordered``) — overlap-free pages too, so that the mode has one path."""
+    ordered = check_overlap(overlap)
+
     def check(H, W, rows):
-        rects = region_rects(H, W, boxes, [w is not None for w in out_ws], scale, feather, rows)
+        rects = region_rects(H, W, boxes, [w is not None for w in out_ws], scale, feather, rows, overlap)
         return rects, [r[3] for r in rects]
-    page, _, rects = page_to_device("compose_page", page, joined, out_ws, device, check)
+    page, rows, rects = page_to_device("compose_page", page, joined, out_ws, device, check)
+    if ordered:
+        return paste_ordered(enlarge(page, int(scale)), joined, as_cell(build_table(rects, out_ws, feather, rows)))
     return paste_rects(enlarge(page, int(scale)), joined, rects, out_ws, feather)

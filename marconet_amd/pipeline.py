@@ -497,7 +497,7 @@ class MarconetPipeline:
         return None if char_boxes is None else [[c[0] - box[0], c[1] - box[1], c[2] - box[0], c[3] - box[1]] for c in char_boxes]
 
     @torch.no_grad()
-    def restore_page(self, image, boxes, texts, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False):
+    def restore_page(self, image, boxes, texts, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False, overlap="refuse"):
         """A page and its text regions → the page enlarged ``scale`` times with every text line restored in place: uint8 RGB [s·H, s·W, 3] on the
         host, the bytes of ``pages.compose_host(image, self.restore_lines(crops, texts, char_boxes), boxes, scale, feather)`` for the crops
         ``image[y1:y2, x1:x2]``.  ``image``: uint8 RGB [H, W, 3]; ``boxes[i]``: region i's text-line box [x1, y1, x2, y2] in page pixels (numbers that
@@ -511,9 +511,13 @@ class MarconetPipeline:
         A region ``restore_lines`` answers with ``None`` (no character, a character outside the alphabet) keeps the background; with no boxes at all
         the result is the background.  ValueError naming the region, before anything is copied or launched, for a box that is empty or outside the
         page, a rectangle under 8 output rows, and two restored regions that overlap.
+        ``overlap="order"`` lifts that last refusal: overlapping regions — stacked lines whose outward-rounded boxes share a row, ascenders and
+        descenders of neighbours — are pasted in list order, a later region blended under its own ramp into what the page holds by then (painter's
+        order, ``pages``' head), the bytes of ``pages.compose_host(..., overlap="order")``.  The crops are still taken from the original page.  The
+        page is then composed by ONE ``mnet_paste_ordered_u8`` launch whose workgroups own page tiles, with or without overlaps.
         ``texts`` is required, for ``restore_lines``' reason.  ``details=True`` → ``(page, regions)``: per region a dict with ``plan`` (its windows),
         ``out_w`` (the width of its restored line at height 128) and ``rect`` (x0, y0, rw, rh in the result), None where it kept the background.
-        Not covered: overlapping regions; vertical columns that are rotated or in perspective (upright columns of stacked characters:
+        Not covered: a blend of overlapping regions other than painter's order; vertical columns that are rotated or in perspective (upright columns of stacked characters:
         ``restore_page_columns``; rotated, quadrilateral and perspective regions: ``restore_page_quads``; curved text: ``restore_page_curves``); detection and recognition (the caller's); several pages in one launch."""
         from . import pages
         image, restored = self._page_front("restore_page", image, len(boxes), texts, [char_boxes],
@@ -521,14 +525,14 @@ class MarconetPipeline:
         H, W = int(image.shape[0]), int(image.shape[1])
         boxes = [pages.round_box(b, H, W) for b in boxes]
         try:
-            rects = pages.region_rects(H, W, boxes, restored, scale, feather)
+            rects = pages.region_rects(H, W, boxes, restored, scale, feather, overlap=overlap)
         except ValueError as e:
             raise ValueError("restore_page: %s" % e) from None
         crops = [image[b[1]:b[3], b[0]:b[2]] for b in boxes]
         local = [self._boxes_in_crop(None if char_boxes is None else char_boxes[i], b) for i, b in enumerate(boxes)]
         joined, plans, live = self._joined_lines(crops, texts, local, max_glyphs, overlap_glyphs, "restore_page", "region")
         dev = next(self.sr.parameters()).device
-        return self._page_finish(plans, lambda out_ws: pages.compose_page(image, joined, out_ws, boxes, scale, feather, device=dev), details,
+        return self._page_finish(plans, lambda out_ws: pages.compose_page(image, joined, out_ws, boxes, scale, feather, device=dev, overlap=overlap), details,
                                  [dict(rect=r) for r in rects])
 
     @torch.no_grad()
@@ -637,7 +641,8 @@ class MarconetPipeline:
         return self._page_finish(plans, compose, details, [dict(polygon=r["out_polygon"], size=(r["rw"], r["rh"])) for r in regions])
 
     @torch.no_grad()
-    def restore_page_columns(self, image, boxes, texts, vertical=None, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False):
+    def restore_page_columns(self, image, boxes, texts, vertical=None, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False,
+                             overlap="refuse"):
         """``restore_page`` for pages with vertical text: columns of upright characters stacked top to bottom (shop signs, couplets, book spines,
         traditional typesetting).  ``boxes[i]``: region i's box [x1, y1, x2, y2] in page pixels, rounded outward as in ``restore_page``;
         ``vertical[i]``: region i is a column, read top to bottom (None: every region is); a region with ``vertical[i]`` false is a horizontal line,
@@ -657,7 +662,10 @@ class MarconetPipeline:
         text's length, an empty cell, a cell under 8 output rows, ``plan_windows``' refusals (a cell wider than 512 px at height 32).
         ``details=True`` → ``(page, regions)``: per region ``restore_page``'s dict, for a column with ``cuts`` (page rows) and ``widths`` (its cells'
         widths in the virtual strip) added; None where it kept the background.
-        Not covered: overlapping regions; vertical columns that are rotated or in perspective; right-to-left ordering of columns (the caller's);
+        ``overlap="order"`` as in ``restore_page``, across both kinds of region (a sign's column over the line next to it): the bytes of
+        ``columns.compose_columns_host(..., overlap="order")``, composed by ONE ``mnet_paste_ordered_u8`` launch over one table that holds the lines'
+        regions and the columns' cells together in region order, a column's cells consecutive, in the place of the two paste launches.
+        Not covered: a blend of overlapping regions other than painter's order; vertical columns that are rotated or in perspective; right-to-left ordering of columns (the caller's);
         curved vertical columns (curved horizontal text: ``restore_page_curves``); detection and recognition; several pages in one launch."""
         from . import columns as cl, lq_device, pages
         who, n = "restore_page_columns", len(boxes)
@@ -668,9 +676,10 @@ class MarconetPipeline:
         boxes = [pages.round_box(b, H, W) for b in boxes]
         cb = [None if char_boxes is None else char_boxes[i] for i in range(n)]
         try:
-            pages.region_rects(H, W, boxes, restored, scale, feather)
+            ordered = pages.check_overlap(overlap)
+            pages.region_rects(H, W, boxes, restored, scale, feather, overlap=overlap)
             cuts = [cl.cell_cuts(boxes[i], len(texts[i]), cb[i], region=i) if vertical[i] and restored[i] else None for i in range(n)]
-            rects = cl.check_columns(H, W, boxes, restored, cuts, scale, feather)
+            rects = cl.check_columns(H, W, boxes, restored, cuts, scale, feather, overlap=overlap)
         except ValueError as e:
             raise ValueError("%s: %s" % (who, e)) from None
         widths = [None if c is None else cl.cell_widths(b, c) for b, c in zip(boxes, cuts)]
@@ -704,6 +713,9 @@ class MarconetPipeline:
                 prep = lq_device.prepare_packed(packed, [o[0] for o in order], [o[1] for o in order])
                 joined = self._restore_planned(prep.lq, labels, locs_rows, plans, live)
                 line_of = {i: l for l, i in enumerate(live)}
+                if ordered:                                                                      # one table in region order, one launch by page tile
+                    col_of = dict(zip(cols, columns))
+                    return pages.paste_ordered(out, joined, cl.mixed_table(joined, [(line_of[i], rects[i], col_of.get(i, out_ws[i])) for i in live], int(feather)))
                 pages.paste_rects(out, joined, rects, [out_ws[i] if i in lines_ else None for i in range(n)], int(feather), [line_of[i] for i in lines_])
                 cl.paste_columns(out, joined, [line_of[i] for i in cols], columns, [rects[i] for i in cols], int(feather))
             return out
