@@ -99,6 +99,14 @@ class TileSpan(ctypes.Structure):
     _fields_ = [("first", c_int), ("count", c_int)]
 
 
+class PageItem(ctypes.Structure):
+    """mirror of ``mnet_page_item`` (include/marconet_hip_mixed.h): one thing mnet_paste_mixed_u8 pastes — entry ``index`` of the table of its ``kind``"""
+    _fields_ = [("kind", c_int), ("index", c_int), ("x0", c_int), ("y0", c_int), ("rw", c_int), ("rh", c_int)]
+
+
+ITEM_CELL, ITEM_QUAD, ITEM_CURVE = 0, 1, 2      # MNET_ITEM_*
+
+
 class CurveSeg(ctypes.Structure):
     """mirror of ``mnet_curve_seg`` (include/marconet_hip_curve.h): one bilinear segment of a curved region"""
     _fields_ = [("c", c_double * 8), ("u0", c_int), ("w", c_int), ("bx0", c_int), ("by0", c_int), ("bw", c_int), ("bh", c_int)]
@@ -234,6 +242,12 @@ ORDERED_SYMBOLS = {
     "mnet_paste_ordered_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
 }
 
+# ... and the one include/marconet_hip_mixed.h declares (regions of every kind of a page, overlapping, pasted in the caller's order by page tile)
+MIXED_SYMBOLS = {
+    "mnet_paste_mixed_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                    c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
+}
+
 _lib = None
 
 
@@ -251,7 +265,7 @@ def load():
             "marconet_amd: %s not found — build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or marconet_amd/csrc/build.sh (there is no CPU/eager fallback)" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(UPFOLD_SYMBOLS.items()) + list(UPFOLD_F32Z_SYMBOLS.items()) + list(QUAD_SYMBOLS.items()) + list(COLUMN_SYMBOLS.items()) + list(CURVE_SYMBOLS.items()) + list(ORDERED_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(UPFOLD_SYMBOLS.items()) + list(UPFOLD_F32Z_SYMBOLS.items()) + list(QUAD_SYMBOLS.items()) + list(COLUMN_SYMBOLS.items()) + list(CURVE_SYMBOLS.items()) + list(ORDERED_SYMBOLS.items()) + list(MIXED_SYMBOLS.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is absent
         fn.restype = res
         fn.argtypes = args

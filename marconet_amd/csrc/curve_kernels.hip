@@ -27,34 +27,12 @@
 #include "curve_map.h"
 #include "page_blend.h"
 #include "page_tile.h"
+#include "warp_paste.h"
 
 namespace {
 
 static_assert(CURVE_MAX_SEGS == MNET_CURVE_MAX_SEGS, "curve_map.h and marconet_hip_curve.h disagree");
 static_assert(sizeof(mnet_curve_seg) == 88 && sizeof(mnet_curve_crop) == 32 && sizeof(mnet_curve_region) == 48, "descriptor layout");
-
-struct CurveSegL {           // a segment in LDS
-    double c[8];
-    CurvePrep s;
-    int u0, w, bx0, by0, bw, bh;
-};
-
-// Thread t < nseg stages segment seg0 + t into S[t] → whether it can be followed as far as this thread sees: finite coefficients, w >= 1, and its
-// first column is where its predecessor's ends (0 for the first).  The caller has checked 0 <= seg0, seg0 + nseg <= n_segs.
-__device__ __forceinline__ bool curve_stage(CurveSegL* S, const mnet_curve_seg* __restrict__ segs, int seg0, int t, mnet_curve_seg& g) {
-    g = segs[(size_t)seg0 + t];
-    long long due = 0;
-    if (t > 0) {
-        const mnet_curve_seg* p = segs + ((size_t)seg0 + t - 1);
-        due = (long long)p->u0 + p->w;
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) S[t].c[k] = g.c[k];
-    S[t].s = curve_prep(g.c);
-    S[t].u0 = g.u0; S[t].w = g.w;
-    S[t].bx0 = g.bx0; S[t].by0 = g.by0; S[t].bw = g.bw; S[t].bh = g.bh;
-    return curve_finite8(g.c) && g.w >= 1 && (long long)g.u0 == due;
-}
 
 __global__ void __launch_bounds__(256) curve_crop_u8_kernel(const unsigned char* __restrict__ page, int page_h, int page_w,
                                                             const mnet_curve_crop* __restrict__ crops, const mnet_curve_seg* __restrict__ segs,
@@ -112,21 +90,14 @@ __global__ void __launch_bounds__(256) curve_paste_u8_kernel(const unsigned char
     const PtTile T = pt_tile(tiles_x, tiles_y);
     const mnet_curve_region R = regions[T.desc];
     const int rw = R.rw, rh = R.rh, bw = R.bw, bh = R.bh, nseg = R.nseg;
-    const bool ok = rw >= 1 && rh >= 1 && bw >= 1 && bh >= 1 && R.ax0 >= 0 && R.ay0 >= 0 && R.bx0 >= 0 && R.by0 >= 0 &&
-                    (long long)R.ax0 + rw <= atlas_w && (long long)R.ay0 + rh <= atlas_h && (long long)R.bx0 + bw <= page_w &&
-                    (long long)R.by0 + bh <= page_h && R.feather >= 0 && R.feather <= PAGE_MAX_FEATHER &&
-                    R.seg0 >= 0 && nseg >= 1 && nseg <= CURVE_MAX_SEGS && (long long)R.seg0 + nseg <= n_segs;
     const int i0 = T.x0, j0 = T.y0;
-    if (!ok || i0 >= bw || j0 >= bh) return;             // uniform over the workgroup
+    if (!curve_region_followed(R, atlas_h, atlas_w, page_h, page_w, n_segs) || i0 >= bw || j0 >= bh) return;    // uniform over the workgroup
     const int t = (int)threadIdx.x;
     bool good = true, hit = false;
     if (t < nseg) {
         mnet_curve_seg g;
-        good = curve_stage(S, segs, R.seg0, t, g);
-        good = good && g.bw >= 0 && g.bh >= 0 && g.bx0 >= R.bx0 && g.by0 >= R.by0 && (long long)g.bx0 + g.bw <= (long long)R.bx0 + bw &&
-               (long long)g.by0 + g.bh <= (long long)R.by0 + bh;
-        const long long tx0 = (long long)R.bx0 + i0, ty0 = (long long)R.by0 + j0;          // the tile's page pixels: [tx0, tx0 + 64) x [ty0, ty0 + 16)
-        hit = g.bw > 0 && g.bh > 0 && g.bx0 < tx0 + PT_TX && (long long)g.bx0 + g.bw > tx0 && g.by0 < ty0 + PT_TY && (long long)g.by0 + g.bh > ty0;
+        good = curve_stage(S, segs, R.seg0, t, g) && curve_seg_in_region(g, R);
+        hit = curve_seg_hits(g, (long long)R.bx0 + i0, (long long)R.by0 + j0, PT_TX, PT_TY);      // the tile's page pixels
     }
     if (!__syncthreads_and(good ? 1 : 0)) return;        // the vote is the barrier: S is visible, and the decision is uniform
     if ((long long)S[nseg - 1].u0 + S[nseg - 1].w != rw) return;
@@ -134,8 +105,7 @@ __global__ void __launch_bounds__(256) curve_paste_u8_kernel(const unsigned char
     const int i = i0 + (t & (PT_TX - 1)), ty = t / PT_TX;
     if (i >= bw) return;
     const int X = R.bx0 + i;
-    const double x = LQ_DADD((double)X, 0.5), frh = (double)rh;
-    const unsigned F = (unsigned)R.feather;
+    const double x = LQ_DADD((double)X, 0.5);
     const size_t row_bytes = (size_t)atlas_w * 3;
     const unsigned char* fg0 = atlas + ((size_t)R.ay0 * atlas_w + (size_t)R.ax0) * 3;
 #pragma unroll 1
@@ -143,31 +113,7 @@ __global__ void __launch_bounds__(256) curve_paste_u8_kernel(const unsigned char
         const int j = j0 + ty + 4 * r;
         if (j >= bh) break;
         const int Y = R.by0 + j;
-        const double y = LQ_DADD((double)Y, 0.5);
-#pragma unroll 1
-        for (int k = 0; k < nseg; ++k) {
-            const CurveSegL& s = S[k];
-            if (X < s.bx0 || X - s.bx0 >= s.bw || Y < s.by0 || Y - s.by0 >= s.bh) continue;      // the integer box, before any fp64
-            const CurveInv p = curve_inv(s.c, s.s, x, y);
-            if (!(p.valid && p.u >= 0.0 && p.u < (double)s.w && p.v >= 0.0 && p.v < frh)) continue;
-            int x0, x1, ax;
-            curve_taps_x(quad_fix(p.u), s.u0, rw, &x0, &x1, &ax);
-            const QuadTaps q = quad_taps(0, quad_fix(p.v), rw, rh);
-            const unsigned char* r0 = fg0 + (size_t)q.y0 * row_bytes;
-            const unsigned char* r1 = fg0 + (size_t)q.y1 * row_bytes;
-            unsigned char* d = page + ((size_t)Y * page_w + (size_t)X) * 3;
-            unsigned fa = 0u, fb = 0u;
-            if (F) {
-                fa = page_feather_axis((unsigned)(s.u0 + (int)floor(p.u)), (unsigned)rw, F);
-                fb = page_feather_axis((unsigned)(int)floor(p.v), (unsigned)rh, F);
-            }
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                const unsigned fg = (unsigned)quad_mix(r0[(size_t)x0 * 3 + ch], r0[(size_t)x1 * 3 + ch], r1[(size_t)x0 * 3 + ch], r1[(size_t)x1 * 3 + ch], ax, q.ay);
-                d[ch] = (unsigned char)(F ? page_feather(d[ch], fg, fa, fb, F) : fg);
-            }
-            break;                                                                                // the first claim wins
-        }
+        curve_paste_pixel(S, nseg, rw, rh, (unsigned)R.feather, fg0, row_bytes, X, Y, x, LQ_DADD((double)Y, 0.5), page + ((size_t)Y * page_w + (size_t)X) * 3);
     }
 }
 

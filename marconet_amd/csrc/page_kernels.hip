@@ -89,6 +89,9 @@ __device__ __forceinline__ CellView cell_view(const mnet_column_paste& R, const 
             (unsigned)((long long)R.y0 - R.fy0)};
 }
 
+// mixed_kernels.hip includes this file for the body above alone (MNET_PAGE_CELL_ONLY), so that a cell's arithmetic stays stated once, here
+#ifndef MNET_PAGE_CELL_ONLY
+
 __device__ __forceinline__ void paste_cell(PtTaps& s, const PtTile T, const mnet_column_paste R, const unsigned char* __restrict__ lines, int n_lines, int rows,
                                   int line_w, unsigned char* page, int page_h, int page_w) {
     const int k = R.k, rw = R.rw, rh = R.rh;
@@ -230,7 +233,11 @@ int ordered_launch(const uint8_t* lines, int32_t n_lines, int32_t rows, int32_t 
     return MNET_OK;
 }
 
+#endif  // MNET_PAGE_CELL_ONLY
+
 }  // namespace
+
+#ifndef MNET_PAGE_CELL_ONLY
 
 extern "C" int mnet_paste_u8(const uint8_t* lines, int32_t n_lines, int32_t rows, int32_t line_w, const mnet_paste_region* regions, int32_t n_regions,
                              uint8_t* page, int32_t page_h, int32_t page_w, void* stream) {
@@ -247,3 +254,5 @@ extern "C" int mnet_paste_ordered_u8(const uint8_t* lines, int32_t n_lines, int3
                                      int32_t page_w, void* stream) {
     return ordered_launch(lines, n_lines, rows, line_w, cells, n_cells, spans, n_spans, order, n_order, page, page_h, page_w, stream);
 }
+
+#endif  // MNET_PAGE_CELL_ONLY

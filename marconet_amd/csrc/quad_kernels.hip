@@ -18,15 +18,9 @@
 #include "quad_map.h"
 #include "page_blend.h"
 #include "page_tile.h"
+#include "warp_paste.h"
 
 namespace {
-
-__device__ inline bool quad_finite9(const double* m) {
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) ok = ok && isfinite(m[k]);
-    return ok;
-}
 
 __global__ void __launch_bounds__(256) quad_crop_u8_kernel(const unsigned char* __restrict__ page, int page_h, int page_w,
                                                            const mnet_quad_crop* __restrict__ crops, int tiles_x, int tiles_y,
@@ -68,16 +62,12 @@ __global__ void __launch_bounds__(256) quad_paste_u8_kernel(const unsigned char*
     const PtTile T = pt_tile(tiles_x, tiles_y);
     const mnet_quad_region R = regions[T.desc];
     const int rw = R.rw, rh = R.rh, bw = R.bw, bh = R.bh;
-    const bool ok = rw >= 1 && rh >= 1 && bw >= 1 && bh >= 1 && R.ax0 >= 0 && R.ay0 >= 0 && R.bx0 >= 0 && R.by0 >= 0 &&
-                    (long long)R.ax0 + rw <= atlas_w && (long long)R.ay0 + rh <= atlas_h && (long long)R.bx0 + bw <= page_w &&
-                    (long long)R.by0 + bh <= page_h && R.feather >= 0 && R.feather <= PAGE_MAX_FEATHER && quad_finite9(R.n);
     const int i0 = T.x0, j0 = T.y0;
-    if (!ok || i0 >= bw || j0 >= bh) return;             // uniform over the workgroup
+    if (!quad_region_followed(R, atlas_h, atlas_w, page_h, page_w) || i0 >= bw || j0 >= bh) return;             // uniform over the workgroup
     const int t = (int)threadIdx.x, i = i0 + (t & (PT_TX - 1)), ty = t / PT_TX;
     if (i >= bw) return;
     const int X = R.bx0 + i;
-    const double x = LQ_DADD((double)X, 0.5), frw = (double)rw, frh = (double)rh;
-    const unsigned F = (unsigned)R.feather;
+    const double x = LQ_DADD((double)X, 0.5);
     const size_t row_bytes = (size_t)atlas_w * 3;
     const unsigned char* fg0 = atlas + ((size_t)R.ay0 * atlas_w + (size_t)R.ax0) * 3;
 #pragma unroll
@@ -85,22 +75,7 @@ __global__ void __launch_bounds__(256) quad_paste_u8_kernel(const unsigned char*
         const int j = j0 + ty + 4 * r;
         if (j >= bh) break;
         const int Y = R.by0 + j;
-        const QuadPos p = quad_pos(R.n, x, LQ_DADD((double)Y, 0.5));
-        if (!(p.valid && p.u >= 0.0 && p.u < frw && p.v >= 0.0 && p.v < frh)) continue;
-        const QuadTaps q = quad_taps(quad_fix(p.u), quad_fix(p.v), rw, rh);
-        const unsigned char* r0 = fg0 + (size_t)q.y0 * row_bytes;
-        const unsigned char* r1 = fg0 + (size_t)q.y1 * row_bytes;
-        unsigned char* d = page + ((size_t)Y * page_w + (size_t)X) * 3;
-        unsigned fa = 0u, fb = 0u;
-        if (F) {
-            fa = page_feather_axis((unsigned)(int)floor(p.u), (unsigned)rw, F);
-            fb = page_feather_axis((unsigned)(int)floor(p.v), (unsigned)rh, F);
-        }
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            const unsigned fg = (unsigned)quad_mix(r0[(size_t)q.x0 * 3 + ch], r0[(size_t)q.x1 * 3 + ch], r1[(size_t)q.x0 * 3 + ch], r1[(size_t)q.x1 * 3 + ch], q.ax, q.ay);
-            d[ch] = (unsigned char)(F ? page_feather(d[ch], fg, fa, fb, F) : fg);
-        }
+        quad_paste_pixel(R.n, rw, rh, (unsigned)R.feather, fg0, row_bytes, x, LQ_DADD((double)Y, 0.5), page + ((size_t)Y * page_w + (size_t)X) * 3);
     }
 }
 

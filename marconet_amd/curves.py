@@ -22,8 +22,8 @@ their shared rung at its end points only, bilinear patches agree along all of it
 and 1 / h folded in, a segment is A = T_k, E = (T_k+1 - T_k) / w, F = (B_k - T_k) / h, G = (T_k - T_k+1 + B_k+1 - B_k) / (w h); a point (u, v) of the
 segment's w x h rectangle lies at A + E u + F v + G u v.  For a parallelogram G is exactly 0 and the forward map is bit for bit ``quads.quad_pos``
 of ``quads.quad_map``: for 4-point polygons that are parallelograms, integer boxes included, everything here is ``quads``' bytes.
-``MarconetPipeline.restore_page_curves`` ties it to the networks.  Out of scope: overlapping regions, curved vertical columns, detection and
-recognition, several pages per launch.
+``MarconetPipeline.restore_page_curves`` ties it to the networks.  Out of scope: overlapping regions and pages that hold other kinds of region as
+well (both are ``regions``': ``MarconetPipeline.restore_page_regions``), curved vertical columns, detection and recognition, several pages per launch.
 """
 import math
 
@@ -315,10 +315,10 @@ def _seg_records(seg_lists):
     return tab, first
 
 
-def crop_table(seg_lists, sizes, c0s=None):
+def crop_table(seg_lists, sizes, c0s=None, base=0):
     """→ (numpy record array of ``mnet_curve_crop``, that of ``mnet_curve_seg``, the flat buffer's size in bytes): crop k is ``sizes[k]`` = (w, h)
-    along the segments ``seg_lists[k]`` from column ``c0s[k]`` (default 0) of its region's strip; the crops are packed tightly in order.  A list
-    that serves several windows (the same object) is stored once."""
+    along the segments ``seg_lists[k]`` from column ``c0s[k]`` (default 0) of its region's strip; the crops are packed tightly in order from byte
+    ``base``.  A list that serves several windows (the same object) is stored once."""
     uniq, index = [], {}
     for segs in seg_lists:
         if id(segs) not in index:
@@ -326,7 +326,7 @@ def crop_table(seg_lists, sizes, c0s=None):
             uniq.append(segs)
     seg_tab, first = _seg_records(uniq)
     tab = np.zeros((len(seg_lists),), dtype=np.dtype(_lib.CurveCrop))
-    off = 0
+    off = int(base)
     for k, (segs, (w, h)) in enumerate(zip(seg_lists, sizes)):
         tab[k] = (off, int(w), int(h), 0 if c0s is None else int(c0s[k]), first[index[id(segs)]], len(segs), 0)
         off += 3 * int(w) * int(h)
@@ -343,11 +343,15 @@ def paste_table(regions, feather, atlas_xy):
     return tab, seg_tab
 
 
-def crop_curves(page_d, seg_lists, sizes, c0s=None):
-    """``page_d`` uint8 RGB [H, W, 3] on the device → (uint8 [bytes] on the device: ``warp_crop_host`` of every crop, packed tightly in order, the
-    offsets of the crops): one copy of each table, one launch"""
-    tab, seg_tab, nbytes = crop_table(seg_lists, sizes, c0s)
-    dst = torch.empty((nbytes,), dtype=torch.uint8, device=page_d.device)
+def crop_curves(page_d, seg_lists, sizes, c0s=None, base=0, dst=None):
+    """``page_d`` uint8 RGB [H, W, 3] on the device → (uint8 [bytes] on the device: ``warp_crop_host`` of every crop, packed tightly in order from
+    byte ``base``, the offsets of the crops): one copy of each table, one launch.  ``dst``: an existing flat buffer that holds the crops' bytes
+    (the packed batch several sources share), written inside the crops only; None: a new one, the first ``base`` bytes left to the caller"""
+    tab, seg_tab, nbytes = crop_table(seg_lists, sizes, c0s, base)
+    if dst is None:
+        dst = torch.empty((nbytes,), dtype=torch.uint8, device=page_d.device)
+    elif dst.dtype != torch.uint8 or dst.dim() != 1 or dst.numel() < nbytes:
+        raise ValueError("crop_curves: a flat uint8 buffer of at least %d bytes expected" % nbytes)
     with ops.on_device(page_d):
         ops.curve_crop_u8(page_d, ops.table_to_device(tab, page_d.device), ops.table_to_device(seg_tab, page_d.device),
                           max(int(w) for w, _ in sizes), max(int(h) for _, h in sizes), dst)

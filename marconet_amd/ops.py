@@ -935,6 +935,50 @@ def paste_ordered_u8(lines, cells, spans, order, page):
     return page
 
 
+def paste_mixed_u8(lines, atlas, cells, quads, curves, segs, items, spans, order, page):
+    """mnet_paste_mixed_u8 (the bytes of regions.compose_regions_host's loop: pages.paste_host / columns.paste_column_host / quads.warp_paste_host /
+    curves.warp_paste_host applied item after item in the table's order, overlaps included): ``lines`` uint8 [L,rows,line_w,3] BGR, ``atlas`` uint8
+    [AH,AW,3] RGB holding the upright foregrounds of every quadrilateral and curved region, the tables ``cells`` (``_lib.ColumnPaste``), ``quads``
+    (``_lib.QuadRegion``), ``curves`` (``_lib.CurveRegion``) with ``segs`` (``_lib.CurveSeg``) — each None where the page has none of its kind, ``lines``
+    None without cells and ``atlas`` None without quads and curves —, ``items`` uint8 [n, sizeof(mnet_page_item)] (``_lib.PageItem``), ``spans`` /
+    ``order`` over the items as ``paste_ordered_u8`` takes them over cells, ``page`` uint8 [H,W,3] RGB holding the background — all on the device.
+    ``page`` is modified IN PLACE inside the items and returned; a span, an entry, an item or a descriptor that cannot be followed is skipped."""
+    lib = _lib.load()
+    who = "paste_mixed_u8"
+    _need_cuda(*[t for t in (lines, atlas, cells, quads, curves, segs, items, spans, order, page) if t is not None])
+    _need_u8(who, "page", page, 3)
+    if lines is not None:
+        _need_u8(who, "lines", lines, 4)
+    if atlas is not None:
+        _need_u8(who, "atlas", atlas, 3)
+    for what, table, struct in (("cell table", cells, _lib.ColumnPaste), ("quad table", quads, _lib.QuadRegion), ("curve table", curves, _lib.CurveRegion),
+                                ("segment table", segs, _lib.CurveSeg)):
+        if table is not None:
+            _check_table(who, what, table, struct, 8)
+    _check_table(who, "item table", items, _lib.PageItem, 4)
+    _check_table(who, "span table", spans, _lib.TileSpan, 4)
+    if order.dtype != torch.int32 or order.dim() != 1:
+        raise TypeError("%s: order must be int32 [n]" % who)
+    if not spans.is_contiguous() or not order.is_contiguous() or not items.is_contiguous():
+        raise ValueError("%s: items, spans and order must be contiguous" % who)
+    n = [0 if t is None else int(t.shape[0]) for t in (cells, quads, curves, segs)]
+    if items.shape[0] < 1 or order.shape[0] < 1 or page.numel() == 0 or (n[0] and (lines is None or lines.numel() == 0)) or \
+            ((n[1] or n[2]) and (atlas is None or atlas.numel() == 0)) or (n[2] and not n[3]):
+        raise ValueError("%s: empty batch (%d items, %d order entries, %d cells, %d quads, %d curves, %d segments, lines %s, atlas %s, page %s)"
+                         % (who, items.shape[0], order.shape[0], n[0], n[1], n[2], n[3], None if lines is None else list(lines.shape),
+                            None if atlas is None else list(atlas.shape), list(page.shape)))
+    tiles_x, tiles_y = page_tiles(page.shape[0], page.shape[1])
+    if spans.shape[0] != tiles_x * tiles_y:
+        raise ValueError("%s: %d spans for a page of %d x %d tiles" % (who, spans.shape[0], tiles_x, tiles_y))
+    ptr = lambda t: None if t is None else _p(t)
+    ls = (0, 0, 0) if lines is None else tuple(int(v) for v in lines.shape[:3])
+    ats = (0, 0) if atlas is None else tuple(int(v) for v in atlas.shape[:2])
+    _lib.check(lib.mnet_paste_mixed_u8(ptr(lines), ls[0], ls[1], ls[2], ptr(atlas), ats[0], ats[1], ptr(cells), n[0], ptr(quads), n[1], ptr(curves), n[2],
+                                       ptr(segs), n[3], _p(items), int(items.shape[0]), _p(spans), int(spans.shape[0]), _p(order), int(order.shape[0]),
+                                       _p(page), int(page.shape[0]), int(page.shape[1]), _stream()), "mnet_paste_mixed_u8")
+    return page
+
+
 def nonfinite_flag(x, out=None):
     """mnet_nonfinite_flag: int32 [1] device tensor (``out``: a one-element int32 view to write into), 1 iff the fp32 / fp16 tensor
     ``x`` holds an inf or NaN (no synchronisation here)"""

@@ -18,13 +18,16 @@ no order there.  ``overlap="order"`` is painter's order, and this is its one sta
 ``paste_host`` (a column by ``columns.paste_column_host``); a later region is blended, under its own feather ramp, into what the page holds at that
 moment, earlier regions included.  The loops of ``compose_host`` and ``columns.compose_columns_host`` do exactly that; ``"order"`` only drops the
 pairwise refusal, every other refusal stands, and the crops the networks read are taken from the original page, so they do not depend on the order.
-The device reproduces it byte for byte (``mnet_paste_ordered_u8``: one thread does all blends of a pixel, in that order).
+The device reproduces it byte for byte (``mnet_paste_ordered_u8``: one thread does all blends of a pixel, in that order).  The same order holds
+across kinds of region — a quadrilateral by ``quads.warp_paste_host``, a curve by ``curves.warp_paste_host``, in their place of the list:
+``regions.compose_regions_host``, ``mnet_paste_mixed_u8``.
 
 ``MarconetPipeline.restore_page`` ties them to the networks.  A region is an axis-aligned integer box [x1, y1, x2, y2] in page pixels: the reference
 handles regular layouts without perspective only; rotated and quadrilateral regions are ``quads``' (``MarconetPipeline.restore_page_quads``).  Out of
 scope: vertical columns that are rotated or in perspective (upright columns of stacked characters are ``columns``': ``MarconetPipeline.
-restore_page_columns``), any blend of overlapping regions other than painter's order, detection and recognition (the caller's), and several pages
-in one launch.
+restore_page_columns``; a page that mixes boxes, columns, quadrilaterals and curves, overlapping or not, is ``regions``':
+``MarconetPipeline.restore_page_regions``), any blend of overlapping regions other than painter's order, detection and recognition (the
+caller's), and several pages in one launch.
 """
 import math
 

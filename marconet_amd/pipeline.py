@@ -518,7 +518,8 @@ class MarconetPipeline:
         ``texts`` is required, for ``restore_lines``' reason.  ``details=True`` → ``(page, regions)``: per region a dict with ``plan`` (its windows),
         ``out_w`` (the width of its restored line at height 128) and ``rect`` (x0, y0, rw, rh in the result), None where it kept the background.
         Not covered: a blend of overlapping regions other than painter's order; vertical columns that are rotated or in perspective (upright columns of stacked characters:
-        ``restore_page_columns``; rotated, quadrilateral and perspective regions: ``restore_page_quads``; curved text: ``restore_page_curves``); detection and recognition (the caller's); several pages in one launch."""
+        ``restore_page_columns``; rotated, quadrilateral and perspective regions: ``restore_page_quads``; curved text: ``restore_page_curves``; a page
+        that mixes these kinds, overlapping or not: ``restore_page_regions``); detection and recognition (the caller's); several pages in one launch."""
         from . import pages
         image, restored = self._page_front("restore_page", image, len(boxes), texts, [char_boxes],
                                            "one text (and one list of character boxes, or None) per box", "boxes")
@@ -554,8 +555,9 @@ class MarconetPipeline:
         copied or launched: ``quads.check_quads``' refusals.  A quadrilateral partly outside the page is allowed (the crop replicates the page's
         border, the paste is clipped).  ``details=True`` → ``(page, regions)``: per region a dict with ``plan``, ``out_w``, ``quad`` (the corners
         in the result) and ``size`` (rw, rh: the upright foreground's size), None where it kept the background.
-        Not covered: overlapping regions; vertical columns that are rotated or in perspective (upright columns: ``restore_page_columns``); curved
-        vertical columns (curved text: ``restore_page_curves``); detection and recognition; several pages in one launch."""
+        Not covered: overlapping regions, and other kinds of region on the same page (both: ``restore_page_regions``); vertical columns that are
+        rotated or in perspective (upright columns: ``restore_page_columns``); curved vertical columns (curved text: ``restore_page_curves``);
+        detection and recognition; several pages in one launch."""
         from . import lq_device, quads as qd
         image, restored = self._page_front("restore_page_quads", image, len(quads), texts, [char_boxes],
                                            "one text (and one list of character boxes, or None) per quadrilateral", "quadrilaterals")
@@ -608,8 +610,9 @@ class MarconetPipeline:
         anything is copied or launched: ``curves.check_curves``' refusals.  A region partly outside the page is allowed (the crop replicates the
         page's border, the paste is clipped).  ``details=True`` → ``(page, regions)``: per region a dict with ``plan``, ``out_w``, ``polygon``
         (the points in the result) and ``size`` (rw, rh: the upright foreground's size), None where it kept the background.
-        Not covered: overlapping regions; curved vertical columns (upright ones: ``restore_page_columns``); detection and recognition; several
-        pages in one launch."""
+        Not covered: overlapping regions — a seal over the text lines — and other kinds of region on the same page (both:
+        ``restore_page_regions``); curved vertical columns (upright ones: ``restore_page_columns``); detection and recognition; several pages in
+        one launch."""
         from . import curves as cv, lq_device
         image, restored = self._page_front("restore_page_curves", image, len(polygons), texts, [char_boxes],
                                            "one text (and one list of character boxes, or None) per polygon", "polygons")
@@ -666,7 +669,8 @@ class MarconetPipeline:
         ``columns.compose_columns_host(..., overlap="order")``, composed by ONE ``mnet_paste_ordered_u8`` launch over one table that holds the lines'
         regions and the columns' cells together in region order, a column's cells consecutive, in the place of the two paste launches.
         Not covered: a blend of overlapping regions other than painter's order; vertical columns that are rotated or in perspective; right-to-left ordering of columns (the caller's);
-        curved vertical columns (curved horizontal text: ``restore_page_curves``); detection and recognition; several pages in one launch."""
+        curved vertical columns (curved horizontal text: ``restore_page_curves``); a column on one page with a quadrilateral or a curved region
+        (``restore_page_regions``); detection and recognition; several pages in one launch."""
         from . import columns as cl, lq_device, pages
         who, n = "restore_page_columns", len(boxes)
         image, restored = self._page_front(who, image, n, texts, [char_boxes, vertical],
@@ -721,6 +725,108 @@ class MarconetPipeline:
             return out
         return self._page_finish(plans, compose, details,
                                  [dict(rect=r) if c is None else dict(rect=r, cuts=c, widths=w) for r, c, w in zip(rects, cuts, widths)])
+
+    @torch.no_grad()
+    def restore_page_regions(self, image, regions, texts, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False,
+                             overlap="refuse"):
+        """``restore_page`` for a page that MIXES kinds of text region, which may lie over one another: a seal stamped over the text lines, a slanted
+        stamp across a table, a sign's column beside a rotated line.  ``regions[i]``: a dict with exactly one of ``"box"`` ([x1, y1, x2, y2], rounded
+        outward as in ``restore_page``; with ``"vertical": True`` a column of upright characters as in ``restore_page_columns``), ``"quad"`` (four
+        corners as in ``restore_page_quads``) and ``"polygon"`` (2K points as in ``restore_page_curves``) — the JSON ``examples/restore_regions.py``
+        reads; other keys are ignored.  ``texts``, ``char_boxes`` (in PAGE pixels), ``scale``, ``feather``, ``max_glyphs``, ``overlap_glyphs`` as in
+        those entry points.
+        → uint8 RGB [s·H, s·W, 3] on the host: the bytes of ``regions.compose_regions_host(image, lines, regions, texts, char_boxes, scale, feather,
+        overlap)`` for the lines ``restore_lines`` gives for each region's crop as its kind defines it.  A page of one kind without overlaps gives
+        that kind's entry point's bytes.
+        The page is uploaded once.  ALL windows of ALL regions go into ONE packed buffer — the host crops of the horizontal boxes at its head, then
+        at most one ``mnet_column_gather_u8``, one ``mnet_quad_crop_u8`` and one ``mnet_curve_crop_u8`` launch, each writing from its own base
+        offset — and are restored as ONE batch and joined on the device.  One ``mnet_paste_u8`` launch brings the lines of the quadrilaterals and
+        curves to their upright foregrounds in one atlas, ONE ``mnet_paste_mixed_u8`` launch whose workgroups own page tiles pastes every region in
+        list order, and ONE device→host copy brings the page back.
+        ``overlap="refuse"`` (the default): two restored regions whose interiors intersect, of whatever kinds, are a ValueError that names both
+        (``regions``' head states the rule; regions that only touch are not an overlap).  ``overlap="order"``: painter's order, ``pages``' head.
+        Both modes compose through the same launch.  Every refusal — each kind's own, naming the region — is raised before anything is copied or
+        launched.  ``details=True`` → ``(page, regions)``: per region its kind's existing dict plus ``kind`` ("line", "column", "quad", "curve"),
+        None where it kept the background.
+        Not covered: a blend of overlapping regions other than painter's order; vertical columns that are rotated or curved; detection and
+        recognition (the caller's); several pages in one launch."""
+        from . import columns as cl, curves as cv, lq_device, pages, quads as qd, regions as rg
+        who, n = "restore_page_regions", len(regions)
+        image, restored = self._page_front(who, image, n, texts, [char_boxes], "one text (and one list of character boxes, or None) per region", "regions")
+        H, W = int(image.shape[0]), int(image.shape[1])
+        cb = [None if char_boxes is None else char_boxes[i] for i in range(n)]
+        try:
+            recs = rg.normalize_regions(H, W, regions, restored, texts, cb, scale, feather, overlap)
+        except ValueError as e:
+            raise ValueError("%s: %s" % (who, e)) from None
+        sizes, local, maps = [], [None] * n, [None] * n
+        for i, r in enumerate(recs):
+            try:
+                if r["kind"] == "column" and "widths" in r:
+                    sizes.append((cl.LQ_H, sum(r["widths"])))
+                    local[i] = cl.virtual_boxes(r["widths"])
+                elif r["kind"] in ("line", "column"):
+                    sizes.append((r["box"][3] - r["box"][1], r["box"][2] - r["box"][0]))
+                    local[i] = self._boxes_in_crop(cb[i], r["box"])
+                else:
+                    sizes.append((r["ch"], r["cw"]))
+                    if r["kind"] == "quad":
+                        maps[i] = qd.quad_map(r["quad"], r["cw"], r["ch"])
+                    if cb[i] is not None:
+                        local[i] = qd.char_boxes_in_crop(cb[i], maps[i], r["cw"], r["ch"]) if r["kind"] == "quad" else \
+                            cv.char_boxes_in_crop(cb[i], r["segs"], r["cw"], r["ch"])
+            except ValueError as e:
+                raise ValueError("%s: region %d: %s" % (who, i, e)) from None
+        plans, labels, locs_rows, live = self._plan_lines(sizes, texts, local, max_glyphs, overlap_glyphs, who, "region")
+        of_kind = lambda *kinds: [i for i in live if recs[i]["kind"] in kinds]
+        lines_, cols, qds, cvs = of_kind("line"), of_kind("column"), of_kind("quad"), of_kind("curve")
+        flat, where, head = [], {}, 0                                   # the horizontal windows' crops, at the head of the packed batch
+        for i in lines_:
+            x1, y1, x2, y2 = recs[i]["box"]
+            for k, p in enumerate(plans[i]):
+                where[(i, k)] = ((y2 - y1, p.c1 - p.c0), head)
+                flat.append(np.ascontiguousarray(image[y1:y2, x1 + p.c0:x1 + p.c1]).reshape(-1))
+                head += flat[-1].size
+        columns = [(recs[i]["box"], recs[i]["cuts"], recs[i]["widths"], plans[i]) for i in cols]
+        cell_tab, shapes, offsets, q_base = cl.gather_table(columns, head)                          # its refusals, before anything is copied
+        for key, h_w, off in zip([(i, k) for i in cols for k in range(len(plans[i]))], shapes, offsets):
+            where[key] = (h_w, off)
+        q_wins, c_wins = [(i, k, p) for i in qds for k, p in enumerate(plans[i])], [(i, k, p) for i in cvs for k, p in enumerate(plans[i])]
+        q_sizes, c_sizes = [(p.c1 - p.c0, recs[i]["ch"]) for i, _, p in q_wins], [(p.c1 - p.c0, recs[i]["ch"]) for i, _, p in c_wins]
+        q_tab, c_base = qd.crop_table([maps[i] for i, _, _ in q_wins], q_sizes, [p.c0 for _, _, p in q_wins], q_base)
+        c_tab, _, nbytes = cv.crop_table([recs[i]["segs"] for i, _, _ in c_wins], c_sizes, [p.c0 for _, _, p in c_wins], c_base)
+        for wins, wh, tab in ((q_wins, q_sizes, q_tab), (c_wins, c_sizes, c_tab)):
+            for (i, k, _), (w, h), off in zip(wins, wh, tab["offset"]):
+                where[(i, k)] = ((h, w), int(off))
+
+        def compose(out_ws):
+            page_d = torch.from_numpy(np.ascontiguousarray(image)).to(next(self.sr.parameters()).device)      # the one copy of the page
+            out = pages.enlarge(page_d, int(scale))
+            if live:
+                packed = torch.empty((nbytes,), dtype=torch.uint8, device=page_d.device)         # the ragged batch of every kind's windows
+                if cols:
+                    with ops.on_device(page_d):
+                        ops.column_gather_u8(page_d, ops.table_to_device(cell_tab, page_d.device), int(cell_tab["dw"].max()), cl.LQ_H, packed)
+                if q_wins:
+                    qd.crop_quads(page_d, [maps[i] for i, _, _ in q_wins], q_sizes, [p.c0 for _, _, p in q_wins], q_base, packed)
+                if c_wins:
+                    cv.crop_curves(page_d, [recs[i]["segs"] for i, _, _ in c_wins], c_sizes, [p.c0 for _, _, p in c_wins], c_base, packed)
+                if head:
+                    packed[:head].copy_(torch.from_numpy(np.concatenate(flat)))               # the horizontal crops, as restore_page uploads them
+                order = [where[(i, k)] for i in live for k in range(len(plans[i]))]
+                prep = lq_device.prepare_packed(packed, [o[0] for o in order], [o[1] for o in order])
+                joined = self._restore_planned(prep.lq, labels, locs_rows, plans, live)
+                rg.paste_regions(out, joined, out_ws, recs, int(feather))
+            return out
+        extra = []
+        for r in recs:
+            if r["kind"] in ("line", "column"):
+                extra.append(dict(kind=r["kind"], rect=r["rect"], **({"cuts": r["cuts"], "widths": r["widths"]} if "widths" in r else {})))
+            elif r["kind"] == "quad":
+                extra.append(dict(kind="quad", quad=r["out_quad"], size=(r["rw"], r["rh"])))
+            else:
+                extra.append(dict(kind="curve", polygon=r["out_polygon"], size=(r["rw"], r["rh"])))
+        return self._page_finish(plans, compose, details, extra)
 
     @torch.no_grad()
     def _strips_from_images(self, images, texts, boxes, max_glyphs, preview, host_preview):

@@ -14,7 +14,8 @@ fp64, what "the crop of a quadrilateral" and "the line pasted into a quadrilater
 A region is four corners [[x, y]] x 4 in page pixels (pixel i covers [i, i + 1)), in the text's own reading order: top-left, top-right,
 bottom-right, bottom-left of the line as it is read — a line rotated by 90 degrees is a quadrilateral whose first corner is elsewhere.  For an
 integer axis-aligned box all of this is ``pages``' own bytes; for its right-angle rotations it is ``np.rot90`` of them.  ``MarconetPipeline.
-restore_page_quads`` ties it to the networks.  Out of scope: vertical columns that are rotated or in perspective (upright ones: ``columns``), curved vertical columns (curved text: ``curves``), detection and
+restore_page_quads`` ties it to the networks.  Out of scope: overlapping regions and pages that hold other kinds of region as well (both are
+``regions``': ``MarconetPipeline.restore_page_regions``), vertical columns that are rotated or in perspective (upright ones: ``columns``), curved vertical columns (curved text: ``curves``), detection and
 recognition, several pages per launch.
 """
 import math
@@ -248,11 +249,11 @@ def compose_quads_host(page, lines, quads, scale=4, feather=8):
 
 
 # ------------------------------------------------------------------------------------------------------------------- the device path
-def crop_table(maps, sizes, c0s=None):
+def crop_table(maps, sizes, c0s=None, base=0):
     """→ (numpy record array of ``mnet_quad_crop``, the flat buffer's size in bytes): crop k is ``sizes[k]`` = (w, h) under ``maps[k]`` from column
-    ``c0s[k]`` (default 0) of its region's rectified crop; the crops are packed tightly in order"""
+    ``c0s[k]`` (default 0) of its region's rectified crop; the crops are packed tightly in order from byte ``base``"""
     tab = np.zeros((len(maps),), dtype=np.dtype(_lib.QuadCrop))
-    off = 0
+    off = int(base)
     for k, (M, (w, h)) in enumerate(zip(maps, sizes)):
         tab[k] = (off, int(w), int(h), 0 if c0s is None else int(c0s[k]), 0, [float(v) for v in M])
         off += 3 * int(w) * int(h)
@@ -268,11 +269,15 @@ def paste_table(regions, feather, atlas_xy):
     return tab
 
 
-def crop_quads(page_d, maps, sizes, c0s=None):
-    """``page_d`` uint8 RGB [H, W, 3] on the device → (uint8 [bytes] on the device: ``warp_crop_host`` of every crop, packed tightly in order, the
-    offsets of the crops): one copy of the table, one launch"""
-    tab, nbytes = crop_table(maps, sizes, c0s)
-    dst = torch.empty((nbytes,), dtype=torch.uint8, device=page_d.device)
+def crop_quads(page_d, maps, sizes, c0s=None, base=0, dst=None):
+    """``page_d`` uint8 RGB [H, W, 3] on the device → (uint8 [bytes] on the device: ``warp_crop_host`` of every crop, packed tightly in order from
+    byte ``base``, the offsets of the crops): one copy of the table, one launch.  ``dst``: an existing flat buffer that holds the crops' bytes
+    (the packed batch several sources share), written inside the crops only; None: a new one, the first ``base`` bytes left to the caller"""
+    tab, nbytes = crop_table(maps, sizes, c0s, base)
+    if dst is None:
+        dst = torch.empty((nbytes,), dtype=torch.uint8, device=page_d.device)
+    elif dst.dtype != torch.uint8 or dst.dim() != 1 or dst.numel() < nbytes:
+        raise ValueError("crop_quads: a flat uint8 buffer of at least %d bytes expected" % nbytes)
     with ops.on_device(page_d):
         ops.quad_crop_u8(page_d, ops.table_to_device(tab, page_d.device), max(int(w) for w, _ in sizes), max(int(h) for _, h in sizes), dst)
     return dst, [int(o) for o in tab["offset"]]
