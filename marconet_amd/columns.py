@@ -245,11 +245,16 @@ def mixed_table(joined, regions, feather):
     """one table for ``pages.paste_ordered``: ``regions`` in paste order, region r = (its line's index in ``joined``, its rectangle in the enlarged
     page, the width of its line — a horizontal line — or its column as ``gather_table`` takes it) → record array of ``mnet_column_paste``: a line as
     ``pages.as_cell`` of ``pages.build_table``'s record, a column as ``paste_table``'s cells, consecutive.  ``paste_columns``' refusals."""
-    rows, parts = int(joined.shape[1]), []
     for l, rect, what in regions:
         if isinstance(what, tuple):
             _check_lines("mixed_table", joined, [l], [what])
-            parts.append(paste_table([what], [l], [rect], feather, rows))
-        else:
-            parts.append(pages.as_cell(pages.build_table([rect], [int(what)], feather, rows, [l])))
+    parts = [region_cells(l, rect, what, feather, int(joined.shape[1])) for l, rect, what in regions]
     return np.concatenate(parts) if parts else np.zeros((0,), dtype=np.dtype(_lib.ColumnPaste))
+
+
+def region_cells(l, rect, what, feather, rows=ROW_H):
+    """the ``mnet_column_paste`` records of ONE region of ``mixed_table``, which reads line ``l`` into ``rect``: ``what`` is the width of a horizontal
+    line (→ one record, ``pages.as_cell`` of ``pages.build_table``'s) or a column as ``gather_table`` takes it (→ ``paste_table``'s cells)"""
+    if isinstance(what, tuple):
+        return paste_table([what], [l], [rect], feather, rows)
+    return pages.as_cell(pages.build_table([rect], [int(what)], feather, rows, [l]))

@@ -2,7 +2,7 @@
 // every column resized on its own and laid side by side as the horizontal strip mnet_lq_from_u8 reads), for all columns of the page in ONE launch.  The
 // definition is the host's, byte for byte: marconet_amd/columns.py's virtual_strip.  The arithmetic is lq_from_u8_kernel's: the 8-bit INTER_CUBIC
 // resample with the taps of lq_taps.h, both passes in integers, one rounding shift by 22 bits (page_tile.h).  The scatter out, mnet_column_paste_u8,
-// stands beside its twin in page_kernels.hip.
+// stands beside its twin in page_kernels.hip; a cell's per-pixel body is cell_paste.h's.
 //
 // Launch shape: page_tile.h's tile over one cell's output, counted from the cell's own corner; the grid is n cells x the tiles of max_dw x dst_h; a
 // workgroup whose tile lies outside its cell returns before it loads anything.  Bytes are read and written with byte loads and stores (3-byte pixels

@@ -1,5 +1,6 @@
-// What the page-path kernels share (lq_kernels.hip, page_kernels.hip, column_kernels.hip, quad_kernels.hip): the tile, its place in the grid, the
-// cubic taps of a tile in LDS and the integer cubic itself — stated once, so that a fix reaches every kernel.
+// What the page-path kernels share (lq_kernels.hip, page_kernels.hip, column_kernels.hip, quad_kernels.hip and, through cell_paste.h,
+// mixed_kernels.hip): the tile, its place in the grid, the cubic taps of a tile in LDS and the integer cubic itself — stated once, so that a fix
+// reaches every kernel.
 //
 // The tile: 256 threads take 64 columns x 16 rows of ONE descriptor's output, counted from that output's own corner; thread t has column t % 64 and
 // the rows t / 64 + 4 i, i < 4 (x fastest: stores coalesce).  The launcher does not see the device table, so the grid is n descriptors x the tiles of

@@ -778,37 +778,60 @@ def _need_u8(who, name, t, dims):
         raise TypeError("%s: %s must be uint8 %s" % (who, name, _U8_FORMS[dims]))
 
 
+def _paste_lines(who, unit, struct, lines, table, page):
+    """``paste_u8`` and ``column_paste_u8``: the one wrapper of the two per-descriptor pastes, whose descriptor ``who`` calls a ``unit``"""
+    lib = _lib.load()
+    _need_cuda(lines, table, page)
+    _need_u8(who, "lines", lines, 4)
+    _need_u8(who, "page", page, 3)
+    _check_table(who, "%s table" % unit, table, struct, 8)
+    if table.shape[0] < 1 or lines.numel() == 0 or page.numel() == 0:
+        raise ValueError("%s: empty batch (%d %ss, lines %s, page %s)" % (who, table.shape[0], unit, list(lines.shape), list(page.shape)))
+    _lib.check(getattr(lib, "mnet_" + who)(_p(lines), int(lines.shape[0]), int(lines.shape[1]), int(lines.shape[2]), _p(table), int(table.shape[0]), _p(page),
+                                           int(page.shape[0]), int(page.shape[1]), _stream()), "mnet_" + who)
+    return page
+
+
 def paste_u8(lines, regions, page):
     """mnet_paste_u8 (the bytes of pages.paste_host, region by region): ``lines`` uint8 [L,rows,line_w,3] BGR (``stitch_u8``), ``regions`` uint8
     [R, sizeof(mnet_paste_region)] (``_lib.PasteRegion``), ``page`` uint8 [H,W,3] RGB holding the background — all on the device.  ``page`` is
     modified IN PLACE inside the regions' rectangles and returned; a region whose descriptor cannot be followed keeps the background."""
+    return _paste_lines("paste_u8", "region", _lib.PasteRegion, lines, regions, page)
+
+
+def column_paste_u8(lines, cells, page):
+    """mnet_column_paste_u8 (the bytes of columns.paste_column_host, cell by cell): ``lines`` uint8 [L,rows,line_w,3] BGR (``stitch_u8``), ``cells``
+    uint8 [n, sizeof(mnet_column_paste)] (``_lib.ColumnPaste``), ``page`` uint8 [H,W,3] RGB holding the background — all on the device.  ``page`` is
+    modified IN PLACE inside the cells' rectangles and returned; a cell whose descriptor cannot be followed keeps the background."""
+    return _paste_lines("column_paste_u8", "cell", _lib.ColumnPaste, lines, cells, page)
+
+
+def _warp(who, src_name, src, table_name, table, struct, segs, max_w, max_h, dst_name, dst):
+    """the one wrapper of the quadrilateral's and the curve's crop and paste: ``src`` (the page, or the atlas) is read through ``table`` (and the
+    curve's ``segs``, None for a quadrilateral) into ``dst`` (the flat batch [bytes], or the page), which is returned"""
     lib = _lib.load()
-    _need_cuda(lines, regions, page)
-    _need_u8("paste_u8", "lines", lines, 4)
-    _need_u8("paste_u8", "page", page, 3)
-    _check_table("paste_u8", "region table", regions, _lib.PasteRegion, 8)
-    if regions.shape[0] < 1 or lines.numel() == 0 or page.numel() == 0:
-        raise ValueError("paste_u8: empty batch (%d regions, lines %s, page %s)" % (regions.shape[0], list(lines.shape), list(page.shape)))
-    _lib.check(lib.mnet_paste_u8(_p(lines), int(lines.shape[0]), int(lines.shape[1]), int(lines.shape[2]), _p(regions), int(regions.shape[0]), _p(page),
-                                 int(page.shape[0]), int(page.shape[1]), _stream()), "mnet_paste_u8")
-    return page
+    _need_cuda(*[t for t in (src, table, segs, dst) if t is not None])
+    _need_u8(who, src_name, src, 3)
+    _need_u8(who, dst_name, dst, 3 if dst_name == "page" else 1)
+    _check_table(who, "%s table" % table_name, table, struct, 8)
+    if segs is not None:
+        _check_table(who, "segment table", segs, _lib.CurveSeg, 8)
+    if table.shape[0] < 1 or (segs is not None and segs.shape[0] < 1) or src.numel() == 0 or dst.numel() == 0 or int(max_w) < 1 or int(max_h) < 1:
+        ends = "atlas %s, page %s" % (list(src.shape), list(dst.shape)) if dst_name == "page" else "page %s, %d bytes" % (list(src.shape), dst.numel())
+        raise ValueError("%s: empty batch (%d %ss of at most %d x %d, %s%s)" % (who, table.shape[0], table_name, int(max_w), int(max_h),
+                                                                               "" if segs is None else "%d segments, " % segs.shape[0], ends))
+    seg_args = () if segs is None else (_p(segs), int(segs.shape[0]))
+    dst_args = (int(dst.shape[0]), int(dst.shape[1])) if dst_name == "page" else (int(dst.numel()),)
+    _lib.check(getattr(lib, "mnet_" + who)(_p(src), int(src.shape[0]), int(src.shape[1]), _p(table), int(table.shape[0]), *seg_args, int(max_w), int(max_h),
+                                           _p(dst), *dst_args, _stream()), "mnet_" + who)
+    return dst
 
 
 def quad_crop_u8(page, crops, max_w, max_h, dst):
     """mnet_quad_crop_u8 (the bytes of quads.warp_crop_host, crop by crop): ``page`` uint8 [H,W,3] RGB, ``crops`` uint8 [n, sizeof(mnet_quad_crop)]
     (``_lib.QuadCrop``), ``dst`` uint8 [bytes], the flat buffer of the ragged batch — all on the device; ``max_w`` / ``max_h``: the largest crop size
     of the table.  ``dst`` is written inside the crops only and returned; a crop whose descriptor cannot be followed leaves its bytes as they are."""
-    lib = _lib.load()
-    _need_cuda(page, crops, dst)
-    _need_u8("quad_crop_u8", "page", page, 3)
-    _need_u8("quad_crop_u8", "dst", dst, 1)
-    _check_table("quad_crop_u8", "crop table", crops, _lib.QuadCrop, 8)
-    if crops.shape[0] < 1 or page.numel() == 0 or dst.numel() == 0 or int(max_w) < 1 or int(max_h) < 1:
-        raise ValueError("quad_crop_u8: empty batch (%d crops of at most %d x %d, page %s, %d bytes)"
-                         % (crops.shape[0], int(max_w), int(max_h), list(page.shape), dst.numel()))
-    _lib.check(lib.mnet_quad_crop_u8(_p(page), int(page.shape[0]), int(page.shape[1]), _p(crops), int(crops.shape[0]), int(max_w), int(max_h), _p(dst),
-                                     int(dst.numel()), _stream()), "mnet_quad_crop_u8")
-    return dst
+    return _warp("quad_crop_u8", "page", page, "crop", crops, _lib.QuadCrop, None, max_w, max_h, "dst", dst)
 
 
 def quad_paste_u8(atlas, regions, max_bw, max_bh, page):
@@ -816,17 +839,7 @@ def quad_paste_u8(atlas, regions, max_bw, max_bh, page):
     foregrounds, ``regions`` uint8 [R, sizeof(mnet_quad_region)] (``_lib.QuadRegion``), ``page`` uint8 [H,W,3] RGB holding the background — all on
     the device; ``max_bw`` / ``max_bh``: the largest bounding box of the table.  ``page`` is modified IN PLACE inside the quadrilaterals and
     returned; a region whose descriptor cannot be followed keeps the background."""
-    lib = _lib.load()
-    _need_cuda(atlas, regions, page)
-    _need_u8("quad_paste_u8", "atlas", atlas, 3)
-    _need_u8("quad_paste_u8", "page", page, 3)
-    _check_table("quad_paste_u8", "region table", regions, _lib.QuadRegion, 8)
-    if regions.shape[0] < 1 or atlas.numel() == 0 or page.numel() == 0 or int(max_bw) < 1 or int(max_bh) < 1:
-        raise ValueError("quad_paste_u8: empty batch (%d regions of at most %d x %d, atlas %s, page %s)"
-                         % (regions.shape[0], int(max_bw), int(max_bh), list(atlas.shape), list(page.shape)))
-    _lib.check(lib.mnet_quad_paste_u8(_p(atlas), int(atlas.shape[0]), int(atlas.shape[1]), _p(regions), int(regions.shape[0]), int(max_bw), int(max_bh),
-                                      _p(page), int(page.shape[0]), int(page.shape[1]), _stream()), "mnet_quad_paste_u8")
-    return page
+    return _warp("quad_paste_u8", "atlas", atlas, "region", regions, _lib.QuadRegion, None, max_bw, max_bh, "page", page)
 
 
 def curve_crop_u8(page, crops, segs, max_w, max_h, dst):
@@ -834,18 +847,7 @@ def curve_crop_u8(page, crops, segs, max_w, max_h, dst):
     (``_lib.CurveCrop``), ``segs`` uint8 [S, sizeof(mnet_curve_seg)] (``_lib.CurveSeg``), ``dst`` uint8 [bytes], the flat buffer of the ragged batch —
     all on the device; ``max_w`` / ``max_h``: the largest crop size of the table.  ``dst`` is written inside the crops only and returned; a crop whose
     descriptor cannot be followed leaves its bytes as they are."""
-    lib = _lib.load()
-    _need_cuda(page, crops, segs, dst)
-    _need_u8("curve_crop_u8", "page", page, 3)
-    _need_u8("curve_crop_u8", "dst", dst, 1)
-    _check_table("curve_crop_u8", "crop table", crops, _lib.CurveCrop, 8)
-    _check_table("curve_crop_u8", "segment table", segs, _lib.CurveSeg, 8)
-    if crops.shape[0] < 1 or segs.shape[0] < 1 or page.numel() == 0 or dst.numel() == 0 or int(max_w) < 1 or int(max_h) < 1:
-        raise ValueError("curve_crop_u8: empty batch (%d crops of at most %d x %d, %d segments, page %s, %d bytes)"
-                         % (crops.shape[0], int(max_w), int(max_h), segs.shape[0], list(page.shape), dst.numel()))
-    _lib.check(lib.mnet_curve_crop_u8(_p(page), int(page.shape[0]), int(page.shape[1]), _p(crops), int(crops.shape[0]), _p(segs), int(segs.shape[0]),
-                                      int(max_w), int(max_h), _p(dst), int(dst.numel()), _stream()), "mnet_curve_crop_u8")
-    return dst
+    return _warp("curve_crop_u8", "page", page, "crop", crops, _lib.CurveCrop, segs, max_w, max_h, "dst", dst)
 
 
 def curve_paste_u8(atlas, regions, segs, max_bw, max_bh, page):
@@ -853,19 +855,7 @@ def curve_paste_u8(atlas, regions, segs, max_bw, max_bh, page):
     foregrounds, ``regions`` uint8 [R, sizeof(mnet_curve_region)] (``_lib.CurveRegion``), ``segs`` uint8 [S, sizeof(mnet_curve_seg)]
     (``_lib.CurveSeg``), ``page`` uint8 [H,W,3] RGB holding the background — all on the device; ``max_bw`` / ``max_bh``: the largest bounding box of
     the table.  ``page`` is modified IN PLACE inside the regions and returned; a region whose descriptor cannot be followed keeps the background."""
-    lib = _lib.load()
-    _need_cuda(atlas, regions, segs, page)
-    _need_u8("curve_paste_u8", "atlas", atlas, 3)
-    _need_u8("curve_paste_u8", "page", page, 3)
-    _check_table("curve_paste_u8", "region table", regions, _lib.CurveRegion, 8)
-    _check_table("curve_paste_u8", "segment table", segs, _lib.CurveSeg, 8)
-    if regions.shape[0] < 1 or segs.shape[0] < 1 or atlas.numel() == 0 or page.numel() == 0 or int(max_bw) < 1 or int(max_bh) < 1:
-        raise ValueError("curve_paste_u8: empty batch (%d regions of at most %d x %d, %d segments, atlas %s, page %s)"
-                         % (regions.shape[0], int(max_bw), int(max_bh), segs.shape[0], list(atlas.shape), list(page.shape)))
-    _lib.check(lib.mnet_curve_paste_u8(_p(atlas), int(atlas.shape[0]), int(atlas.shape[1]), _p(regions), int(regions.shape[0]), _p(segs),
-                                       int(segs.shape[0]), int(max_bw), int(max_bh), _p(page), int(page.shape[0]), int(page.shape[1]), _stream()),
-               "mnet_curve_paste_u8")
-    return page
+    return _warp("curve_paste_u8", "atlas", atlas, "region", regions, _lib.CurveRegion, segs, max_bw, max_bh, "page", page)
 
 
 def column_gather_u8(page, cells, max_dw, dst_h, dst):
@@ -886,25 +876,24 @@ def column_gather_u8(page, cells, max_dw, dst_h, dst):
     return dst
 
 
-def column_paste_u8(lines, cells, page):
-    """mnet_column_paste_u8 (the bytes of columns.paste_column_host, cell by cell): ``lines`` uint8 [L,rows,line_w,3] BGR (``stitch_u8``), ``cells``
-    uint8 [n, sizeof(mnet_column_paste)] (``_lib.ColumnPaste``), ``page`` uint8 [H,W,3] RGB holding the background — all on the device.  ``page`` is
-    modified IN PLACE inside the cells' rectangles and returned; a cell whose descriptor cannot be followed keeps the background."""
-    lib = _lib.load()
-    _need_cuda(lines, cells, page)
-    _need_u8("column_paste_u8", "lines", lines, 4)
-    _need_u8("column_paste_u8", "page", page, 3)
-    _check_table("column_paste_u8", "cell table", cells, _lib.ColumnPaste, 8)
-    if cells.shape[0] < 1 or lines.numel() == 0 or page.numel() == 0:
-        raise ValueError("column_paste_u8: empty batch (%d cells, lines %s, page %s)" % (cells.shape[0], list(lines.shape), list(page.shape)))
-    _lib.check(lib.mnet_column_paste_u8(_p(lines), int(lines.shape[0]), int(lines.shape[1]), int(lines.shape[2]), _p(cells), int(cells.shape[0]), _p(page),
-                                        int(page.shape[0]), int(page.shape[1]), _stream()), "mnet_column_paste_u8")
-    return page
-
-
 def page_tiles(page_h, page_w):
     """the count of 64 x 16 tiles of a page, row-major from its origin (csrc/page_tile.h's pt_grid(1, page_w, page_h)) → (tiles_x, tiles_y)"""
     return -(-int(page_w) // 64), -(-int(page_h) // 16)
+
+
+def _check_order(who, spans, order, items=None):
+    """what the two page-tile compositors ask alike of their spans and order (and the mixed one of its items)"""
+    _check_table(who, "span table", spans, _lib.TileSpan, 4)
+    if order.dtype != torch.int32 or order.dim() != 1:
+        raise TypeError("%s: order must be int32 [n]" % who)
+    if not spans.is_contiguous() or not order.is_contiguous() or not (items is None or items.is_contiguous()):
+        raise ValueError("%s: %sspans and order must be contiguous" % (who, "" if items is None else "items, "))
+
+
+def _check_span_count(who, spans, page):
+    tiles_x, tiles_y = page_tiles(page.shape[0], page.shape[1])
+    if spans.shape[0] != tiles_x * tiles_y:
+        raise ValueError("%s: %d spans for a page of %d x %d tiles" % (who, spans.shape[0], tiles_x, tiles_y))
 
 
 def paste_ordered_u8(lines, cells, spans, order, page):
@@ -914,21 +903,16 @@ def paste_ordered_u8(lines, cells, spans, order, page):
     ``order`` int32 [n_order], indices into ``cells`` (``pages.bin_tiles`` makes both), ``page`` uint8 [H,W,3] RGB holding the background — all on the
     device.  ``page`` is modified IN PLACE inside the cells' rectangles and returned; a span, an entry or a cell that cannot be followed is skipped."""
     lib = _lib.load()
+    who = "paste_ordered_u8"
     _need_cuda(lines, cells, spans, order, page)
-    _need_u8("paste_ordered_u8", "lines", lines, 4)
-    _need_u8("paste_ordered_u8", "page", page, 3)
-    _check_table("paste_ordered_u8", "cell table", cells, _lib.ColumnPaste, 8)
-    _check_table("paste_ordered_u8", "span table", spans, _lib.TileSpan, 4)
-    if order.dtype != torch.int32 or order.dim() != 1:
-        raise TypeError("paste_ordered_u8: order must be int32 [n]")
-    if not spans.is_contiguous() or not order.is_contiguous():
-        raise ValueError("paste_ordered_u8: spans and order must be contiguous")
+    _need_u8(who, "lines", lines, 4)
+    _need_u8(who, "page", page, 3)
+    _check_table(who, "cell table", cells, _lib.ColumnPaste, 8)
+    _check_order(who, spans, order)
     if cells.shape[0] < 1 or order.shape[0] < 1 or lines.numel() == 0 or page.numel() == 0:
         raise ValueError("paste_ordered_u8: empty batch (%d cells, %d order entries, lines %s, page %s)"
                          % (cells.shape[0], order.shape[0], list(lines.shape), list(page.shape)))
-    tiles_x, tiles_y = page_tiles(page.shape[0], page.shape[1])
-    if spans.shape[0] != tiles_x * tiles_y:
-        raise ValueError("paste_ordered_u8: %d spans for a page of %d x %d tiles" % (spans.shape[0], tiles_x, tiles_y))
+    _check_span_count(who, spans, page)
     _lib.check(lib.mnet_paste_ordered_u8(_p(lines), int(lines.shape[0]), int(lines.shape[1]), int(lines.shape[2]), _p(cells), int(cells.shape[0]),
                                          _p(spans), int(spans.shape[0]), _p(order), int(order.shape[0]), _p(page), int(page.shape[0]),
                                          int(page.shape[1]), _stream()), "mnet_paste_ordered_u8")
@@ -956,20 +940,14 @@ def paste_mixed_u8(lines, atlas, cells, quads, curves, segs, items, spans, order
         if table is not None:
             _check_table(who, what, table, struct, 8)
     _check_table(who, "item table", items, _lib.PageItem, 4)
-    _check_table(who, "span table", spans, _lib.TileSpan, 4)
-    if order.dtype != torch.int32 or order.dim() != 1:
-        raise TypeError("%s: order must be int32 [n]" % who)
-    if not spans.is_contiguous() or not order.is_contiguous() or not items.is_contiguous():
-        raise ValueError("%s: items, spans and order must be contiguous" % who)
+    _check_order(who, spans, order, items)
     n = [0 if t is None else int(t.shape[0]) for t in (cells, quads, curves, segs)]
     if items.shape[0] < 1 or order.shape[0] < 1 or page.numel() == 0 or (n[0] and (lines is None or lines.numel() == 0)) or \
             ((n[1] or n[2]) and (atlas is None or atlas.numel() == 0)) or (n[2] and not n[3]):
         raise ValueError("%s: empty batch (%d items, %d order entries, %d cells, %d quads, %d curves, %d segments, lines %s, atlas %s, page %s)"
                          % (who, items.shape[0], order.shape[0], n[0], n[1], n[2], n[3], None if lines is None else list(lines.shape),
                             None if atlas is None else list(atlas.shape), list(page.shape)))
-    tiles_x, tiles_y = page_tiles(page.shape[0], page.shape[1])
-    if spans.shape[0] != tiles_x * tiles_y:
-        raise ValueError("%s: %d spans for a page of %d x %d tiles" % (who, spans.shape[0], tiles_x, tiles_y))
+    _check_span_count(who, spans, page)
     ptr = lambda t: None if t is None else _p(t)
     ls = (0, 0, 0) if lines is None else tuple(int(v) for v in lines.shape[:3])
     ats = (0, 0) if atlas is None else tuple(int(v) for v in atlas.shape[:2])

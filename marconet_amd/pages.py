@@ -229,6 +229,35 @@ def paste_rects(out, joined, rects, out_ws, feather, line_index=None):
     return out
 
 
+def atlas_layout(sizes):
+    """the atlas of upright foregrounds that quadrilaterals and curved regions are pasted from: ``sizes[i]`` = (rw, rh), or None for a region without
+    one → (per region its rectangle (0, y, rw, rh), the rectangles stacked vertically in order, None where there is none; the atlas' (Σ rh, max rw))"""
+    rects, y = [None] * len(sizes), 0
+    for i, size in enumerate(sizes):
+        if size is not None:
+            rects[i] = (0, y, int(size[0]), int(size[1]))
+            y += int(size[1])
+    return rects, (y, max((r[2] for r in rects if r is not None), default=0))
+
+
+def fill_atlas(joined, fg, atlas_hw):
+    """→ the atlas on ``joined``'s device, uint8 RGB [Σ rh, max rw, 3], zeroed, with every line of ``joined`` brought to its upright foreground —
+    ``line_to_rect``'s bytes — by ONE ``mnet_paste_u8`` launch; ``fg``: ``build_table`` of ``atlas_layout``'s rectangles at feather 0"""
+    atlas = torch.zeros(tuple(atlas_hw) + (3,), dtype=torch.uint8, device=joined.device)
+    with ops.on_device(joined):
+        return ops.paste_u8(joined, ops.table_to_device(fg, joined.device), atlas)
+
+
+def crop_buffer(who, dst, nbytes, device):
+    """the flat buffer ``quads.crop_quads`` / ``curves.crop_curves`` write ``nbytes`` of: ``dst`` as given (ValueError naming ``who`` where it cannot
+    hold them), or a new one on ``device`` for None"""
+    if dst is None:
+        return torch.empty((nbytes,), dtype=torch.uint8, device=device)
+    if dst.dtype != torch.uint8 or dst.dim() != 1 or dst.numel() < nbytes:
+        raise ValueError("%s: a flat uint8 buffer of at least %d bytes expected" % (who, nbytes))
+    return dst
+
+
 def as_cell(regions):
     """record array of ``mnet_paste_region`` → the same regions as ``mnet_column_paste`` records: the slice starts at column 0 and the feather
     rectangle is the region's own (csrc/page_kernels.hip's as_cell), so that one table holds lines and column cells together"""

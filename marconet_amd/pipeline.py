@@ -521,20 +521,21 @@ class MarconetPipeline:
         ``restore_page_columns``; rotated, quadrilateral and perspective regions: ``restore_page_quads``; curved text: ``restore_page_curves``; a page
         that mixes these kinds, overlapping or not: ``restore_page_regions``); detection and recognition (the caller's); several pages in one launch."""
         from . import pages
-        image, restored = self._page_front("restore_page", image, len(boxes), texts, [char_boxes],
-                                           "one text (and one list of character boxes, or None) per box", "boxes")
+        who = "restore_page"
+        image, restored = self._page_front(who, image, len(boxes), texts, [char_boxes], "one text (and one list of character boxes, or None) per box", "boxes")
         H, W = int(image.shape[0]), int(image.shape[1])
         boxes = [pages.round_box(b, H, W) for b in boxes]
         try:
             rects = pages.region_rects(H, W, boxes, restored, scale, feather, overlap=overlap)
         except ValueError as e:
-            raise ValueError("restore_page: %s" % e) from None
-        crops = [image[b[1]:b[3], b[0]:b[2]] for b in boxes]
-        local = [self._boxes_in_crop(None if char_boxes is None else char_boxes[i], b) for i, b in enumerate(boxes)]
-        joined, plans, live = self._joined_lines(crops, texts, local, max_glyphs, overlap_glyphs, "restore_page", "region")
-        dev = next(self.sr.parameters()).device
-        return self._page_finish(plans, lambda out_ws: pages.compose_page(image, joined, out_ws, boxes, scale, feather, device=dev, overlap=overlap), details,
-                                 [dict(rect=r) for r in rects])
+            raise ValueError("%s: %s" % (who, e)) from None
+
+        def paste(out, joined, out_ws, live, plans):
+            if pages.check_overlap(overlap):
+                return pages.paste_ordered(out, joined, pages.as_cell(pages.build_table(rects, out_ws, feather, int(joined.shape[1]))))
+            return pages.paste_rects(out, joined, rects, out_ws, feather)
+        return self._restore_page_records(who, image, [dict(kind="line", box=b, rect=r) for b, r in zip(boxes, rects)], texts, char_boxes, scale, max_glyphs,
+                                          overlap_glyphs, paste, details, [dict(rect=r) for r in rects])
 
     @torch.no_grad()
     def restore_page_quads(self, image, quads, texts, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False):
@@ -558,36 +559,17 @@ class MarconetPipeline:
         Not covered: overlapping regions, and other kinds of region on the same page (both: ``restore_page_regions``); vertical columns that are
         rotated or in perspective (upright columns: ``restore_page_columns``); curved vertical columns (curved text: ``restore_page_curves``);
         detection and recognition; several pages in one launch."""
-        from . import lq_device, quads as qd
-        image, restored = self._page_front("restore_page_quads", image, len(quads), texts, [char_boxes],
+        from . import quads as qd
+        who = "restore_page_quads"
+        image, restored = self._page_front(who, image, len(quads), texts, [char_boxes],
                                            "one text (and one list of character boxes, or None) per quadrilateral", "quadrilaterals")
         try:
             regions = qd.check_quads(int(image.shape[0]), int(image.shape[1]), quads, restored, scale, feather)
         except ValueError as e:
-            raise ValueError("restore_page_quads: %s" % e) from None
-        maps = [qd.quad_map(r["quad"], r["cw"], r["ch"]) for r in regions]
-        local = [None] * len(regions)
-        for i, r in enumerate(regions):
-            if char_boxes is not None and char_boxes[i] is not None:
-                try:
-                    local[i] = qd.char_boxes_in_crop(char_boxes[i], maps[i], r["cw"], r["ch"])
-                except ValueError as e:
-                    raise ValueError("restore_page_quads: region %d: %s" % (i, e)) from None
-        plans, labels, locs_rows, live = self._plan_lines([(r["ch"], r["cw"]) for r in regions], texts, local, max_glyphs, overlap_glyphs,
-                                                          "restore_page_quads", "region")
-        wins = [(i, p) for i in live for p in plans[i]]
-
-        def compose(out_ws):
-            page_d = torch.from_numpy(np.ascontiguousarray(image)).to(next(self.sr.parameters()).device)      # the one copy of the pixels
-            out = qd.enlarge(page_d, int(scale))
-            if live:
-                sizes = [(p.c1 - p.c0, regions[i]["ch"]) for i, p in wins]
-                crops, offsets = qd.crop_quads(page_d, [maps[i] for i, _ in wins], sizes, [p.c0 for _, p in wins])
-                prep = lq_device.prepare_packed(crops, [(h, w) for w, h in sizes], offsets)
-                joined = self._restore_planned(prep.lq, labels, locs_rows, plans, live)
-                qd.paste_quads(out, joined, out_ws, regions, int(feather))
-            return out
-        return self._page_finish(plans, compose, details, [dict(quad=r["out_quad"], size=(r["rw"], r["rh"])) for r in regions])
+            raise ValueError("%s: %s" % (who, e)) from None
+        return self._restore_page_records(who, image, [dict(r, kind="quad") for r in regions], texts, char_boxes, scale, max_glyphs, overlap_glyphs,
+                                          lambda out, joined, out_ws, live, plans: qd.paste_quads(out, joined, out_ws, regions, int(feather)), details,
+                                          [dict(quad=r["out_quad"], size=(r["rw"], r["rh"])) for r in regions])
 
     @torch.no_grad()
     def restore_page_curves(self, image, polygons, texts, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False):
@@ -613,35 +595,17 @@ class MarconetPipeline:
         Not covered: overlapping regions — a seal over the text lines — and other kinds of region on the same page (both:
         ``restore_page_regions``); curved vertical columns (upright ones: ``restore_page_columns``); detection and recognition; several pages in
         one launch."""
-        from . import curves as cv, lq_device
-        image, restored = self._page_front("restore_page_curves", image, len(polygons), texts, [char_boxes],
+        from . import curves as cv
+        who = "restore_page_curves"
+        image, restored = self._page_front(who, image, len(polygons), texts, [char_boxes],
                                            "one text (and one list of character boxes, or None) per polygon", "polygons")
         try:
             regions = cv.check_curves(int(image.shape[0]), int(image.shape[1]), polygons, restored, scale, feather)
         except ValueError as e:
-            raise ValueError("restore_page_curves: %s" % e) from None
-        local = [None] * len(regions)
-        for i, r in enumerate(regions):
-            if char_boxes is not None and char_boxes[i] is not None:
-                try:
-                    local[i] = cv.char_boxes_in_crop(char_boxes[i], r["segs"], r["cw"], r["ch"])
-                except ValueError as e:
-                    raise ValueError("restore_page_curves: region %d: %s" % (i, e)) from None
-        plans, labels, locs_rows, live = self._plan_lines([(r["ch"], r["cw"]) for r in regions], texts, local, max_glyphs, overlap_glyphs,
-                                                          "restore_page_curves", "region")
-        wins = [(i, p) for i in live for p in plans[i]]
-
-        def compose(out_ws):
-            page_d = torch.from_numpy(np.ascontiguousarray(image)).to(next(self.sr.parameters()).device)      # the one copy of the pixels
-            out = cv.enlarge(page_d, int(scale))
-            if live:
-                sizes = [(p.c1 - p.c0, regions[i]["ch"]) for i, p in wins]
-                crops, offsets = cv.crop_curves(page_d, [regions[i]["segs"] for i, _ in wins], sizes, [p.c0 for _, p in wins])
-                prep = lq_device.prepare_packed(crops, [(h, w) for w, h in sizes], offsets)
-                joined = self._restore_planned(prep.lq, labels, locs_rows, plans, live)
-                cv.paste_curves(out, joined, out_ws, regions, int(feather))
-            return out
-        return self._page_finish(plans, compose, details, [dict(polygon=r["out_polygon"], size=(r["rw"], r["rh"])) for r in regions])
+            raise ValueError("%s: %s" % (who, e)) from None
+        return self._restore_page_records(who, image, [dict(r, kind="curve") for r in regions], texts, char_boxes, scale, max_glyphs, overlap_glyphs,
+                                          lambda out, joined, out_ws, live, plans: cv.paste_curves(out, joined, out_ws, regions, int(feather)), details,
+                                          [dict(polygon=r["out_polygon"], size=(r["rw"], r["rh"])) for r in regions])
 
     @torch.no_grad()
     def restore_page_columns(self, image, boxes, texts, vertical=None, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False,
@@ -671,60 +635,35 @@ class MarconetPipeline:
         Not covered: a blend of overlapping regions other than painter's order; vertical columns that are rotated or in perspective; right-to-left ordering of columns (the caller's);
         curved vertical columns (curved horizontal text: ``restore_page_curves``); a column on one page with a quadrilateral or a curved region
         (``restore_page_regions``); detection and recognition; several pages in one launch."""
-        from . import columns as cl, lq_device, pages
+        from . import columns as cl, pages
         who, n = "restore_page_columns", len(boxes)
         image, restored = self._page_front(who, image, n, texts, [char_boxes, vertical],
                                            "one text (one flag, and one list of character boxes, or None) per box", "boxes")
         H, W = int(image.shape[0]), int(image.shape[1])
         vertical = [True] * n if vertical is None else [bool(v) for v in vertical]
         boxes = [pages.round_box(b, H, W) for b in boxes]
-        cb = [None if char_boxes is None else char_boxes[i] for i in range(n)]
         try:
             ordered = pages.check_overlap(overlap)
             pages.region_rects(H, W, boxes, restored, scale, feather, overlap=overlap)
-            cuts = [cl.cell_cuts(boxes[i], len(texts[i]), cb[i], region=i) if vertical[i] and restored[i] else None for i in range(n)]
+            cuts = [cl.cell_cuts(boxes[i], len(texts[i]), None if char_boxes is None else char_boxes[i], region=i) if vertical[i] and restored[i] else None
+                    for i in range(n)]
             rects = cl.check_columns(H, W, boxes, restored, cuts, scale, feather, overlap=overlap)
         except ValueError as e:
             raise ValueError("%s: %s" % (who, e)) from None
-        widths = [None if c is None else cl.cell_widths(b, c) for b, c in zip(boxes, cuts)]
-        sizes = [(b[3] - b[1], b[2] - b[0]) if w is None else (cl.LQ_H, sum(w)) for b, w in zip(boxes, widths)]
-        local = [cl.virtual_boxes(widths[i]) if widths[i] is not None else self._boxes_in_crop(cb[i], b) for i, b in enumerate(boxes)]
-        plans, labels, locs_rows, live = self._plan_lines(sizes, texts, local, max_glyphs, overlap_glyphs, who, "region")
-        cols, lines_ = [i for i in live if cuts[i] is not None], [i for i in live if cuts[i] is None]
-        columns = [(boxes[i], cuts[i], widths[i], plans[i]) for i in cols]
-        flat, where, head = [], {}, 0                                   # the horizontal windows' crops, at the head of the packed batch
-        for i in lines_:
-            x1, y1, x2, y2 = boxes[i]
-            for k, p in enumerate(plans[i]):
-                where[(i, k)] = ((y2 - y1, p.c1 - p.c0), head)
-                flat.append(np.ascontiguousarray(image[y1:y2, x1 + p.c0:x1 + p.c1]).reshape(-1))
-                head += flat[-1].size
-        cell_tab, shapes, offsets, nbytes = cl.gather_table(columns, head)                        # its refusals, before anything is copied
-        for (i, k), h_w, off in zip([(i, k) for i in cols for k in range(len(plans[i]))], shapes, offsets):
-            where[(i, k)] = (h_w, off)
+        recs = [dict(kind="line", box=b, rect=r) if c is None else dict(kind="column", box=b, rect=r, cuts=c, widths=cl.cell_widths(b, c))
+                for b, r, c in zip(boxes, rects, cuts)]
 
-        def compose(out_ws):
-            page_d = torch.from_numpy(np.ascontiguousarray(image)).to(next(self.sr.parameters()).device)      # the one copy of the page
-            out = pages.enlarge(page_d, int(scale))
-            if live:
-                packed = torch.empty((nbytes,), dtype=torch.uint8, device=page_d.device)         # the ragged batch: the crops, then the columns' windows
-                if cols:
-                    with ops.on_device(page_d):
-                        ops.column_gather_u8(page_d, ops.table_to_device(cell_tab, page_d.device), int(cell_tab["dw"].max()), cl.LQ_H, packed)
-                if head:
-                    packed[:head].copy_(torch.from_numpy(np.concatenate(flat)))               # the horizontal crops, as restore_page uploads them
-                order = [where[(i, k)] for i in live for k in range(len(plans[i]))]
-                prep = lq_device.prepare_packed(packed, [o[0] for o in order], [o[1] for o in order])
-                joined = self._restore_planned(prep.lq, labels, locs_rows, plans, live)
-                line_of = {i: l for l, i in enumerate(live)}
-                if ordered:                                                                      # one table in region order, one launch by page tile
-                    col_of = dict(zip(cols, columns))
-                    return pages.paste_ordered(out, joined, cl.mixed_table(joined, [(line_of[i], rects[i], col_of.get(i, out_ws[i])) for i in live], int(feather)))
-                pages.paste_rects(out, joined, rects, [out_ws[i] if i in lines_ else None for i in range(n)], int(feather), [line_of[i] for i in lines_])
-                cl.paste_columns(out, joined, [line_of[i] for i in cols], columns, [rects[i] for i in cols], int(feather))
-            return out
-        return self._page_finish(plans, compose, details,
-                                 [dict(rect=r) if c is None else dict(rect=r, cuts=c, widths=w) for r, c, w in zip(rects, cuts, widths)])
+        def paste(out, joined, out_ws, live, plans):
+            line_of = {i: l for l, i in enumerate(live)}
+            cols, lines_ = [i for i in live if cuts[i] is not None], [i for i in live if cuts[i] is None]
+            columns = [(boxes[i], cuts[i], recs[i]["widths"], plans[i]) for i in cols]
+            if ordered:                                                                          # one table in region order, one launch by page tile
+                col_of = dict(zip(cols, columns))
+                return pages.paste_ordered(out, joined, cl.mixed_table(joined, [(line_of[i], rects[i], col_of.get(i, out_ws[i])) for i in live], int(feather)))
+            pages.paste_rects(out, joined, rects, [out_ws[i] if i in lines_ else None for i in range(n)], int(feather), [line_of[i] for i in lines_])
+            return cl.paste_columns(out, joined, [line_of[i] for i in cols], columns, [rects[i] for i in cols], int(feather))
+        return self._restore_page_records(who, image, recs, texts, char_boxes, scale, max_glyphs, overlap_glyphs, paste, details,
+                                          [dict(rect=r["rect"]) if "cuts" not in r else dict(rect=r["rect"], cuts=r["cuts"], widths=r["widths"]) for r in recs])
 
     @torch.no_grad()
     def restore_page_regions(self, image, regions, texts, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False,
@@ -750,15 +689,36 @@ class MarconetPipeline:
         None where it kept the background.
         Not covered: a blend of overlapping regions other than painter's order; vertical columns that are rotated or curved; detection and
         recognition (the caller's); several pages in one launch."""
-        from . import columns as cl, curves as cv, lq_device, pages, quads as qd, regions as rg
+        from . import regions as rg
         who, n = "restore_page_regions", len(regions)
         image, restored = self._page_front(who, image, n, texts, [char_boxes], "one text (and one list of character boxes, or None) per region", "regions")
-        H, W = int(image.shape[0]), int(image.shape[1])
-        cb = [None if char_boxes is None else char_boxes[i] for i in range(n)]
         try:
-            recs = rg.normalize_regions(H, W, regions, restored, texts, cb, scale, feather, overlap)
+            recs = rg.normalize_regions(int(image.shape[0]), int(image.shape[1]), regions, restored, texts,
+                                        [None if char_boxes is None else char_boxes[i] for i in range(n)], scale, feather, overlap)
         except ValueError as e:
             raise ValueError("%s: %s" % (who, e)) from None
+        extra = []
+        for r in recs:
+            if r["kind"] in ("line", "column"):
+                extra.append(dict(kind=r["kind"], rect=r["rect"], **({"cuts": r["cuts"], "widths": r["widths"]} if "widths" in r else {})))
+            elif r["kind"] == "quad":
+                extra.append(dict(kind="quad", quad=r["out_quad"], size=(r["rw"], r["rh"])))
+            else:
+                extra.append(dict(kind="curve", polygon=r["out_polygon"], size=(r["rw"], r["rh"])))
+        return self._restore_page_records(who, image, recs, texts, char_boxes, scale, max_glyphs, overlap_glyphs,
+                                          lambda out, joined, out_ws, live, plans: rg.paste_regions(out, joined, out_ws, recs, int(feather)), details, extra)
+
+    def _restore_page_records(self, who, image, recs, texts, char_boxes, scale, max_glyphs, overlap_glyphs, paste, details, extra):
+        """the one driver of the five ``restore_page*`` entry points, from their checked regions to the page on the host.  ``recs[i]``: region i's
+        record as ``regions.normalize_regions`` gives it — ``kind`` "line" or "column" with ``box`` (a column that is restored: ``cuts``, ``widths``),
+        "quad" (``quads.check_quads``' record) or "curve" (``curves.check_curves``') —; ``char_boxes`` in PAGE pixels.  Per kind the crop's size and
+        the character boxes in the crop (a kind's ValueError names ``who`` and the region), ``_plan_lines``, the packed layout — the host crops of
+        the lines at the head, then the columns', the quadrilaterals' and the curves' windows, each kind from its own base —, and in ``compose``:
+        one upload of the page, the background, at most one gather / crop launch per kind present, ``lq_device.prepare_packed``, the forward and
+        the join, then ``paste(out, joined, out_ws, live, plans)``, the caller's paste, and ``_page_finish`` with the caller's ``extra``."""
+        from . import columns as cl, curves as cv, lq_device, pages, quads as qd
+        n = len(recs)
+        cb = [None if char_boxes is None else char_boxes[i] for i in range(n)]
         sizes, local, maps = [], [None] * n, [None] * n
         for i, r in enumerate(recs):
             try:
@@ -778,10 +738,11 @@ class MarconetPipeline:
             except ValueError as e:
                 raise ValueError("%s: region %d: %s" % (who, i, e)) from None
         plans, labels, locs_rows, live = self._plan_lines(sizes, texts, local, max_glyphs, overlap_glyphs, who, "region")
-        of_kind = lambda *kinds: [i for i in live if recs[i]["kind"] in kinds]
-        lines_, cols, qds, cvs = of_kind("line"), of_kind("column"), of_kind("quad"), of_kind("curve")
+        of_kind = lambda kind: [i for i in live if recs[i]["kind"] == kind]
+        cols = of_kind("column")
+        q_wins, c_wins = [[(i, k, p) for i in of_kind(kind) for k, p in enumerate(plans[i])] for kind in ("quad", "curve")]
         flat, where, head = [], {}, 0                                   # the horizontal windows' crops, at the head of the packed batch
-        for i in lines_:
+        for i in of_kind("line"):
             x1, y1, x2, y2 = recs[i]["box"]
             for k, p in enumerate(plans[i]):
                 where[(i, k)] = ((y2 - y1, p.c1 - p.c0), head)
@@ -791,7 +752,6 @@ class MarconetPipeline:
         cell_tab, shapes, offsets, q_base = cl.gather_table(columns, head)                          # its refusals, before anything is copied
         for key, h_w, off in zip([(i, k) for i in cols for k in range(len(plans[i]))], shapes, offsets):
             where[key] = (h_w, off)
-        q_wins, c_wins = [(i, k, p) for i in qds for k, p in enumerate(plans[i])], [(i, k, p) for i in cvs for k, p in enumerate(plans[i])]
         q_sizes, c_sizes = [(p.c1 - p.c0, recs[i]["ch"]) for i, _, p in q_wins], [(p.c1 - p.c0, recs[i]["ch"]) for i, _, p in c_wins]
         q_tab, c_base = qd.crop_table([maps[i] for i, _, _ in q_wins], q_sizes, [p.c0 for _, _, p in q_wins], q_base)
         c_tab, _, nbytes = cv.crop_table([recs[i]["segs"] for i, _, _ in c_wins], c_sizes, [p.c0 for _, _, p in c_wins], c_base)
@@ -812,20 +772,11 @@ class MarconetPipeline:
                 if c_wins:
                     cv.crop_curves(page_d, [recs[i]["segs"] for i, _, _ in c_wins], c_sizes, [p.c0 for _, _, p in c_wins], c_base, packed)
                 if head:
-                    packed[:head].copy_(torch.from_numpy(np.concatenate(flat)))               # the horizontal crops, as restore_page uploads them
+                    packed[:head].copy_(torch.from_numpy(np.concatenate(flat)))               # the lines' crops: the one upload beside the page's
                 order = [where[(i, k)] for i in live for k in range(len(plans[i]))]
                 prep = lq_device.prepare_packed(packed, [o[0] for o in order], [o[1] for o in order])
-                joined = self._restore_planned(prep.lq, labels, locs_rows, plans, live)
-                rg.paste_regions(out, joined, out_ws, recs, int(feather))
+                paste(out, self._restore_planned(prep.lq, labels, locs_rows, plans, live), out_ws, live, plans)
             return out
-        extra = []
-        for r in recs:
-            if r["kind"] in ("line", "column"):
-                extra.append(dict(kind=r["kind"], rect=r["rect"], **({"cuts": r["cuts"], "widths": r["widths"]} if "widths" in r else {})))
-            elif r["kind"] == "quad":
-                extra.append(dict(kind="quad", quad=r["out_quad"], size=(r["rw"], r["rh"])))
-            else:
-                extra.append(dict(kind="curve", polygon=r["out_polygon"], size=(r["rw"], r["rh"])))
         return self._page_finish(plans, compose, details, extra)
 
     @torch.no_grad()

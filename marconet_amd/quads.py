@@ -21,7 +21,6 @@ recognition, several pages per launch.
 import math
 
 import numpy as np
-import torch
 
 from . import _lib, lq_io, ops, pages
 
@@ -274,10 +273,7 @@ def crop_quads(page_d, maps, sizes, c0s=None, base=0, dst=None):
     byte ``base``, the offsets of the crops): one copy of the table, one launch.  ``dst``: an existing flat buffer that holds the crops' bytes
     (the packed batch several sources share), written inside the crops only; None: a new one, the first ``base`` bytes left to the caller"""
     tab, nbytes = crop_table(maps, sizes, c0s, base)
-    if dst is None:
-        dst = torch.empty((nbytes,), dtype=torch.uint8, device=page_d.device)
-    elif dst.dtype != torch.uint8 or dst.dim() != 1 or dst.numel() < nbytes:
-        raise ValueError("crop_quads: a flat uint8 buffer of at least %d bytes expected" % nbytes)
+    dst = pages.crop_buffer("crop_quads", dst, nbytes, page_d.device)
     with ops.on_device(page_d):
         ops.quad_crop_u8(page_d, ops.table_to_device(tab, page_d.device), max(int(w) for w, _ in sizes), max(int(h) for _, h in sizes), dst)
     return dst, [int(o) for o in tab["offset"]]
@@ -290,17 +286,11 @@ def paste_quads(out, joined, out_ws, regions, feather, rows=ROW_H):
     live = [i for i, w in enumerate(out_ws) if w is not None]
     if not live:
         return out
-    rects, y = [None] * len(out_ws), 0
-    for i in live:
-        rects[i] = (0, y, regions[i]["rw"], regions[i]["rh"])
-        y += regions[i]["rh"]
-    atlas = torch.zeros((y, max(regions[i]["rw"] for i in live), 3), dtype=torch.uint8, device=out.device)
-    fg_d = ops.table_to_device(pages.build_table(rects, out_ws, 0, rows), out.device)
+    rects, atlas_hw = pages.atlas_layout([None if w is None else (r["rw"], r["rh"]) for w, r in zip(out_ws, regions)])
     quad_d = ops.table_to_device(paste_table([regions[i] for i in live], feather, [rects[i][:2] for i in live]), out.device)
+    atlas = pages.fill_atlas(joined, pages.build_table(rects, out_ws, 0, rows), atlas_hw)
     with ops.on_device(out):
-        ops.paste_u8(joined, fg_d, atlas)
-        ops.quad_paste_u8(atlas, quad_d, max(regions[i]["bbox"][2] for i in live), max(regions[i]["bbox"][3] for i in live), out)
-    return out
+        return ops.quad_paste_u8(atlas, quad_d, max(regions[i]["bbox"][2] for i in live), max(regions[i]["bbox"][3] for i in live), out)
 
 
 def compose_page_quads(page, joined, out_ws, quads, scale=4, feather=8, device=None):

@@ -136,10 +136,7 @@ def mixed_tables(recs, out_ws, feather, rows=ROW_H, line_index=None):
     live = [i for i, w in enumerate(out_ws) if w is not None]
     line_of = {i: (l if line_index is None else int(line_index[l])) for l, i in enumerate(live)}
     warped = [i for i in live if recs[i]["kind"] in ("quad", "curve")]
-    fg_rects, y = [None] * len(recs), 0
-    for i in warped:
-        fg_rects[i] = (0, y, recs[i]["rw"], recs[i]["rh"])
-        y += recs[i]["rh"]
+    fg_rects, atlas_hw = pages.atlas_layout([(r["rw"], r["rh"]) if i in warped else None for i, r in enumerate(recs)])
     qs, cs = [i for i in warped if recs[i]["kind"] == "quad"], [i for i in warped if recs[i]["kind"] == "curve"]
     quad_tab = quads.paste_table([recs[i] for i in qs], feather, [fg_rects[i][:2] for i in qs])
     curve_tab, seg_tab = curves.paste_table([recs[i] for i in cs], feather, [fg_rects[i][:2] for i in cs])
@@ -147,10 +144,7 @@ def mixed_tables(recs, out_ws, feather, rows=ROW_H, line_index=None):
     for i in live:
         r, kind = recs[i], recs[i]["kind"]
         if kind in ("line", "column"):
-            if kind == "line":
-                part = pages.as_cell(pages.build_table([r["rect"]], [int(out_ws[i])], feather, rows, [line_of[i]]))
-            else:
-                part = columns.paste_table([(r["box"], r["cuts"], r["widths"], None)], [line_of[i]], [r["rect"]], feather, rows)
+            part = columns.region_cells(line_of[i], r["rect"], out_ws[i] if kind == "line" else (r["box"], r["cuts"], r["widths"], None), feather, rows)
             for c in part:
                 rect = (int(c["x0"]), int(c["y0"]), int(c["rw"]), int(c["rh"]))
                 entries.append(rect)
@@ -178,7 +172,7 @@ def mixed_tables(recs, out_ws, feather, rows=ROW_H, line_index=None):
         fg = pages.build_table(fg_rects, [out_ws[i] if i in warped else None for i in range(len(recs))], 0, rows, [line_of[i] for i in warped])
     return dict(cells=np.concatenate(cell_parts) if cell_parts else np.zeros((0,), dtype=np.dtype(_lib.ColumnPaste)), quads=quad_tab, curves=curve_tab,
                 segs=seg_tab, items=item_tab, entries=entry_tab, entry_item=np.asarray(entry_item, dtype=np.int32), fg=fg,
-                atlas_hw=(y, max([recs[i]["rw"] for i in warped], default=0)))
+                atlas_hw=atlas_hw)
 
 
 def bin_items(entries, entry_item, page_h, page_w):
@@ -212,10 +206,7 @@ def paste_tables(out, joined, tabs):
     dev = out.device
     up = lambda t: ops.table_to_device(t, dev) if len(t) else None
     with ops.on_device(out):
-        atlas = None
-        if tabs["fg"] is not None:
-            atlas = torch.zeros(tuple(tabs["atlas_hw"]) + (3,), dtype=torch.uint8, device=dev)
-            ops.paste_u8(joined, ops.table_to_device(tabs["fg"], dev), atlas)
+        atlas = None if tabs["fg"] is None else pages.fill_atlas(joined, tabs["fg"], tabs["atlas_hw"])
         ops.paste_mixed_u8(joined if len(tabs["cells"]) else None, atlas, up(tabs["cells"]), up(tabs["quads"]), up(tabs["curves"]), up(tabs["segs"]),
                            ops.table_to_device(tabs["items"], dev), ops.table_to_device(spans, dev), torch.from_numpy(order).to(dev), out)
     return out

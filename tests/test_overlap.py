@@ -354,14 +354,17 @@ def test_ops_refuses_cpu_tensors_and_bad_tables():
 def test_build_script_stamps_the_header_and_the_kernel_shares_the_paste_body():
     sh = open(os.path.join(CSRC, "build.sh")).read()
     assert ('[ "$1" = page_kernels ] && cat "$HERE/lq_taps.h" "$HERE/page_blend.h" "$HERE/page_tile.h" "$HERE/../../include/marconet_hip_columns.h" '
-            '"$HERE/../../include/marconet_hip_ordered.h"') in sh
-    src = open(os.path.join(CSRC, "page_kernels.hip")).read()
-    assert "marconet_hip_ordered.h" in src and "mnet_paste_ordered_u8" in src
-    # one box average, one cubic gather, one blend: stated once, called by paste_cell (the two per-descriptor kernels) and by the ordered kernel
-    assert src.count("page_box_avg(") == 1 and src.count("page_feather(") == 1 and src.count("pt_round_clip(") == 1
-    assert src.count("cell_foreground(") == 3 and src.count("cell_blend(") == 3 and src.count("cell_followed(") == 3
-    assert src.count("__shared__ PtTaps s;") == 3 and "__shared__" not in src.replace("__shared__ PtTaps s;", "")     # the kernel's LDS is one PtTaps
-    assert "asm" not in src
+            '"$HERE/cell_paste.h"') in sh
+    src, body = open(os.path.join(CSRC, "page_kernels.hip")).read(), open(os.path.join(CSRC, "cell_paste.h")).read()
+    # the ordered compositor is an instantiation of the page-tile compositor, in mixed_kernels.hip (tests/test_regions.py)
+    assert '#include "cell_paste.h"' in src and "marconet_hip_ordered.h" not in src and "mnet_paste_ordered_u8" not in src
+    # one box average, one cubic gather, one blend: stated once, in cell_paste.h, called by paste_cell (the two per-descriptor kernels) and by the compositor
+    assert body.count("page_box_avg(") == 1 and body.count("page_feather(") == 1 and body.count("pt_round_clip(") == 1
+    assert "page_box_avg(" not in src and "page_feather(" not in src and "pt_round_clip(" not in src
+    assert src.count("cell_foreground(") == 1 and src.count("cell_blend(") == 1 and src.count("cell_followed(") == 1
+    assert body.count("cell_foreground(") == 1 and body.count("cell_blend(") == 1 and body.count("cell_followed(") == 1       # their definitions
+    assert src.count("__shared__ PtTaps s;") == 2 and "__shared__" not in src.replace("__shared__ PtTaps s;", "")     # the kernels' LDS is one PtTaps
+    assert "__shared__" not in body and "asm" not in src and "asm" not in body
 
 
 # -------------------------------------------------------------------------------------------------------------------- the example

@@ -370,19 +370,24 @@ def test_build_script_compiles_and_stamps_the_kernel_and_the_bodies_are_stated_o
     sh = open(os.path.join(CSRC, "build.sh")).read()
     assert re.search(r'^SRCS="[^"]*\bmixed_kernels\b[^"]*"', sh, flags=re.M) and 'mixed_kernels) echo "-ffp-contract=off" ;;' in sh
     stamp = re.search(r'\[ "\$1" = mixed_kernels \] && cat ([^;]*);', sh).group(1)
-    for name in ("page_kernels.hip", "warp_paste.h", "curve_map.h", "quad_map.h", "lq_taps.h", "page_blend.h", "page_tile.h", "marconet_hip_columns.h",
+    for name in ("cell_paste.h", "warp_paste.h", "curve_map.h", "quad_map.h", "lq_taps.h", "page_blend.h", "page_tile.h", "marconet_hip_columns.h",
                  "marconet_hip_ordered.h", "marconet_hip_quad.h", "marconet_hip_curve.h", "marconet_hip_mixed.h"):
         assert name in stamp, name
+    assert "page_kernels.hip" not in stamp
     for unit in ("quad_kernels", "curve_kernels"):
         assert "warp_paste.h" in re.search(r'\[ "\$1" = %s \] && cat ([^;]*);' % unit, sh).group(1)
     src = {n: open(os.path.join(CSRC, n)).read() for n in ("mixed_kernels.hip", "quad_kernels.hip", "curve_kernels.hip", "page_kernels.hip", "warp_paste.h")}
     mixed = src["mixed_kernels.hip"]
-    assert "#define MNET_PAGE_CELL_ONLY" in mixed and '#include "page_kernels.hip"' in mixed and '#include "warp_paste.h"' in mixed and "mnet_paste_mixed_u8" in mixed
-    # the per-pixel arithmetic is stated once: in page_kernels.hip's head for a cell, in warp_paste.h for a quadrilateral and a curve
+    assert '#include "cell_paste.h"' in mixed and '#include "warp_paste.h"' in mixed and ".hip\"" not in mixed
+    assert not any("MNET_PAGE_CELL_ONLY" in open(os.path.join(CSRC, n)).read() for n in os.listdir(CSRC) if os.path.isfile(os.path.join(CSRC, n)))
+    # ONE page-tile compositor, which both entry points launch
+    assert mixed.count("__global__") == 1 and "mnet_paste_ordered_u8" in mixed and "mnet_paste_mixed_u8" in mixed
+    # the per-pixel arithmetic is stated once: in cell_paste.h for a cell, in warp_paste.h for a quadrilateral and a curve
     for body in ("quad_pos(", "curve_inv(", "quad_mix(", "page_feather("):
         assert body not in mixed and src["warp_paste.h"].count(body) == 1, body
     assert "quad_pos(R.n" not in src["quad_kernels.hip"] and "curve_inv(" not in src["curve_kernels.hip"] and "page_feather(" not in src["quad_kernels.hip"] + src["curve_kernels.hip"]
     assert src["quad_kernels.hip"].count("quad_paste_pixel(") == 1 and src["curve_kernels.hip"].count("curve_paste_pixel(") == 1
     assert mixed.count("quad_paste_pixel(") == 1 and mixed.count("curve_paste_pixel(") == 1 and mixed.count("cell_foreground(") == 1 and mixed.count("cell_blend(") == 1
+    assert mixed.count("cell_followed(") == 1
     assert "page_box_avg(" not in mixed and "pt_round_clip(" not in mixed and "asm" not in mixed and "asm" not in src["warp_paste.h"]
     assert mixed.count("__shared__") == 2 and "__shared__ PtTaps s;" in mixed and "__shared__ CurveSegL S[CURVE_MAX_SEGS];" in mixed
