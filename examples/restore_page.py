@@ -5,7 +5,9 @@
 
 ``regions.json`` is a list of ``{"box": [x1, y1, x2, y2], "text": "...", "char_boxes": [[x1, y1, x2, y2], ...]}``: a text line's box in page pixels
 (axis-aligned; numbers that are not integers are rounded outward), its characters, and — optionally — its character boxes in page pixels (evenly
-spaced ones otherwise).  The detector and the recogniser that produce them are the caller's (SURVEY.md §8f NEXT-4).  A region with no character or
+spaced ones otherwise).  The detector that produces the boxes is the caller's (SURVEY.md §8f NEXT-4); so is the recogniser, but a region WITHOUT
+``"text"`` is read by the encoder itself (marconet_amd/blind.py: overlapping probe windows give its text and character boxes; not a ``"vertical"``
+region, whose cells are cut from its text).  A region with no character or
 with a character outside the alphabet keeps the enlarged page's own pixels, as the script skips such a strip (test_sr.py:168-170, :181-190).
 A region may carry ``"quad": [[x, y], [x, y], [x, y], [x, y]]`` instead of ``"box"``: the four corners of a rotated or perspective line in its own
 reading order (top-left, top-right, bottom-right, bottom-left as the line is read).  If any region does, all regions go through
@@ -46,9 +48,11 @@ def load_regions(path):
     with open(path, encoding="utf8") as f:
         regions = json.load(f)
     def well_formed(r):
-        if not isinstance(r, dict) or "text" not in r or ("box" in r) + ("quad" in r) + ("polygon" in r) != 1:
+        if not isinstance(r, dict) or not isinstance(r.get("text", ""), str) or ("box" in r) + ("quad" in r) + ("polygon" in r) != 1:
             return False
         if not isinstance(r.get("vertical", False), bool) or ("vertical" in r and "box" not in r):
+            return False
+        if r.get("vertical", False) and "text" not in r:                      # a column's cells are cut from its text: it cannot be read blind
             return False
         if "box" in r:
             return isinstance(r["box"], list) and len(r["box"]) == 4 and all(isinstance(v, (int, float)) for v in r["box"])
@@ -59,7 +63,8 @@ def load_regions(path):
     if not isinstance(regions, list) or not all(well_formed(r) for r in regions):
         raise SystemExit('restore_page.py: %s must hold a list of {"box": [x1, y1, x2, y2], "text": "..."} or {"quad": [[x, y], [x, y], [x, y], [x, y]], '
                          '"text": "..."} or {"polygon": [[x, y], ...], "text": "..."} objects (numbers; one of "box", "quad" and "polygon" per region; '
-                         '"vertical": true or false beside a "box" only)' % path)
+                         '"vertical": true or false beside a "box" only; "text" may be left out — the region is then read by the encoder — except for a '
+                         '"vertical" region)' % path)
     vertical = [bool(r.get("vertical", False)) for r in regions] if any(r.get("vertical", False) for r in regions) else None
     if vertical is not None and any("quad" in r for r in regions):
         raise SystemExit('restore_page.py: %s holds a "vertical" region (%d) and a "quad" region (%d): vertical columns go through restore_page_columns, '
@@ -77,7 +82,7 @@ def load_regions(path):
     polygons = None
     if any("polygon" in r for r in regions):
         polygons = [r["polygon"] if "polygon" in r else q for r, q in zip(regions, quads)]
-    return ([r.get("box") for r in regions], [r["text"] for r in regions], char_boxes if any(c is not None for c in char_boxes) else None, quads, vertical,
+    return ([r.get("box") for r in regions], [r.get("text") for r in regions], char_boxes if any(c is not None for c in char_boxes) else None, quads, vertical,
             polygons)
 
 
@@ -113,6 +118,8 @@ def main():
         page, regions = pipe.restore_page(lq_io.load_png(a.image), boxes, texts, char_boxes=char_boxes, scale=a.scale, feather=a.feather, details=True,
                                           overlap=a.overlap)
     for i, (r, text) in enumerate(zip(regions, texts)):
+        if text is None and r is not None:
+            text = "%s (read%s)" % (r["text"], ", a probe window held more than 16 characters" if r["overflow"] else "")
         if r is None:
             print("Region %d keeps the page's pixels (no character, or a character outside the alphabet): %r" % (i, text))
         elif "cuts" in r:

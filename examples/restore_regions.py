@@ -6,10 +6,11 @@
 ``regions.json`` is the file examples/restore_page.py reads: a list of objects with ``"text"`` and exactly one of ``"box": [x1, y1, x2, y2]`` (a text
 line; with ``"vertical": true`` a column of upright characters), ``"quad": [[x, y] x 4]`` (a rotated or perspective line, corners in reading order)
 and ``"polygon": [[x, y], ...]`` (the 2K points of a curved line), optionally with ``"char_boxes"`` in page pixels.  Any mix is accepted and the page
-is restored in ONE call: a line, a column, a slanted stamp and a seal over the line.
+is restored in ONE call: a line, a column, a slanted stamp and a seal over the line.  A region WITHOUT ``"text"`` is read by the encoder itself
+(marconet_amd/blind.py; not a ``"vertical"`` region, whose cells are cut from its text — that is refused by name).
 Two regions whose interiors intersect, of whatever kinds, are refused by default; ``--overlap order`` pastes them in the file's order (painter's
 order: a later region is blended, under its own feather ramp, over the earlier ones).
-Not covered: a blend other than painter's order, vertical columns that are rotated or curved, detection and recognition, several pages per call.
+Not covered: a blend other than painter's order, vertical columns that are rotated or curved, detection, several pages per call.
 
 Weights: ``$MARCONET_CKPT_DIR`` as in examples/restore_strips.py; without them the seeded synthetic weights run and the page shows the plumbing, not a
 restoration.  Needs the GPU (there is no CPU path in this package)."""
@@ -30,15 +31,16 @@ def load_regions(path):
     """→ (the region dicts, their texts, their character boxes or None)"""
     with open(path, encoding="utf8") as f:
         regions = json.load(f)
-    if not isinstance(regions, list) or not all(isinstance(r, dict) and isinstance(r.get("text"), str) for r in regions):
-        raise SystemExit('restore_regions.py: %s must hold a list of objects with "text" and one of "box", "quad" and "polygon"' % path)
+    if not isinstance(regions, list) or not all(isinstance(r, dict) and isinstance(r.get("text", ""), str) for r in regions):
+        raise SystemExit('restore_regions.py: %s must hold a list of objects with one of "box", "quad" and "polygon" and a "text" (a region without '
+                         '"text" is read by the encoder)' % path)
     try:
         for i, r in enumerate(regions):
             rg.region_kind(r, i)
     except ValueError as e:
         raise SystemExit("restore_regions.py: %s: %s" % (path, e))
     char_boxes = [r.get("char_boxes") for r in regions]
-    return regions, [r["text"] for r in regions], char_boxes if any(c is not None for c in char_boxes) else None
+    return regions, [r.get("text") for r in regions], char_boxes if any(c is not None for c in char_boxes) else None
 
 
 def main():
@@ -62,6 +64,8 @@ def main():
     page, info = pipe.restore_page_regions(lq_io.load_png(a.image), regions, texts, char_boxes=char_boxes, scale=a.scale, feather=a.feather, details=True,
                                            overlap=a.overlap)
     for i, (r, text) in enumerate(zip(info, texts)):
+        if text is None and r is not None:
+            text = "%s (read%s)" % (r["text"], ", a probe window held more than 16 characters" if r["overflow"] else "")
         if r is None:
             print("Region %d keeps the page's pixels (no character, or a character outside the alphabet): %r" % (i, text))
         else:

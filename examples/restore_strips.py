@@ -3,7 +3,7 @@
 (preview | box marks | super-resolved strip | structure priors — the file test_sr.py:232 writes, under the same name).
 
     python examples/restore_strips.py -i <strips dir> -o <out dir> [-m] [--precision fp16x2] [--batch 64] [--device-prep | --device-panel]
-                                      [--calibrate [--calibrate-apply]] [--long-lines]
+                                      [--calibrate [--calibrate-apply]] [--long-lines [--blind]]
 
 Same flags as the script (-i / -o / -m, test_sr.py:236-241).  What differs, and why:
   * the YOLO character detector and the modelscope OCR (test_sr.py:55-56,86-96) are not part of this build (SURVEY.md §8f NEXT-4).  With
@@ -20,10 +20,11 @@ Same flags as the script (-i / -o / -m, test_sr.py:236-241).  What differs, and 
     mode and in the fp16x3 reference mode (fp32 for ``--precision fp16x3``) on the device and the report of ``MarconetPipeline.calibrate`` is printed — is the
     mode inside half the 1e-3 parity bar on THESE weights, and at which stage does the deviation enter.  A failed check ends the program with status 2;
     with ``--calibrate-apply`` the pipeline falls back to the reference mode instead and goes on.
-  * ``--long-lines`` (opt-in, needs ``-m``): a strip the script skips for its width (more than 512 px at height 32, test_sr.py:108-110) is cut into
+  * ``--long-lines`` (opt-in, needs ``-m`` or ``--blind``): a strip the script skips for its width (more than 512 px at height 32, test_sr.py:108-110) is cut into
     overlapping windows of whole characters, all windows are restored in one batch and joined on the GPU (MarconetPipeline.restore_lines); it is saved
     under the script's file name as the super-resolved line ALONE (the four-row panel is bounded by the 2048-px SR canvas).  Everything else is
-    saved as before.
+    saved as before.  With ``--blind`` in the place of ``-m`` the encoder reads the wide strips too: overlapping probe windows, each keeping the
+    characters well inside it (marconet_amd/blind.py), give the text and the character boxes the windows are cut by.
 Needs the GPU (there is no CPU path in this package)."""
 import argparse
 import os
@@ -113,8 +114,9 @@ def device_panels(pipe, paths, names, manual, save_path, max_glyphs=16):
             print("Restoring %s. Using %s text: %s -> %s" % (name, "given" if manual else "predicted", s["text"], out))
 
 
-def long_lines(pipe, paths, names, save_path):
-    """--long-lines: the strips of the chunk that are too wide go through restore_lines and are saved; → the positions of the others"""
+def long_lines(pipe, paths, names, save_path, blind=False):
+    """--long-lines: the strips of the chunk that are too wide go through restore_lines and are saved; → the positions of the others.
+    ``blind``: their texts are read by the encoder (restore_lines with None per line) and not taken from the file names"""
     from PIL import Image
     from marconet_amd.long_lines import too_wide
     wide = []
@@ -123,15 +125,23 @@ def long_lines(pipe, paths, names, save_path):
             if too_wide(im.size[1], im.size[0]):
                 wide.append(i)
     if wide:
-        texts = [lq_io.manual_text(paths[i]) for i in wide]
-        lines = pipe.restore_lines([lq_io.load_png(paths[i]) for i in wide], texts)
+        images = [lq_io.load_png(paths[i]) for i in wide]
+        if blind:
+            lines, _, read = pipe.restore_lines(images, [None] * len(images), details=True)
+            texts = ["" if r is None else r["text"] for r in read]
+            for i, r in zip(wide, read):
+                if r is not None and r["overflow"]:
+                    print("Warning: %s: a probe window held more than 16 characters; those beyond the sixteenth were not read" % names[i])
+        else:
+            texts = [lq_io.manual_text(paths[i]) for i in wide]
+            lines = pipe.restore_lines(images, texts)
         for i, text, line in zip(wide, texts, lines):
             if line is None:                                                     # test_sr.py:168-170, :181-190
                 print("Error in %s (no character, or a character outside the alphabet). Continue..." % names[i])
                 continue
             out = os.path.join(save_path, "%s_%s.png" % (os.path.splitext(names[i])[0], text))       # test_sr.py:232
             Image.fromarray(np.ascontiguousarray(line[:, :, ::-1])).save(out)    # BGR → RGB
-            print("Restoring %s as a long line of %d px. Using given text: %s -> %s" % (names[i], line.shape[1], text, out))
+            print("Restoring %s as a long line of %d px. Using %s text: %s -> %s" % (names[i], line.shape[1], "predicted" if blind else "given", text, out))
     return [i for i in range(len(paths)) if i not in wide]
 
 
@@ -159,10 +169,13 @@ def main():
     ap.add_argument("--device-panel", action="store_true", help="also compose the saved panel on the GPU (MarconetPipeline.restore_panels); implies --device-prep")
     ap.add_argument("--calibrate", action="store_true", help="check the precision mode against a more accurate one on the first batch (MarconetPipeline.calibrate) and exit with status 2 if it fails")
     ap.add_argument("--calibrate-apply", action="store_true", help="with --calibrate: fall back to the reference mode instead of exiting")
-    ap.add_argument("--long-lines", action="store_true", help="with -m: restore strips wider than 512 px at height 32 window by window and join them (MarconetPipeline.restore_lines)")
+    ap.add_argument("--long-lines", action="store_true", help="with -m or --blind: restore strips wider than 512 px at height 32 window by window and join them (MarconetPipeline.restore_lines)")
+    ap.add_argument("--blind", action="store_true", help="with --long-lines: the encoder reads the wide strips' text and character boxes itself (restore_lines with None as their texts)")
     a = ap.parse_args()
-    if a.long_lines and not a.manual:
-        ap.error("--long-lines needs -m: a window is a run of whole characters, and windows cut without the text would cut characters in half")
+    if a.blind and not a.long_lines:
+        ap.error("--blind applies to --long-lines (a strip of at most 512 px at height 32 is read blind without -m anyway)")
+    if a.long_lines and not (a.manual or a.blind):
+        ap.error("--long-lines needs -m or --blind: a window is a run of whole characters, so the text is given (-m) or read by the encoder (--blind)")
     save_path = a.save_path or a.test_path.rstrip("/") + "_" + time.strftime("%m-%d_%H-%M", time.localtime()) + "_MARCONet"
     os.makedirs(save_path, exist_ok=True)
     if not torch.cuda.is_available():
@@ -176,7 +189,7 @@ def main():
         chunk = names[s0:s0 + a.batch]
         paths = [os.path.join(a.test_path, f) for f in chunk]
         if a.long_lines:
-            rest = long_lines(pipe, paths, chunk, save_path)
+            rest = long_lines(pipe, paths, chunk, save_path, blind=a.blind and not a.manual)
             chunk, paths = [chunk[i] for i in rest], [paths[i] for i in rest]
             if not chunk:
                 continue

@@ -127,3 +127,69 @@ def prepare_packed(src_device, shapes, offsets, preview=False):
         if int(off) < 0 or int(off) + 3 * int(h) * int(w) > src_device.numel():
             raise ValueError("prepare_packed: image %d (%d x %d at byte %d) lies outside the %d bytes given" % (k, int(w), int(h), int(off), src_device.numel()))
     return _resize_packed(src_device, geoms, [int(o) for o in offsets], list(range(len(geoms))), [], preview)
+
+
+def check_windows(windows, nbytes, who="prepare_windows"):
+    """the host half of ``prepare_windows``, which needs no device: ``windows[k]`` = (offset, pitch, h, w) inside a buffer of ``nbytes`` bytes → their
+    ``Geometry``s; per window, in order, the errors of its size (``shape_geometry``), then ValueError for a negative offset, a pitch under 3·w or a
+    last row that ends outside the buffer"""
+    geoms = []
+    for k, (off, pitch, h, w) in enumerate(windows):
+        g = shape_geometry(h, w, False)
+        off, pitch = int(off), int(pitch)
+        if off < 0 or pitch < 3 * g.w or pitch > 0x7fffffff or off + (g.h - 1) * pitch + 3 * g.w > int(nbytes):
+            raise ValueError("%s: window %d (%d x %d at byte %d, pitch %d) lies outside the %d bytes given, or its rows overlap"
+                             % (who, k, g.w, g.h, off, pitch, int(nbytes)))
+        geoms.append(g)
+    return geoms
+
+
+def window_table(geoms, windows):
+    """→ numpy record array of ``mnet_lq_window`` [n]"""
+    tab = np.zeros((len(geoms),), dtype=np.dtype(_lib.LqWindow))
+    for k, (g, win) in enumerate(zip(geoms, windows)):
+        tab[k] = (int(win[0]), int(win[1]), g.h, g.w, g.dw, g.scale)
+    return tab
+
+
+def upload_lines(images, device):
+    """images: uint8 RGB HxWx3 arrays → (uint8 [bytes] on ``device``, the images packed tightly one behind the other — each an image of its own
+    pitch 3·w —, the byte at which each begins): the one copy of the pixels that every window of every line is then a view of.  ``strip_geometry``'s
+    errors for an array that is no uint8 HxWx3 image; the sizes themselves are the windows' business."""
+    flat, offsets, off = [], [], 0
+    for img in images:
+        shape = np.shape(img)
+        if len(shape) != 3:
+            raise ValueError("uint8 RGB HxWx3 array expected, got shape %s" % (tuple(shape),))
+        if np.asarray(img).dtype != np.uint8:
+            raise TypeError("resize_cubic: uint8 HxWxC image expected")
+        if int(shape[2]) != 3:
+            raise ValueError("uint8 RGB HxWx3 array expected, got %d channels" % int(shape[2]))
+        offsets.append(off)
+        flat.append(np.ascontiguousarray(img).reshape(-1))
+        off += flat[-1].size
+    src = torch.from_numpy(np.concatenate(flat) if flat else np.zeros((0,), dtype=np.uint8)).to(torch.device(device))
+    return src, offsets
+
+
+def line_window(offset, h, w, c0, c1):
+    """the columns [c0, c1) of a tightly packed h x w image that begins at byte ``offset``, as a window of ``prepare_windows``"""
+    return (int(offset) + 3 * int(c0), 3 * int(w), int(h), int(c1) - int(c0))
+
+
+def prepare_windows(src_device, windows):
+    """``prepare_strips`` for windows that are VIEWS of images on the device: ``src_device`` uint8 [bytes]; ``windows[k]`` = (offset, pitch, h, w) — the
+    byte of the window's first pixel, the bytes per row of the image it lies in, its size → ``Prepared`` of all windows (no preview), the bits
+    ``prepare_strips`` gives for the same pixels copied out tightly: BORDER_REPLICATE clamps into the window, not into the image around it.  No pixel
+    is copied, overlapping windows share theirs; one copy of the table, ONE launch (``mnet_lq_windows_u8``).  ``check_windows``' errors, all before
+    anything is launched."""
+    if not torch.is_tensor(src_device) or src_device.dtype != torch.uint8 or src_device.dim() != 1:
+        raise TypeError("prepare_windows: uint8 [bytes] device tensor expected")
+    windows = list(windows)
+    if not windows:
+        raise ValueError("prepare_windows: at least one window expected")
+    geoms = check_windows(windows, src_device.numel())
+    table = ops.table_to_device(window_table(geoms, windows), src_device.device)               # the one copy of the table
+    with ops.on_device(src_device):
+        lq = ops.lq_windows_u8(src_device, table, LQ_H, LQ_W)
+    return Prepared(lq, [g.dw for g in geoms], [g.show_w for g in geoms], list(range(len(geoms))), None, [])

@@ -18,7 +18,7 @@ from .packing import MX_DTYPE, SPLIT_DTYPE, is_split, mx_weight_rows, new_tensor
 
 __all__ = ["conv2d", "linear", "nchw_to_nhwc", "nhwc_to_nchw", "upsample2x", "affine_act", "groupnorm_affine",
            "adain_crop_concat", "adain_crop_concat_gn", "glyph_scatter_affine", "layernorm", "token_mix", "attention", "pixelnorm",
-           "embed_gather", "demod", "argmax_rows", "convert", "fused_bias_act", "sr_postprocess", "lq_from_u8", "panel_u8", "paste_u8", "quad_crop_u8", "quad_paste_u8", "curve_crop_u8", "curve_paste_u8", "paste_ordered_u8", "conv3x3_rgb", "torgb", "stats",
+           "embed_gather", "demod", "argmax_rows", "convert", "fused_bias_act", "sr_postprocess", "lq_from_u8", "lq_windows_u8", "panel_u8", "paste_u8", "quad_crop_u8", "quad_paste_u8", "curve_crop_u8", "curve_paste_u8", "paste_ordered_u8", "conv3x3_rgb", "torgb", "stats",
            "pack_weights", "pack_wsq", "gather_rows", "style_rows", "nonfinite_flag", "compare_stats", "gn_partial_buffer", "can_emit_gn_partial", "groupnorm_affine_from_partial",
            "polyphase_plan", "upconv3x3_polyphase", "polyphase_ring_fix", "groupnorm_affine_from_partial_ring", "upfold_plan", "upfold3x3",
            "ACT_NONE", "ACT_RELU", "ACT_LRELU", "ACT_LRELU_SQRT2", "ACT_TANH", "ACT_GELU", "ACT_SIGMOID"]
@@ -716,6 +716,23 @@ def lq_from_u8(src, table, dst_h, canvas_w, preview=False, out=None):
     out = _out("lq_from_u8", out, (n, dst_h, canvas_w, 3) if preview else (n, 3, dst_h, canvas_w), torch.uint8 if preview else torch.float32, src.device)
     _lib.check(lib.mnet_lq_from_u8(_p(src), _p(table), n, dst_h, canvas_w, _p(out), _lib.LQ_FORM_U8_HWC if preview else _lib.LQ_FORM_F32_NCHW,
                                    _stream()), "mnet_lq_from_u8")
+    return out
+
+
+def lq_windows_u8(src, table, dst_h=32, canvas_w=512, out=None):
+    """mnet_lq_windows_u8 (``lq_from_u8``'s fp32 form for windows that are VIEWS of images on the device): ``src`` uint8 [bytes]; ``table`` uint8
+    [n, sizeof(mnet_lq_window)], the windows' descriptors (``_lib.LqWindow``: first byte, row pitch, size), both on the device.
+    → fp32 [n,3,dst_h,canvas_w], the bits ``lq_from_u8`` gives for each window's pixels copied out tightly (−1 beyond a window's width).
+    The kernel writes the whole of ``out``; a descriptor that does not lie inside ``src`` is written as fill (``lq_device.prepare_windows`` refuses it)."""
+    lib = _lib.load()
+    _need_cuda(src, table, out)
+    if src.dtype != torch.uint8 or src.dim() != 1 or not src.is_contiguous():
+        raise TypeError("lq_windows_u8: uint8 [bytes] pixels expected")
+    _check_table("lq_windows_u8", "window table", table, _lib.LqWindow, 8)
+    n = int(table.shape[0])
+    out = _out("lq_windows_u8", out, (n, 3, dst_h, canvas_w), torch.float32, src.device)
+    _lib.check(lib.mnet_lq_windows_u8(_p(src), src.numel(), _p(table), n, dst_h, canvas_w, _p(out), _lib.LQ_FORM_F32_NCHW, _stream()),
+               "mnet_lq_windows_u8")
     return out
 
 

@@ -398,7 +398,7 @@ class MarconetPipeline:
         return (out, strips) if details else out
 
     @torch.no_grad()
-    def restore_lines(self, images, texts, boxes=None, max_glyphs=16, overlap_glyphs=2, details=False):
+    def restore_lines(self, images, texts, boxes=None, max_glyphs=16, overlap_glyphs=2, details=False, probe_width=384):
         """Whole text lines, however wide: what the script tells its user to do by hand for a strip wider than 512 px at height 32 ("crop it into
         shorter segments", test_sr.py:108-110) and the joining it leaves to them.  ``images``: uint8 RGB HxWx3 arrays; ``texts[i]``: the line's
         characters; ``boxes[i]``: its character boxes in source pixels, or evenly spaced ones.  Per line ``long_lines.plan_windows`` cuts windows of
@@ -408,46 +408,137 @@ class MarconetPipeline:
         line on the device (``long_lines.compose_lines``: the bytes of ``long_lines.stitch_host``) and ONE device→host copy brings them back.
         → per image a uint8 BGR array [128, out_w, 3] (a line that fits one window: ``restore_images``' own bytes); ``None`` for a line with no
         character or with a character outside the alphabet — ``restore_strips``' decisions, applied to the line as a whole.
-        ``texts`` is required: windows cut without character boxes would cut characters in half.  ``details=True`` → ``(lines, plans)``."""
-        joined, plans, live = self._joined_lines(images, texts, boxes, max_glyphs, overlap_glyphs, "restore_lines", "image")
+        ``None`` as a line's entry of ``texts`` means "read it" (``blind``'s head states the reading; ``read_lines`` returns it) — ``[None] *
+        len(images)`` reads every line.  ``texts`` itself stays required: ``texts=None`` is refused as it always was here (a caller who forgot
+        the texts is told so; the page entry points, where the boxes are the caller's statement, take ``texts=None`` as a None per region).  The
+        lines are uploaded once, packed one behind the other, and every probe window of every line that is read goes through the encoder as ONE
+        batch of views of them (``lq_device.prepare_windows``).  A line of one probe takes its labels (at most ``max_glyphs``) and ``preds_locs``
+        straight from the encoder, as ``restore_images(texts=None)`` does — a call that holds only such lines gives its bytes —; a line of several
+        probes is read, and its text and boxes are planned as given ones are (``plan_windows``' ValueErrors name the line).  The planned windows
+        are then views of the uploaded lines too.  An empty reading gives ``None``.  With every text given nothing changes.
+        ``details=True`` → ``(lines, plans)``; where a text was ``None``, ``(lines, plans, readings)``: per line that was read a dict with ``text``,
+        ``boxes`` (source pixels) and ``overflow`` (a probe held more than the encoder's 16 characters), None for the others."""
+        if texts is None:
+            raise ValueError("restore_lines needs texts: a window is a run of whole characters, and windows cut blind would cut characters in half "
+                             "(restore_images(texts=None) reads a strip of at most 512 px at height 32 without them) — None as a line's ENTRY of "
+                             "texts has the encoder read that line: [None] * len(images) reads them all")
+        joined, plans, live, read = self._joined_lines(images, texts, boxes, max_glyphs, overlap_glyphs, "restore_lines", "image", probe_width)
         out = [None] * len(images)
         if live:
             from . import long_lines
             joined = joined.cpu().numpy()                                                         # the one device→host copy
             for l, i in enumerate(live):
                 out[i] = joined[l, :, :long_lines.plan_out_w(plans[i]), :]
+        if details and read is not None:
+            return out, plans, [self._reading_details(read.get(i)) for i in range(len(images))]
         return (out, plans) if details else out
 
-    def _joined_lines(self, images, texts, boxes, max_glyphs, overlap_glyphs, who, what):
+    @torch.no_grad()
+    def read_lines(self, images, probe_width=384):
+        """What the encoder reads in whole text lines, however wide: per image dict(text, labels, boxes [[x1, 0, x2, h]] in source pixels, probes,
+        overflow), None for an empty reading — ``blind.read_host``'s result, ``==`` (``blind``'s head states the rules).  ONE upload of the lines
+        packed one behind the other, ONE ``mnet_lq_windows_u8`` launch over all probes of all lines (views: overlapping probes share their
+        pixels), ONE encoder forward and ONE device→host copy of the indices and the locations; the merge, a few hundred short rows, runs on
+        the host."""
+        from . import blind, lq_device
+        sizes = [tuple(int(v) for v in np.shape(img)[:2]) for img in images]
+        src, offsets = lq_device.upload_lines(images, next(self.sr.parameters()).device)
+        probes = blind.line_probes(sizes, probe_width)
+        if not images:
+            return []
+        wins = [lq_device.line_window(offsets[i], h, w, p[0], p[1]) for i, (h, w) in enumerate(sizes) for p in probes[i]]
+        rows, locs = blind.encode(self, lq_device.prepare_windows(src, wins).lq)
+        return blind.decode(sizes, probes, rows, locs)
+
+    @staticmethod
+    def _reading_details(r, dx=0.0, dy=0.0):
+        """what ``details`` reports of a reading (None stays None): text, boxes — moved by (dx, dy) — and overflow"""
+        return None if r is None else dict(text=r["text"], boxes=[[b[0] + dx, b[1] + dy, b[2] + dx, b[3] + dy] for b in r["boxes"]], overflow=r["overflow"])
+
+    def _read_regions(self, sizes, need, probe_width, max_glyphs, make_lq, who, what):
+        """the reading pass of the restore entry points: ``need``: the lines (regions) whose text is None; ``make_lq(probes)`` → the encoder input
+        of their probes (``probes[i]``: ``blind.plan_probes`` of line i), fp32 [ΣP,3,32,512] in ``need``'s order → {i: reading}.  A line of
+        several probes: ``blind.decode``'s dict, None for an empty reading.  A line of one probe: labels (int64 [n,1], at most ``max_glyphs``) and
+        ``locs``, its ``preds_locs`` row, straight from the encoder as ``_strips_from_images(texts=None)`` takes them, beside text, boxes, overflow."""
+        from . import blind, lq_io
+        probes = {}
+        for i in need:
+            try:
+                probes[i] = blind.plan_probes(sizes[i][0], sizes[i][1], probe_width)
+            except ValueError as e:
+                raise ValueError("%s: %s %d: %s" % (who, what, i, e)) from None
+        rows, locs = blind.encode(self, make_lq(probes))
+        read, j = {}, 0
+        for i in need:
+            (h, w), pr = sizes[i], probes[i]
+            if len(pr) > 1:
+                read[i] = blind.decode([sizes[i]], [pr], rows[j:j + len(pr)], locs[j:j + len(pr)])[0]
+            else:
+                lab = collapse_indices(rows[j])
+                labels = torch.tensor(lab, dtype=torch.int64).reshape(-1, 1)[:max_glyphs]
+                n = int(labels.shape[0])
+                lr = torch.from_numpy(np.array(locs[j:j + 1], dtype=np.float32))
+                edges = [(float(lr[0, 2 * g]) * 512 * h / 32, float(lr[0, 2 * g + 1]) * 512 * h / 32) for g in range(min(n, blind.SLOTS))]
+                read[i] = dict(labels=labels, locs=locs_from_left_right(lr)[:, :2 * n].contiguous(), text=lq_io.text_from_labels(labels.flatten().tolist()),
+                               boxes=[[min(a, b), 0.0, max(a, b), float(h)] for a, b in edges], probes=list(pr), overflow=len(lab) > n)
+            j += len(pr)
+        return read
+
+    def _joined_lines(self, images, texts, boxes, max_glyphs, overlap_glyphs, who, what, probe_width=384):
         """``restore_lines`` up to the joined lines on the device: → (uint8 BGR [L,128,max out_w,3] — ``long_lines.compose_lines`` of the L lines
         that are restored, or None where there is none —, the plan per image (None for a line that is skipped), the positions of the L lines in
-        ``images``).  ``who`` / ``what`` name the entry point and its unit ("image", "region") in the errors."""
+        ``images``, and — where a text is None — the readings, {position: ``_read_regions``' entry}, else None).  ``who`` / ``what`` name the entry
+        point and its unit ("image", "region") in the errors.  With every text given the windows' crops are taken on the host; with a text to read
+        the lines are uploaded once and the probes and the planned windows are views of them (``lq_device.prepare_windows``)."""
         from . import lq_device
-        plans, labels, locs_rows, live = self._plan_lines([(int(img.shape[0]), int(img.shape[1])) for img in images], texts, boxes, max_glyphs,
-                                                          overlap_glyphs, who, what)
+        sizes = [tuple(int(v) for v in np.shape(img)[:2]) for img in images]
+        dev = next(self.sr.parameters()).device
+        texts = self._texts_or_read(who, texts, len(images))
+        need =[i for i, t in enumerate(texts) if t is None] if len(texts) == len(images) else []
+        if not need:
+            plans, labels, locs_rows, live = self._plan_lines(sizes, texts, boxes, max_glyphs, overlap_glyphs, who, what)
+            if not live:
+                return None, plans, live, None
+            crops = [np.ascontiguousarray(images[i][:, p.c0:p.c1]) for i in live for p in plans[i]]
+            prep = lq_device.prepare_strips(crops, dev)
+            return self._restore_planned(prep.lq, labels, locs_rows, plans, live), plans, live, None
+        src, offsets = lq_device.upload_lines(images, dev)                                        # the one copy of the pixels
+        view = lambda i, c0, c1: lq_device.line_window(offsets[i], sizes[i][0], sizes[i][1], c0, c1)
+        read = self._read_regions(sizes, need, probe_width, max_glyphs,
+                                  lambda probes: lq_device.prepare_windows(src, [view(i, p[0], p[1]) for i in need for p in probes[i]]).lq, who, what)
+        plans, labels, locs_rows, live = self._plan_lines(sizes, texts, boxes, max_glyphs, overlap_glyphs, who, what, read)
         if not live:
-            return None, plans, live
-        crops = [np.ascontiguousarray(images[i][:, p.c0:p.c1]) for i in live for p in plans[i]]
-        prep = lq_device.prepare_strips(crops, next(self.sr.parameters()).device)
-        return self._restore_planned(prep.lq, labels, locs_rows, plans, live), plans, live
+            return None, plans, live, read
+        prep = lq_device.prepare_windows(src, [view(i, p.c0, p.c1) for i in live for p in plans[i]])
+        return self._restore_planned(prep.lq, labels, locs_rows, plans, live), plans, live, read
 
-    def _plan_lines(self, sizes, texts, boxes, max_glyphs, overlap_glyphs, who, what):
+    def _plan_lines(self, sizes, texts, boxes, max_glyphs, overlap_glyphs, who, what, read=None):
         """the planning half of ``_joined_lines``, which needs no pixel: ``sizes[i]`` = (h, w) of line i, ``boxes[i]`` its character boxes in its own
         pixels (or None: evenly spaced ones) → (the plan per line, None for a line that is skipped; per window of the batch, in the plans' order,
-        its label tensor and its ``preds_locs`` row; the positions of the lines that are restored)"""
-        from . import long_lines, lq_io
-        if texts is None:
-            raise ValueError("%s needs texts: a window is a run of whole characters, and windows cut blind would cut characters in half "
-                             "(restore_images(texts=None) reads a strip of at most 512 px at height 32 without them)" % who)
+        its label tensor and its ``preds_locs`` row; the positions of the lines that are restored).  ``read``: {i: the reading of a line whose text
+        is None} (``_read_regions``): an empty one skips the line, a one-probe line is one window with the encoder's own labels and ``preds_locs``,
+        a read line's labels and boxes stand in for the given ones."""
+        from . import long_lines, lq_device, lq_io
         if len(texts) != len(sizes):
             raise ValueError("%s: one text per %s expected (%d %ss, %d texts)" % (who, what, len(sizes), what, len(texts)))
         n_cls = self.gan.TextGenerator.class_num
         plans, labels, locs_rows = [None] * len(sizes), [], []
         for i, ((h, w), text) in enumerate(zip(sizes, texts)):
+            r = None if read is None or i not in read else read[i]
+            if text is None:
+                if r is None:                                                  # an empty reading: the script's skip of an empty text
+                    continue
+                if "locs" in r:
+                    if not script_skips(r["labels"], n_cls):
+                        plans[i] = [long_lines.Window(0, w, 0, int(r["labels"].shape[0]), 0, int(lq_device.shape_geometry(h, w).show_w))]
+                        labels.append(r["labels"])
+                        locs_rows.append(r["locs"])
+                    continue
+                text = r["labels"]
             lab = lq_io.label_tensor(text)
             if script_skips(lab, n_cls):
                 continue
-            bx = boxes[i] if boxes is not None and boxes[i] is not None else lq_io.evenly_spaced_boxes(len(text), w, h)
+            bx = r["boxes"] if r is not None else boxes[i] if boxes is not None and boxes[i] is not None else lq_io.evenly_spaced_boxes(len(text), w, h)
             try:
                 plans[i] = long_lines.plan_windows(h, w, bx, max_glyphs, overlap_glyphs)
             except ValueError as e:
@@ -467,17 +558,44 @@ class MarconetPipeline:
     def _page_front(self, who, image, n, texts, per_region, expected, units):
         """the intake of the three ``restore_page*`` entry points, ``who``: the ``texts`` refusal, one text — and one entry of every list of
         ``per_region`` that is not None — per region (``n`` of them; the message says ``expected`` of ``units``), a uint8 RGB HxWx3 page (TypeError)
-        → (the page as an array, per region whether it is restored: it has a character and none outside the alphabet)"""
+        → (the page as an array, per region whether it is restored: it has a character and none outside the alphabet, the texts as a list).
+        ``texts=None`` stands for a None per region; a region whose text is None is read (``_restore_page_records``) and is checked as a restored
+        one — whether it has a character is known only once the page is on the device."""
         from . import lq_io
-        if texts is None:
-            raise ValueError("%s needs texts: a window is a run of whole characters, and windows cut blind would cut characters in half" % who)
+        texts = self._texts_or_read(who, texts, n)
         if len(texts) != n or any(l is not None and len(l) != n for l in per_region):
             raise ValueError("%s: %s expected (%d %s, %d texts)" % (who, expected, n, units, len(texts)))
         image = np.asarray(image)
         if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3 or image.size == 0:
             raise TypeError("%s: uint8 RGB HxWx3 page expected" % who)
         n_cls = self.gan.TextGenerator.class_num
-        return image, [not script_skips(lq_io.label_tensor(t), n_cls) for t in texts]
+        return image, [t is None or not script_skips(lq_io.label_tensor(t), n_cls) for t in texts], list(texts)
+
+    def _texts_or_read(self, who, texts, n):
+        """``texts`` as a list, ``texts=None`` standing for a None — "read it" — per unit.  Reading is the encoder's work: with the networks on no
+        HIP device a text that is None is refused here, before anything is copied, in the words this refusal always had"""
+        texts = [None] * n if texts is None else texts
+        if any(t is None for t in texts) and next(self.sr.parameters()).device.type != "cuda":
+            raise ValueError("%s needs texts: a window is a run of whole characters, and windows cut blind would cut characters in half — a text "
+                             "that is None is read by the encoder, which needs the networks on a HIP device (they are on %s)"
+                             % (who, next(self.sr.parameters()).device))
+        return texts
+
+    @staticmethod
+    def _rows_in_order(parts, have, want):
+        """``parts``: tensors whose rows, concatenated, are the items ``have`` → the rows of the items ``want`` (the same items in another order)"""
+        rows = parts[0] if len(parts) == 1 else torch.cat(parts)
+        if have == want:
+            return rows
+        at = {key: j for j, key in enumerate(have)}
+        return rows.index_select(0, torch.tensor([at[key] for key in want], dtype=torch.int64, device=rows.device))
+
+    @staticmethod
+    def _columns_need_text(who, columns):
+        """``columns``: the columns whose text is None.  A column's cells are cut from its text, one per character, so it cannot be read blind"""
+        if columns:
+            raise ValueError("%s: region %d: a column needs its text (its cells are cut from it, one per character): only horizontal lines, "
+                             "quadrilaterals and curves are read where the text is None" % (who, columns[0]))
 
     @staticmethod
     def _page_finish(plans, compose, details, extra):
@@ -497,7 +615,8 @@ class MarconetPipeline:
         return None if char_boxes is None else [[c[0] - box[0], c[1] - box[1], c[2] - box[0], c[3] - box[1]] for c in char_boxes]
 
     @torch.no_grad()
-    def restore_page(self, image, boxes, texts, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False, overlap="refuse"):
+    def restore_page(self, image, boxes, texts=None, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False, overlap="refuse",
+                     probe_width=384):
         """A page and its text regions → the page enlarged ``scale`` times with every text line restored in place: uint8 RGB [s·H, s·W, 3] on the
         host, the bytes of ``pages.compose_host(image, self.restore_lines(crops, texts, char_boxes), boxes, scale, feather)`` for the crops
         ``image[y1:y2, x1:x2]``.  ``image``: uint8 RGB [H, W, 3]; ``boxes[i]``: region i's text-line box [x1, y1, x2, y2] in page pixels (numbers that
@@ -515,14 +634,21 @@ class MarconetPipeline:
         descenders of neighbours — are pasted in list order, a later region blended under its own ramp into what the page holds by then (painter's
         order, ``pages``' head), the bytes of ``pages.compose_host(..., overlap="order")``.  The crops are still taken from the original page.  The
         page is then composed by ONE ``mnet_paste_ordered_u8`` launch whose workgroups own page tiles, with or without overlaps.
-        ``texts`` is required, for ``restore_lines``' reason.  ``details=True`` → ``(page, regions)``: per region a dict with ``plan`` (its windows),
-        ``out_w`` (the width of its restored line at height 128) and ``rect`` (x0, y0, rw, rh in the result), None where it kept the background.
+        ``texts=None``, or ``None`` as one region's text, means "read it", as in ``restore_lines`` (``blind``'s head states the reading): the probe
+        windows of every region that is read are views of the uploaded page (``lq_device.prepare_windows``: no crop is cut, no second upload), ONE
+        encoder forward reads them all, and the region's text and boxes are then planned as given ones are — so are the planned windows of such
+        a page views of it.  A region whose reading is empty keeps the background; it is checked (its rectangle, overlaps) as a restored one.
+        ``details=True`` → ``(page, regions)``: per region a dict with ``plan`` (its windows), ``out_w`` (the width of its restored line at height
+        128) and ``rect`` (x0, y0, rw, rh in the result), for a region that was read also ``text``, ``boxes`` (its character boxes in PAGE pixels)
+        and ``overflow`` (a probe held more than the encoder's 16 characters); None where it kept the background.
         Not covered: a blend of overlapping regions other than painter's order; vertical columns that are rotated or in perspective (upright columns of stacked characters:
         ``restore_page_columns``; rotated, quadrilateral and perspective regions: ``restore_page_quads``; curved text: ``restore_page_curves``; a page
-        that mixes these kinds, overlapping or not: ``restore_page_regions``); detection and recognition (the caller's); several pages in one launch."""
+        that mixes these kinds, overlapping or not: ``restore_page_regions``); detection (the caller's: the boxes) and the QUALITY of a blind reading
+        (the checkpoint's: a text the caller's recogniser supplies is used as given); repairing a probe that overflowed; reading a column
+        (``restore_page_columns`` needs a column's text); several pages in one launch."""
         from . import pages
         who = "restore_page"
-        image, restored = self._page_front(who, image, len(boxes), texts, [char_boxes], "one text (and one list of character boxes, or None) per box", "boxes")
+        image, restored, texts = self._page_front(who, image, len(boxes), texts, [char_boxes], "one text (and one list of character boxes, or None) per box", "boxes")
         H, W = int(image.shape[0]), int(image.shape[1])
         boxes = [pages.round_box(b, H, W) for b in boxes]
         try:
@@ -535,10 +661,10 @@ class MarconetPipeline:
                 return pages.paste_ordered(out, joined, pages.as_cell(pages.build_table(rects, out_ws, feather, int(joined.shape[1]))))
             return pages.paste_rects(out, joined, rects, out_ws, feather)
         return self._restore_page_records(who, image, [dict(kind="line", box=b, rect=r) for b, r in zip(boxes, rects)], texts, char_boxes, scale, max_glyphs,
-                                          overlap_glyphs, paste, details, [dict(rect=r) for r in rects])
+                                          overlap_glyphs, paste, details, [dict(rect=r) for r in rects], probe_width)
 
     @torch.no_grad()
-    def restore_page_quads(self, image, quads, texts, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False):
+    def restore_page_quads(self, image, quads, texts=None, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False, probe_width=384):
         """``restore_page`` for text regions that are convex quadrilaterals — rotated rectangles and four-point polygons, what a text detector emits
         for a sign photographed at an angle, a slanted scan or a line of rotated characters.  ``quads[i]``: region i's four corners [[x, y]] x 4 in
         page pixels (any numbers), in the text's own reading order: top-left, top-right, bottom-right, bottom-left of the line as it is read (a line
@@ -558,10 +684,13 @@ class MarconetPipeline:
         in the result) and ``size`` (rw, rh: the upright foreground's size), None where it kept the background.
         Not covered: overlapping regions, and other kinds of region on the same page (both: ``restore_page_regions``); vertical columns that are
         rotated or in perspective (upright columns: ``restore_page_columns``); curved vertical columns (curved text: ``restore_page_curves``);
-        detection and recognition; several pages in one launch."""
+        detection; several pages in one launch.
+        ``texts=None`` / a region's text ``None``: the region is read as in ``restore_page`` — its probe windows come from one more
+        ``mnet_quad_crop_u8`` launch (the probes' first columns and widths) through ``lq_device.prepare_packed`` —; ``details`` then adds ``text``,
+        ``boxes`` (in the RECTIFIED CROP's pixels) and ``overflow``.  ``char_boxes[i]`` may be ``{"crop": boxes}``: boxes in the crop already."""
         from . import quads as qd
         who = "restore_page_quads"
-        image, restored = self._page_front(who, image, len(quads), texts, [char_boxes],
+        image, restored, texts = self._page_front(who, image, len(quads), texts, [char_boxes],
                                            "one text (and one list of character boxes, or None) per quadrilateral", "quadrilaterals")
         try:
             regions = qd.check_quads(int(image.shape[0]), int(image.shape[1]), quads, restored, scale, feather)
@@ -569,10 +698,10 @@ class MarconetPipeline:
             raise ValueError("%s: %s" % (who, e)) from None
         return self._restore_page_records(who, image, [dict(r, kind="quad") for r in regions], texts, char_boxes, scale, max_glyphs, overlap_glyphs,
                                           lambda out, joined, out_ws, live, plans: qd.paste_quads(out, joined, out_ws, regions, int(feather)), details,
-                                          [dict(quad=r["out_quad"], size=(r["rw"], r["rh"])) for r in regions])
+                                          [dict(quad=r["out_quad"], size=(r["rw"], r["rh"])) for r in regions], probe_width)
 
     @torch.no_grad()
-    def restore_page_curves(self, image, polygons, texts, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False):
+    def restore_page_curves(self, image, polygons, texts=None, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False, probe_width=384):
         """``restore_page_quads`` for text regions that are curved strips — seals and round stamps, arched shop signs, logos, text on bottles and
         banners: what a text detector emits as a polygon of 2K points (CTW1500, Total-Text and ArT style).  ``polygons[i]``: region i's 2K points
         [[x, y]] in page pixels (any numbers), 2 <= K <= 33: the K top points left to right in reading order, then the K bottom points right to
@@ -593,11 +722,12 @@ class MarconetPipeline:
         page's border, the paste is clipped).  ``details=True`` → ``(page, regions)``: per region a dict with ``plan``, ``out_w``, ``polygon``
         (the points in the result) and ``size`` (rw, rh: the upright foreground's size), None where it kept the background.
         Not covered: overlapping regions — a seal over the text lines — and other kinds of region on the same page (both:
-        ``restore_page_regions``); curved vertical columns (upright ones: ``restore_page_columns``); detection and recognition; several pages in
-        one launch."""
+        ``restore_page_regions``); curved vertical columns (upright ones: ``restore_page_columns``); detection; several pages in one launch.
+        ``texts=None`` / a region's text ``None``: the region is read as in ``restore_page_quads``, its probes by one more ``mnet_curve_crop_u8``
+        launch; ``details`` then adds ``text``, ``boxes`` (in the rectified strip's pixels) and ``overflow``; ``char_boxes[i]`` may be ``{"crop": boxes}``."""
         from . import curves as cv
         who = "restore_page_curves"
-        image, restored = self._page_front(who, image, len(polygons), texts, [char_boxes],
+        image, restored, texts = self._page_front(who, image, len(polygons), texts, [char_boxes],
                                            "one text (and one list of character boxes, or None) per polygon", "polygons")
         try:
             regions = cv.check_curves(int(image.shape[0]), int(image.shape[1]), polygons, restored, scale, feather)
@@ -605,11 +735,11 @@ class MarconetPipeline:
             raise ValueError("%s: %s" % (who, e)) from None
         return self._restore_page_records(who, image, [dict(r, kind="curve") for r in regions], texts, char_boxes, scale, max_glyphs, overlap_glyphs,
                                           lambda out, joined, out_ws, live, plans: cv.paste_curves(out, joined, out_ws, regions, int(feather)), details,
-                                          [dict(polygon=r["out_polygon"], size=(r["rw"], r["rh"])) for r in regions])
+                                          [dict(polygon=r["out_polygon"], size=(r["rw"], r["rh"])) for r in regions], probe_width)
 
     @torch.no_grad()
     def restore_page_columns(self, image, boxes, texts, vertical=None, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False,
-                             overlap="refuse"):
+                             overlap="refuse", probe_width=384):
         """``restore_page`` for pages with vertical text: columns of upright characters stacked top to bottom (shop signs, couplets, book spines,
         traditional typesetting).  ``boxes[i]``: region i's box [x1, y1, x2, y2] in page pixels, rounded outward as in ``restore_page``;
         ``vertical[i]``: region i is a column, read top to bottom (None: every region is); a region with ``vertical[i]`` false is a horizontal line,
@@ -634,14 +764,17 @@ class MarconetPipeline:
         regions and the columns' cells together in region order, a column's cells consecutive, in the place of the two paste launches.
         Not covered: a blend of overlapping regions other than painter's order; vertical columns that are rotated or in perspective; right-to-left ordering of columns (the caller's);
         curved vertical columns (curved horizontal text: ``restore_page_curves``); a column on one page with a quadrilateral or a curved region
-        (``restore_page_regions``); detection and recognition; several pages in one launch."""
+        (``restore_page_regions``); detection and recognition; several pages in one launch.
+        A horizontal region whose text is ``None`` is read as in ``restore_page``; a COLUMN whose text is ``None`` is a ValueError that names it:
+        its cells are cut from its text, one per character."""
         from . import columns as cl, pages
         who, n = "restore_page_columns", len(boxes)
-        image, restored = self._page_front(who, image, n, texts, [char_boxes, vertical],
+        image, restored, texts = self._page_front(who, image, n, texts, [char_boxes, vertical],
                                            "one text (one flag, and one list of character boxes, or None) per box", "boxes")
         H, W = int(image.shape[0]), int(image.shape[1])
         vertical = [True] * n if vertical is None else [bool(v) for v in vertical]
         boxes = [pages.round_box(b, H, W) for b in boxes]
+        self._columns_need_text(who, [i for i in range(n) if vertical[i] and texts[i] is None])
         try:
             ordered = pages.check_overlap(overlap)
             pages.region_rects(H, W, boxes, restored, scale, feather, overlap=overlap)
@@ -663,11 +796,11 @@ class MarconetPipeline:
             pages.paste_rects(out, joined, rects, [out_ws[i] if i in lines_ else None for i in range(n)], int(feather), [line_of[i] for i in lines_])
             return cl.paste_columns(out, joined, [line_of[i] for i in cols], columns, [rects[i] for i in cols], int(feather))
         return self._restore_page_records(who, image, recs, texts, char_boxes, scale, max_glyphs, overlap_glyphs, paste, details,
-                                          [dict(rect=r["rect"]) if "cuts" not in r else dict(rect=r["rect"], cuts=r["cuts"], widths=r["widths"]) for r in recs])
+                                          [dict(rect=r["rect"]) if "cuts" not in r else dict(rect=r["rect"], cuts=r["cuts"], widths=r["widths"]) for r in recs], probe_width)
 
     @torch.no_grad()
-    def restore_page_regions(self, image, regions, texts, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False,
-                             overlap="refuse"):
+    def restore_page_regions(self, image, regions, texts=None, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False,
+                             overlap="refuse", probe_width=384):
         """``restore_page`` for a page that MIXES kinds of text region, which may lie over one another: a seal stamped over the text lines, a slanted
         stamp across a table, a sign's column beside a rotated line.  ``regions[i]``: a dict with exactly one of ``"box"`` ([x1, y1, x2, y2], rounded
         outward as in ``restore_page``; with ``"vertical": True`` a column of upright characters as in ``restore_page_columns``), ``"quad"`` (four
@@ -687,11 +820,16 @@ class MarconetPipeline:
         Both modes compose through the same launch.  Every refusal — each kind's own, naming the region — is raised before anything is copied or
         launched.  ``details=True`` → ``(page, regions)``: per region its kind's existing dict plus ``kind`` ("line", "column", "quad", "curve"),
         None where it kept the background.
-        Not covered: a blend of overlapping regions other than painter's order; vertical columns that are rotated or curved; detection and
-        recognition (the caller's); several pages in one launch."""
+        ``texts=None`` / a region's text ``None``: lines, quadrilaterals and curves are read, each as in its own entry point — the lines' probes
+        views of the page, at most one crop launch per kind for the other probes, ONE encoder forward for all —; a column whose text is ``None`` is
+        a ValueError that names it.  ``details`` then adds ``text``, ``boxes`` (a line's in page pixels, a quadrilateral's and a curve's in their
+        crops) and ``overflow``; ``char_boxes[i]`` may be ``{"crop": boxes}`` for boxes that are in the region's crop already.
+        Not covered: a blend of overlapping regions other than painter's order; vertical columns that are rotated or curved; detection (the
+        caller's) and the quality of a blind reading (the checkpoint's); reading a column; several pages in one launch."""
         from . import regions as rg
         who, n = "restore_page_regions", len(regions)
-        image, restored = self._page_front(who, image, n, texts, [char_boxes], "one text (and one list of character boxes, or None) per region", "regions")
+        image, restored, texts = self._page_front(who, image, n, texts, [char_boxes], "one text (and one list of character boxes, or None) per region", "regions")
+        self._columns_need_text(who, [i for i, r in enumerate(regions) if texts[i] is None and isinstance(r, dict) and "box" in r and r.get("vertical")])
         try:
             recs = rg.normalize_regions(int(image.shape[0]), int(image.shape[1]), regions, restored, texts,
                                         [None if char_boxes is None else char_boxes[i] for i in range(n)], scale, feather, overlap)
@@ -706,16 +844,19 @@ class MarconetPipeline:
             else:
                 extra.append(dict(kind="curve", polygon=r["out_polygon"], size=(r["rw"], r["rh"])))
         return self._restore_page_records(who, image, recs, texts, char_boxes, scale, max_glyphs, overlap_glyphs,
-                                          lambda out, joined, out_ws, live, plans: rg.paste_regions(out, joined, out_ws, recs, int(feather)), details, extra)
+                                          lambda out, joined, out_ws, live, plans: rg.paste_regions(out, joined, out_ws, recs, int(feather)), details, extra, probe_width)
 
-    def _restore_page_records(self, who, image, recs, texts, char_boxes, scale, max_glyphs, overlap_glyphs, paste, details, extra):
+    def _restore_page_records(self, who, image, recs, texts, char_boxes, scale, max_glyphs, overlap_glyphs, paste, details, extra, probe_width=384):
         """the one driver of the five ``restore_page*`` entry points, from their checked regions to the page on the host.  ``recs[i]``: region i's
         record as ``regions.normalize_regions`` gives it — ``kind`` "line" or "column" with ``box`` (a column that is restored: ``cuts``, ``widths``),
         "quad" (``quads.check_quads``' record) or "curve" (``curves.check_curves``') —; ``char_boxes`` in PAGE pixels.  Per kind the crop's size and
         the character boxes in the crop (a kind's ValueError names ``who`` and the region), ``_plan_lines``, the packed layout — the host crops of
         the lines at the head, then the columns', the quadrilaterals' and the curves' windows, each kind from its own base —, and in ``compose``:
         one upload of the page, the background, at most one gather / crop launch per kind present, ``lq_device.prepare_packed``, the forward and
-        the join, then ``paste(out, joined, out_ws, live, plans)``, the caller's paste, and ``_page_finish`` with the caller's ``extra``."""
+        the join, then ``paste(out, joined, out_ws, live, plans)``, the caller's paste, and ``_page_finish`` with the caller's ``extra``.
+        A region whose text is None is read first (``_read_regions``): the page goes to the device then, once; a line's probes are views of it, the
+        quadrilaterals' and curves' probes one crop launch per kind into a buffer of their own; the reading's boxes are in crop coordinates, what
+        ``_plan_lines`` plans.  On such a page the lines' planned windows are views of the page too, in the place of the host crops and their upload."""
         from . import columns as cl, curves as cv, lq_device, pages, quads as qd
         n = len(recs)
         cb = [None if char_boxes is None else char_boxes[i] for i in range(n)]
@@ -727,24 +868,65 @@ class MarconetPipeline:
                     local[i] = cl.virtual_boxes(r["widths"])
                 elif r["kind"] in ("line", "column"):
                     sizes.append((r["box"][3] - r["box"][1], r["box"][2] - r["box"][0]))
-                    local[i] = self._boxes_in_crop(cb[i], r["box"])
+                    local[i] = cb[i]["crop"] if isinstance(cb[i], dict) else self._boxes_in_crop(cb[i], r["box"])
                 else:
                     sizes.append((r["ch"], r["cw"]))
                     if r["kind"] == "quad":
                         maps[i] = qd.quad_map(r["quad"], r["cw"], r["ch"])
-                    if cb[i] is not None:
+                    if isinstance(cb[i], dict):                 # boxes in the rectified crop already: what ``details`` reports of a region that was read
+                        local[i] = cb[i]["crop"]
+                    elif cb[i] is not None:
                         local[i] = qd.char_boxes_in_crop(cb[i], maps[i], r["cw"], r["ch"]) if r["kind"] == "quad" else \
                             cv.char_boxes_in_crop(cb[i], r["segs"], r["cw"], r["ch"])
             except ValueError as e:
                 raise ValueError("%s: region %d: %s" % (who, i, e)) from None
-        plans, labels, locs_rows, live = self._plan_lines(sizes, texts, local, max_glyphs, overlap_glyphs, who, "region")
+        page_dev, W = [], int(image.shape[1])
+
+        def page_on_device():                                           # the one copy of the page, made when it is first needed
+            if not page_dev:
+                page_dev.append(torch.from_numpy(np.ascontiguousarray(image)).to(next(self.sr.parameters()).device))
+            return page_dev[0]
+
+        def page_view(i, c0, c1):                                       # the columns [c0, c1) of line i's box as a window of the page
+            x1, y1, _, y2 = recs[i]["box"]
+            return ((y1 * W + x1 + int(c0)) * 3, 3 * W, y2 - y1, int(c1) - int(c0))
+
+        def read_lq(probes):                                            # the encoder input of every probe, in ``need``'s order
+            page_d = page_on_device()
+            keys = [[(i, k) for i in need if recs[i]["kind"] == kind for k in range(len(probes[i]))] for kind in ("line", "quad", "curve")]
+            parts = []
+            if keys[0]:
+                parts.append(lq_device.prepare_windows(page_d.reshape(-1), [page_view(i, *probes[i][k][:2]) for i, k in keys[0]]).lq)
+            if keys[1] or keys[2]:
+                size = lambda i, k: (probes[i][k][1] - probes[i][k][0], recs[i]["ch"])
+                q_sz, c_sz = [size(i, k) for i, k in keys[1]], [size(i, k) for i, k in keys[2]]
+                q_c0, c_c0 = [probes[i][k][0] for i, k in keys[1]], [probes[i][k][0] for i, k in keys[2]]
+                q_t, base = qd.crop_table([maps[i] for i, _ in keys[1]], q_sz, q_c0, 0)
+                c_t, _, total = cv.crop_table([recs[i]["segs"] for i, _ in keys[2]], c_sz, c_c0, base)
+                buf = torch.empty((total,), dtype=torch.uint8, device=page_d.device)
+                if keys[1]:
+                    qd.crop_quads(page_d, [maps[i] for i, _ in keys[1]], q_sz, q_c0, 0, buf)
+                if keys[2]:
+                    cv.crop_curves(page_d, [recs[i]["segs"] for i, _ in keys[2]], c_sz, c_c0, base, buf)
+                parts.append(lq_device.prepare_packed(buf, [(h, w) for w, h in q_sz + c_sz], [int(o) for o in q_t["offset"]] + [int(o) for o in c_t["offset"]]).lq)
+            return self._rows_in_order(parts, keys[0] + keys[1] + keys[2], [(i, k) for i in need for k in range(len(probes[i]))])
+
+        need = [i for i in range(n) if texts[i] is None]                # the regions that are read: lines, quadrilaterals, curves (a column is refused)
+        read = self._read_regions(sizes, need, probe_width, max_glyphs, read_lq, who, "region") if need else None
+        if details and need:
+            shift = lambda i: (float(recs[i]["box"][0]), float(recs[i]["box"][1])) if recs[i]["kind"] == "line" else (0.0, 0.0)
+            extra = [e if i not in read or read[i] is None else dict(e, **self._reading_details(read[i], *shift(i))) for i, e in enumerate(extra)]
+        plans, labels, locs_rows, live = self._plan_lines(sizes, texts, local, max_glyphs, overlap_glyphs, who, "region", read)
         of_kind = lambda kind: [i for i in live if recs[i]["kind"] == kind]
         cols = of_kind("column")
         q_wins, c_wins = [[(i, k, p) for i in of_kind(kind) for k, p in enumerate(plans[i])] for kind in ("quad", "curve")]
-        flat, where, head = [], {}, 0                                   # the horizontal windows' crops, at the head of the packed batch
+        flat, where, head, views = [], {}, 0, {}                        # the horizontal windows' crops, at the head of the packed batch
         for i in of_kind("line"):
             x1, y1, x2, y2 = recs[i]["box"]
             for k, p in enumerate(plans[i]):
+                if need:                                                # a page that is read is on the device already: its lines' windows are views of it
+                    views[(i, k)] = page_view(i, p.c0, p.c1)
+                    continue
                 where[(i, k)] = ((y2 - y1, p.c1 - p.c0), head)
                 flat.append(np.ascontiguousarray(image[y1:y2, x1 + p.c0:x1 + p.c1]).reshape(-1))
                 head += flat[-1].size
@@ -760,7 +942,7 @@ class MarconetPipeline:
                 where[(i, k)] = ((h, w), int(off))
 
         def compose(out_ws):
-            page_d = torch.from_numpy(np.ascontiguousarray(image)).to(next(self.sr.parameters()).device)      # the one copy of the page
+            page_d = page_on_device()                                                            # the one copy of the page
             out = pages.enlarge(page_d, int(scale))
             if live:
                 packed = torch.empty((nbytes,), dtype=torch.uint8, device=page_d.device)         # the ragged batch of every kind's windows
@@ -773,9 +955,14 @@ class MarconetPipeline:
                     cv.crop_curves(page_d, [recs[i]["segs"] for i, _, _ in c_wins], c_sizes, [p.c0 for _, _, p in c_wins], c_base, packed)
                 if head:
                     packed[:head].copy_(torch.from_numpy(np.concatenate(flat)))               # the lines' crops: the one upload beside the page's
-                order = [where[(i, k)] for i in live for k in range(len(plans[i]))]
-                prep = lq_device.prepare_packed(packed, [o[0] for o in order], [o[1] for o in order])
-                paste(out, self._restore_planned(prep.lq, labels, locs_rows, plans, live), out_ws, live, plans)
+                keys = [(i, k) for i in live for k in range(len(plans[i]))]
+                packed_keys, parts = [key for key in keys if key in where], []
+                if views:
+                    parts.append(lq_device.prepare_windows(page_d.reshape(-1), [views[key] for key in keys if key in views]).lq)
+                if packed_keys:
+                    parts.append(lq_device.prepare_packed(packed, [where[key][0] for key in packed_keys], [where[key][1] for key in packed_keys]).lq)
+                lq = self._rows_in_order(parts, [key for key in keys if key in views] + packed_keys, keys)
+                paste(out, self._restore_planned(lq, labels, locs_rows, plans, live), out_ws, live, plans)
             return out
         return self._page_finish(plans, compose, details, extra)
 
