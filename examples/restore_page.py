@@ -1,13 +1,14 @@
 #!/usr/bin/env python
 """A page and its text-line boxes in, the enlarged page with every text line restored in place out (MarconetPipeline.restore_page).
 
-    python examples/restore_page.py -i page.png -r regions.json -o out.png [--scale 4] [--feather 8] [--overlap refuse] [--precision fp16x2]
+    python examples/restore_page.py -i page.png -r regions.json -o out.png [--scale 4] [--feather 8] [--overlap refuse] [--blind-columns] [--precision fp16x2]
 
 ``regions.json`` is a list of ``{"box": [x1, y1, x2, y2], "text": "...", "char_boxes": [[x1, y1, x2, y2], ...]}``: a text line's box in page pixels
 (axis-aligned; numbers that are not integers are rounded outward), its characters, and — optionally — its character boxes in page pixels (evenly
 spaced ones otherwise).  The detector that produces the boxes is the caller's (SURVEY.md §8f NEXT-4); so is the recogniser, but a region WITHOUT
-``"text"`` is read by the encoder itself (marconet_amd/blind.py: overlapping probe windows give its text and character boxes; not a ``"vertical"``
-region, whose cells are cut from its text).  A region with no character or
+``"text"`` is read by the encoder itself (marconet_amd/blind.py: overlapping probe windows give its text and character boxes; a ``"vertical"``
+region only with ``--blind-columns``: its cells are then measured from its ink profile, marconet_amd/blind_columns.py — without the flag it is refused,
+its cells being cut from its text).  A region with no character or
 with a character outside the alphabet keeps the enlarged page's own pixels, as the script skips such a strip (test_sr.py:168-170, :181-190).
 A region may carry ``"quad": [[x, y], [x, y], [x, y], [x, y]]`` instead of ``"box"``: the four corners of a rotated or perspective line in its own
 reading order (top-left, top-right, bottom-right, bottom-left as the line is read).  If any region does, all regions go through
@@ -23,7 +24,8 @@ Two regions that share a pixel are refused by default.  ``--overlap order`` past
 region is blended, under its own feather ramp, over the earlier ones) — stacked lines whose outward-rounded boxes share a row, a sign's column over the
 line next to it.  It applies to ``"box"`` regions, ``"vertical"`` ones included; a file with a ``"quad"`` or a ``"polygon"`` is refused with it: those kinds
 still refuse overlaps.
-Not covered: overlapping quadrilateral and curved regions, vertical columns that are rotated, in perspective or curved, several pages per call.
+Not covered: overlapping quadrilateral and curved regions, vertical columns that are rotated, in perspective or curved, the quality of a blind
+column's segmentation and reading (columns whose cells are far from square), several pages per call.
 
 All regions are restored as one batch; the page is enlarged (cv2's INTER_CUBIC arithmetic) and every line resized, pasted and feathered on the GPU —
 only the PNG decode and encode run on the host.  Weights: ``$MARCONET_CKPT_DIR`` as in examples/restore_strips.py; without them the seeded
@@ -41,9 +43,9 @@ from marconet_amd import checkpoints, lq_io                                     
 from marconet_amd.pipeline import MarconetPipeline                               # noqa: E402
 
 
-def load_regions(path):
+def load_regions(path, blind_columns=False):
     """→ (boxes, texts, char_boxes or None, quads or None, vertical or None, polygons or None): ``quads`` where any region carries "quad" — then every
-    region's four corners, a box turned into its own; ``vertical`` where any region carries "vertical": true — then one flag per region; ``polygons``
+    region's four corners, a box turned into its own; ``blind_columns``: a "vertical" region may come without "text" (``--blind-columns`` reads it); ``vertical`` where any region carries "vertical": true — then one flag per region; ``polygons``
     where any region carries "polygon" — then every region's points, a box or a quadrilateral turned into its four"""
     with open(path, encoding="utf8") as f:
         regions = json.load(f)
@@ -52,7 +54,7 @@ def load_regions(path):
             return False
         if not isinstance(r.get("vertical", False), bool) or ("vertical" in r and "box" not in r):
             return False
-        if r.get("vertical", False) and "text" not in r:                      # a column's cells are cut from its text: it cannot be read blind
+        if r.get("vertical", False) and "text" not in r and not blind_columns:      # a column's cells are cut from its text: read only on request
             return False
         if "box" in r:
             return isinstance(r["box"], list) and len(r["box"]) == 4 and all(isinstance(v, (int, float)) for v in r["box"])
@@ -64,7 +66,7 @@ def load_regions(path):
         raise SystemExit('restore_page.py: %s must hold a list of {"box": [x1, y1, x2, y2], "text": "..."} or {"quad": [[x, y], [x, y], [x, y], [x, y]], '
                          '"text": "..."} or {"polygon": [[x, y], ...], "text": "..."} objects (numbers; one of "box", "quad" and "polygon" per region; '
                          '"vertical": true or false beside a "box" only; "text" may be left out — the region is then read by the encoder — except for a '
-                         '"vertical" region)' % path)
+                         '"vertical" region without --blind-columns)' % path)
     vertical = [bool(r.get("vertical", False)) for r in regions] if any(r.get("vertical", False) for r in regions) else None
     if vertical is not None and any("quad" in r for r in regions):
         raise SystemExit('restore_page.py: %s holds a "vertical" region (%d) and a "quad" region (%d): vertical columns go through restore_page_columns, '
@@ -95,9 +97,11 @@ def main():
     ap.add_argument("--feather", type=int, default=8, help="width in output pixels of the blend at a region's edge, 0..1024 (0: none)")
     ap.add_argument("--overlap", default="refuse", choices=["refuse", "order"],
                     help="order: overlapping box regions are pasted in the file's order (a later one over the earlier ones); refuse: they are an error")
+    ap.add_argument("--blind-columns", action="store_true",
+                    help='read a "vertical" region that has no "text": its cells are measured from its ink profile (marconet_amd/blind_columns.py)')
     ap.add_argument("--precision", default="fp16x2", choices=["fp16x2", "fp16x3", "fp16", "fp32"])
     a = ap.parse_args()
-    boxes, texts, char_boxes, quads, vertical, polygons = load_regions(a.regions)
+    boxes, texts, char_boxes, quads, vertical, polygons = load_regions(a.regions, a.blind_columns)
     if a.overlap == "order" and (quads is not None or polygons is not None):
         raise SystemExit('restore_page.py: --overlap order applies to "box" regions ("vertical" ones included); %s holds a "quad" or a "polygon", and '
                          'quadrilateral and curved regions still refuse overlaps' % a.regions)
@@ -109,7 +113,7 @@ def main():
     pipe = MarconetPipeline(*checkpoints.build_networks(sde, sdg, sds, "cuda"), precision=a.precision)
     if vertical is not None:
         page, regions = pipe.restore_page_columns(lq_io.load_png(a.image), boxes, texts, vertical=vertical, char_boxes=char_boxes, scale=a.scale, feather=a.feather,
-                                                  details=True, overlap=a.overlap)
+                                                  details=True, overlap=a.overlap, blind_columns=a.blind_columns)
     elif polygons is not None:
         page, regions = pipe.restore_page_curves(lq_io.load_png(a.image), polygons, texts, char_boxes=char_boxes, scale=a.scale, feather=a.feather, details=True)
     elif quads is not None:

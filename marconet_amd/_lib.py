@@ -55,6 +55,11 @@ class LqWindow(ctypes.Structure):
     _fields_ = [("offset", c_i64), ("pitch", c_int), ("h", c_int), ("w", c_int), ("dw", c_int), ("scale", c_double)]
 
 
+class RowInkBox(ctypes.Structure):
+    """mirror of ``mnet_ink_box`` (include/marconet_hip_rowink.h): one box of mnet_row_ink_u8's device table"""
+    _fields_ = [("offset", c_i64), ("pitch", c_int), ("h", c_int), ("w", c_int), ("out", c_int)]
+
+
 class PanelStrip(ctypes.Structure):
     """mirror of ``mnet_panel_strip`` (include/marconet_hip.h): one strip of mnet_panel_u8's device table"""
     _fields_ = [("show_w", c_int), ("preview_index", c_int), ("glyph0", c_int), ("n_glyphs", c_int), ("step", c_double)]
@@ -258,6 +263,11 @@ WINDOW_SYMBOLS = {
     "mnet_lq_windows_u8": (c_int, [c_void_p, c_i64, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
 }
 
+# ... and the one include/marconet_hip_rowink.h declares (the ink profile of boxes of a page: where a column's characters are, from its pixels)
+ROWINK_SYMBOLS = {
+    "mnet_row_ink_u8": (c_int, [c_void_p, c_i64, c_void_p, c_int, c_int, c_void_p, c_i64, c_void_p]),
+}
+
 _lib = None
 
 
@@ -275,7 +285,7 @@ def load():
             "marconet_amd: %s not found — build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or marconet_amd/csrc/build.sh (there is no CPU/eager fallback)" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(UPFOLD_SYMBOLS.items()) + list(UPFOLD_F32Z_SYMBOLS.items()) + list(QUAD_SYMBOLS.items()) + list(COLUMN_SYMBOLS.items()) + list(CURVE_SYMBOLS.items()) + list(ORDERED_SYMBOLS.items()) + list(MIXED_SYMBOLS.items()) + list(WINDOW_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(UPFOLD_SYMBOLS.items()) + list(UPFOLD_F32Z_SYMBOLS.items()) + list(QUAD_SYMBOLS.items()) + list(COLUMN_SYMBOLS.items()) + list(CURVE_SYMBOLS.items()) + list(ORDERED_SYMBOLS.items()) + list(MIXED_SYMBOLS.items()) + list(WINDOW_SYMBOLS.items()) + list(ROWINK_SYMBOLS.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is absent
         fn.restype = res
         fn.argtypes = args

@@ -18,7 +18,7 @@ from .packing import MX_DTYPE, SPLIT_DTYPE, is_split, mx_weight_rows, new_tensor
 
 __all__ = ["conv2d", "linear", "nchw_to_nhwc", "nhwc_to_nchw", "upsample2x", "affine_act", "groupnorm_affine",
            "adain_crop_concat", "adain_crop_concat_gn", "glyph_scatter_affine", "layernorm", "token_mix", "attention", "pixelnorm",
-           "embed_gather", "demod", "argmax_rows", "convert", "fused_bias_act", "sr_postprocess", "lq_from_u8", "lq_windows_u8", "panel_u8", "paste_u8", "quad_crop_u8", "quad_paste_u8", "curve_crop_u8", "curve_paste_u8", "paste_ordered_u8", "conv3x3_rgb", "torgb", "stats",
+           "embed_gather", "demod", "argmax_rows", "convert", "fused_bias_act", "sr_postprocess", "lq_from_u8", "lq_windows_u8", "row_ink_u8", "panel_u8", "paste_u8", "quad_crop_u8", "quad_paste_u8", "curve_crop_u8", "curve_paste_u8", "paste_ordered_u8", "conv3x3_rgb", "torgb", "stats",
            "pack_weights", "pack_wsq", "gather_rows", "style_rows", "nonfinite_flag", "compare_stats", "gn_partial_buffer", "can_emit_gn_partial", "groupnorm_affine_from_partial",
            "polyphase_plan", "upconv3x3_polyphase", "polyphase_ring_fix", "groupnorm_affine_from_partial_ring", "upfold_plan", "upfold3x3",
            "ACT_NONE", "ACT_RELU", "ACT_LRELU", "ACT_LRELU_SQRT2", "ACT_TANH", "ACT_GELU", "ACT_SIGMOID"]
@@ -890,6 +890,23 @@ def column_gather_u8(page, cells, max_dw, dst_h, dst):
                          % (cells.shape[0], int(max_dw), int(dst_h), list(page.shape), dst.numel()))
     _lib.check(lib.mnet_column_gather_u8(_p(page), int(page.shape[0]), int(page.shape[1]), _p(cells), int(cells.shape[0]), int(max_dw), int(dst_h),
                                          _p(dst), int(dst.numel()), _stream()), "mnet_column_gather_u8")
+    return dst
+
+
+def row_ink_u8(src, boxes, max_h, dst):
+    """mnet_row_ink_u8 (``blind_columns.row_ink``, box by box, with ==): ``src`` uint8 [bytes], the page; ``boxes`` uint8 [n, sizeof(mnet_ink_box)]
+    (``_lib.RowInkBox``: first byte, row pitch, size, first index in ``dst``); ``dst`` int32 [len] — all on the device; ``max_h``: the largest box
+    height of the table.  ``dst[out + r]`` = row r's total horizontal variation of integer luma, written for the rows of the boxes only (−1 for a
+    box that does not lie inside ``src``; nothing for rows that do not lie inside ``dst``); ``dst`` is returned.  One launch for all boxes."""
+    lib = _lib.load()
+    _need_cuda(src, boxes, dst)
+    if src.dtype != torch.uint8 or src.dim() != 1:
+        raise TypeError("row_ink_u8: uint8 [bytes] pixels expected")
+    if dst.dtype != torch.int32 or dst.dim() != 1:
+        raise TypeError("row_ink_u8: int32 [len] dst expected")
+    _check_table("row_ink_u8", "box table", boxes, _lib.RowInkBox, 8)
+    _lib.check(lib.mnet_row_ink_u8(_p(src), int(src.numel()), _p(boxes), int(boxes.shape[0]), int(max_h), _p(dst), int(dst.numel()), _stream()),
+               "mnet_row_ink_u8")
     return dst
 
 

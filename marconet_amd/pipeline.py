@@ -450,6 +450,70 @@ class MarconetPipeline:
         rows, locs = blind.encode(self, lq_device.prepare_windows(src, wins).lq)
         return blind.decode(sizes, probes, rows, locs)
 
+    @torch.no_grad()
+    def read_columns(self, image, boxes, scale=4, probe_width=384):
+        """What the encoder reads in vertical text columns whose text is unknown: ``image`` uint8 RGB [H, W, 3], ``boxes[i]`` column i's box
+        [x1, y1, x2, y2] in page pixels (rounded outward: ``pages.round_box``) → per column dict(text, labels, char_boxes [[x1, ya, x2, yb]] in
+        PAGE pixels top to bottom, cuts — ``columns.cell_cuts`` of that reading —, first_cuts, probes, overflow), None for an empty reading:
+        ``blind_columns.read_columns_host``'s result, ``==`` (``blind_columns``' head states the rules).  ``scale``: the scale of the restoration the
+        reading is meant for — ``settle`` drops characters whose cells it could not paste.  ONE upload of the page, ONE ``mnet_row_ink_u8`` launch
+        over all columns as views of the page, one device→host copy of all profiles, the first-pass cells and the probes on the host, ONE
+        ``mnet_column_gather_u8`` launch for every probe of every column (``columns.gather_table``, the probes as windows),
+        ``lq_device.prepare_packed``, ONE encoder forward and ``blind.encode``'s one copy back.  ValueError for a scale outside 1..8 and for a box
+        that is empty or outside the page, before anything is copied."""
+        from . import blind_columns as bc, pages
+        image = pages._page_array(image)
+        boxes = bc.check_boxes(image.shape[0], image.shape[1], boxes, scale)
+        if not boxes:
+            return []
+        page_d = torch.from_numpy(np.ascontiguousarray(image)).to(next(self.sr.parameters()).device)      # the one copy of the page
+        return self._read_columns(page_d, boxes, scale, probe_width)
+
+    def _read_columns(self, page_d, boxes, scale, probe_width, regions=None):
+        """``read_columns`` of a page that is on the device: ``page_d`` uint8 RGB [H, W, 3], ``boxes``: integer boxes inside it; ``regions[k]``: the
+        number a refusal gives column k"""
+        from . import _lib, blind, blind_columns as bc, columns as cl, lq_device
+        W = int(page_d.shape[1])
+        tab, starts, total = np.zeros((len(boxes),), dtype=np.dtype(_lib.RowInkBox)), [], 0
+        for k, (x1, y1, x2, y2) in enumerate(boxes):                    # the boxes as views of the page, as ``page_view`` has a line's windows
+            tab[k] = ((y1 * W + x1) * 3, 3 * W, y2 - y1, x2 - x1, total)
+            starts.append(total)
+            total += y2 - y1
+        ink = torch.empty((total,), dtype=torch.int32, device=page_d.device)
+        with ops.on_device(page_d):
+            ops.row_ink_u8(page_d.reshape(-1), ops.table_to_device(tab, page_d.device), int(tab["h"].max()), ink)
+        ink = ink.cpu().numpy()                                         # the one device→host copy of all profiles
+        plans = bc.plan_columns(boxes, [ink[s:s + b[3] - b[1]] for s, b in zip(starts, boxes)], probe_width, regions)
+        packed, shapes, offsets = cl.gather_columns(page_d, [(p["box"], p["first_cuts"], p["widths"], bc.probe_windows(p["probes"])) for p in plans])
+        rows, locs = blind.encode(self, lq_device.prepare_packed(packed, shapes, offsets).lq)
+        return bc.decode(plans, rows, locs, scale)
+
+    def _columns_read_first(self, who, image, blind, boxes, texts, char_boxes, scale, probe_width):
+        """``blind_columns=True``: the columns ``blind`` (positions in ``boxes``, integer boxes), whose text is None, are read (``_read_columns``)
+        and their readings' text and character boxes stand in for given ones → (the page on the device, to be shared with
+        ``_restore_page_records``; texts; char_boxes; {position: reading}).  An empty reading leaves the text "": the column keeps the background."""
+        n = len(boxes)
+        page_d = torch.from_numpy(np.ascontiguousarray(image)).to(next(self.sr.parameters()).device)      # the one copy of the page
+        try:
+            readings = self._read_columns(page_d, [boxes[i] for i in blind], scale, probe_width, blind)
+        except ValueError as e:
+            raise ValueError("%s: %s" % (who, e)) from None
+        texts, char_boxes = list(texts), [None] * n if char_boxes is None else list(char_boxes)
+        for i, r in zip(blind, readings):
+            texts[i], char_boxes[i] = ("", None) if r is None else (r["text"], r["char_boxes"])
+        return page_d, texts, char_boxes, dict(zip(blind, readings))
+
+    def _restored_again(self, restored, texts, blind):
+        """``_page_front``'s ``restored``, with the columns that were read judged by their reading's text"""
+        from . import lq_io
+        n_cls = self.gan.TextGenerator.class_num
+        return [not script_skips(lq_io.label_tensor(texts[i]), n_cls) if i in blind else r for i, r in enumerate(restored)]
+
+    @staticmethod
+    def _column_reading_details(extra, read):
+        """what ``details`` adds for a column that was read: ``text``, ``char_boxes`` (page pixels), ``first_cuts`` and ``overflow``"""
+        return [e if read.get(i) is None else dict(e, **{k: read[i][k] for k in ("text", "char_boxes", "first_cuts", "overflow")}) for i, e in enumerate(extra)]
+
     @staticmethod
     def _reading_details(r, dx=0.0, dy=0.0):
         """what ``details`` reports of a reading (None stays None): text, boxes — moved by (dx, dy) — and overflow"""
@@ -645,7 +709,7 @@ class MarconetPipeline:
         ``restore_page_columns``; rotated, quadrilateral and perspective regions: ``restore_page_quads``; curved text: ``restore_page_curves``; a page
         that mixes these kinds, overlapping or not: ``restore_page_regions``); detection (the caller's: the boxes) and the QUALITY of a blind reading
         (the checkpoint's: a text the caller's recogniser supplies is used as given); repairing a probe that overflowed; reading a column
-        (``restore_page_columns`` needs a column's text); several pages in one launch."""
+        (``restore_page_columns(blind_columns=True)`` does); several pages in one launch."""
         from . import pages
         who = "restore_page"
         image, restored, texts = self._page_front(who, image, len(boxes), texts, [char_boxes], "one text (and one list of character boxes, or None) per box", "boxes")
@@ -739,7 +803,7 @@ class MarconetPipeline:
 
     @torch.no_grad()
     def restore_page_columns(self, image, boxes, texts, vertical=None, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False,
-                             overlap="refuse", probe_width=384):
+                             overlap="refuse", probe_width=384, blind_columns=False):
         """``restore_page`` for pages with vertical text: columns of upright characters stacked top to bottom (shop signs, couplets, book spines,
         traditional typesetting).  ``boxes[i]``: region i's box [x1, y1, x2, y2] in page pixels, rounded outward as in ``restore_page``;
         ``vertical[i]``: region i is a column, read top to bottom (None: every region is); a region with ``vertical[i]`` false is a horizontal line,
@@ -764,9 +828,16 @@ class MarconetPipeline:
         regions and the columns' cells together in region order, a column's cells consecutive, in the place of the two paste launches.
         Not covered: a blend of overlapping regions other than painter's order; vertical columns that are rotated or in perspective; right-to-left ordering of columns (the caller's);
         curved vertical columns (curved horizontal text: ``restore_page_curves``); a column on one page with a quadrilateral or a curved region
-        (``restore_page_regions``); detection and recognition; several pages in one launch.
-        A horizontal region whose text is ``None`` is read as in ``restore_page``; a COLUMN whose text is ``None`` is a ValueError that names it:
-        its cells are cut from its text, one per character."""
+        (``restore_page_regions``); detection, and the quality of a column's segmentation and reading (``blind_columns``' head: columns whose
+        cells are far from square); several pages in one launch.
+        A horizontal region whose text is ``None`` is read as in ``restore_page``; a COLUMN whose text is ``None`` is a ValueError that names it
+        (its cells are cut from its text, one per character) unless ``blind_columns=True``: such a column is then read first
+        (``read_columns``: its cells measured from its ink profile, ``blind_columns``' head) and its reading's text and character boxes stand in
+        for given ones — the call returns, byte for byte, the call given ``details``' ``text`` and ``char_boxes`` for that column.  The refusals
+        that need no pixel (scale, feather, a box outside the page, ``overlap``) are still raised before anything is copied; the page is
+        uploaded once, for the reading and the restoration; the columns' probes go through an encoder forward of their own, beside the one that
+        reads the horizontal lines.  A column whose reading is empty keeps the background.  ``details`` adds ``text``, ``char_boxes`` (page
+        pixels), ``first_cuts`` and ``overflow`` for a column that was read."""
         from . import columns as cl, pages
         who, n = "restore_page_columns", len(boxes)
         image, restored, texts = self._page_front(who, image, n, texts, [char_boxes, vertical],
@@ -774,7 +845,16 @@ class MarconetPipeline:
         H, W = int(image.shape[0]), int(image.shape[1])
         vertical = [True] * n if vertical is None else [bool(v) for v in vertical]
         boxes = [pages.round_box(b, H, W) for b in boxes]
-        self._columns_need_text(who, [i for i in range(n) if vertical[i] and texts[i] is None])
+        blind, page_d, read = [i for i in range(n) if vertical[i] and texts[i] is None], None, {}
+        if not blind_columns:
+            self._columns_need_text(who, blind)
+        elif blind:
+            try:
+                pages.region_rects(H, W, boxes, restored, scale, feather, overlap=overlap)          # the refusals that need no pixel
+            except ValueError as e:
+                raise ValueError("%s: %s" % (who, e)) from None
+            page_d, texts, char_boxes, read = self._columns_read_first(who, image, blind, boxes, texts, char_boxes, scale, probe_width)
+            restored = self._restored_again(restored, texts, blind)
         try:
             ordered = pages.check_overlap(overlap)
             pages.region_rects(H, W, boxes, restored, scale, feather, overlap=overlap)
@@ -795,12 +875,13 @@ class MarconetPipeline:
                 return pages.paste_ordered(out, joined, cl.mixed_table(joined, [(line_of[i], rects[i], col_of.get(i, out_ws[i])) for i in live], int(feather)))
             pages.paste_rects(out, joined, rects, [out_ws[i] if i in lines_ else None for i in range(n)], int(feather), [line_of[i] for i in lines_])
             return cl.paste_columns(out, joined, [line_of[i] for i in cols], columns, [rects[i] for i in cols], int(feather))
+        extra = [dict(rect=r["rect"]) if "cuts" not in r else dict(rect=r["rect"], cuts=r["cuts"], widths=r["widths"]) for r in recs]
         return self._restore_page_records(who, image, recs, texts, char_boxes, scale, max_glyphs, overlap_glyphs, paste, details,
-                                          [dict(rect=r["rect"]) if "cuts" not in r else dict(rect=r["rect"], cuts=r["cuts"], widths=r["widths"]) for r in recs], probe_width)
+                                          self._column_reading_details(extra, read), probe_width, page_d)
 
     @torch.no_grad()
     def restore_page_regions(self, image, regions, texts=None, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False,
-                             overlap="refuse", probe_width=384):
+                             overlap="refuse", probe_width=384, blind_columns=False):
         """``restore_page`` for a page that MIXES kinds of text region, which may lie over one another: a seal stamped over the text lines, a slanted
         stamp across a table, a sign's column beside a rotated line.  ``regions[i]``: a dict with exactly one of ``"box"`` ([x1, y1, x2, y2], rounded
         outward as in ``restore_page``; with ``"vertical": True`` a column of upright characters as in ``restore_page_columns``), ``"quad"`` (four
@@ -824,12 +905,36 @@ class MarconetPipeline:
         views of the page, at most one crop launch per kind for the other probes, ONE encoder forward for all —; a column whose text is ``None`` is
         a ValueError that names it.  ``details`` then adds ``text``, ``boxes`` (a line's in page pixels, a quadrilateral's and a curve's in their
         crops) and ``overflow``; ``char_boxes[i]`` may be ``{"crop": boxes}`` for boxes that are in the region's crop already.
+        ``blind_columns=True``: a column whose text is ``None`` is read first, as in ``restore_page_columns`` (``read_columns``; an encoder
+        forward of its own beside the one that reads the other kinds), and its reading's text and character boxes stand in for given ones: the
+        call returns, byte for byte, the call given ``details``' ``text`` and ``char_boxes`` for that column.  Every refusal that needs no pixel
+        is still raised before anything is copied, and the page is uploaded once.  ``details`` adds ``text``, ``char_boxes``, ``first_cuts`` and
+        ``overflow`` for such a column; one whose reading is empty keeps the background.
         Not covered: a blend of overlapping regions other than painter's order; vertical columns that are rotated or curved; detection (the
-        caller's) and the quality of a blind reading (the checkpoint's); reading a column; several pages in one launch."""
-        from . import regions as rg
+        caller's) and the quality of a blind reading (the checkpoint's) — for a column also that of its segmentation, and columns whose cells are
+        far from square (``blind_columns``' head); several pages in one launch."""
+        from . import pages, regions as rg
         who, n = "restore_page_regions", len(regions)
         image, restored, texts = self._page_front(who, image, n, texts, [char_boxes], "one text (and one list of character boxes, or None) per region", "regions")
-        self._columns_need_text(who, [i for i, r in enumerate(regions) if texts[i] is None and isinstance(r, dict) and "box" in r and r.get("vertical")])
+        blind, page_d, read = [i for i, r in enumerate(regions) if texts[i] is None and isinstance(r, dict) and "box" in r and r.get("vertical")], None, {}
+        if not blind_columns:
+            self._columns_need_text(who, blind)
+        elif blind:
+            H, W = int(image.shape[0]), int(image.shape[1])
+            one_cell = [None] * n                                       # the refusals that need no pixel: every blind column checked as one cell
+            for i in blind:
+                try:
+                    b = pages.round_box(regions[i]["box"], H, W)
+                    one_cell[i] = [b[1], b[3]]
+                except (TypeError, ValueError):
+                    pass                                                # ``normalize_regions`` refuses the box in its own words
+            try:
+                pre = rg.normalize_regions(H, W, regions, restored, texts, [None if char_boxes is None else char_boxes[i] for i in range(n)], scale,
+                                           feather, overlap, cuts=one_cell)
+            except ValueError as e:
+                raise ValueError("%s: %s" % (who, e)) from None
+            page_d, texts, char_boxes, read = self._columns_read_first(who, image, blind, [r.get("box") for r in pre], texts, char_boxes, scale, probe_width)
+            restored = self._restored_again(restored, texts, blind)
         try:
             recs = rg.normalize_regions(int(image.shape[0]), int(image.shape[1]), regions, restored, texts,
                                         [None if char_boxes is None else char_boxes[i] for i in range(n)], scale, feather, overlap)
@@ -844,9 +949,11 @@ class MarconetPipeline:
             else:
                 extra.append(dict(kind="curve", polygon=r["out_polygon"], size=(r["rw"], r["rh"])))
         return self._restore_page_records(who, image, recs, texts, char_boxes, scale, max_glyphs, overlap_glyphs,
-                                          lambda out, joined, out_ws, live, plans: rg.paste_regions(out, joined, out_ws, recs, int(feather)), details, extra, probe_width)
+                                          lambda out, joined, out_ws, live, plans: rg.paste_regions(out, joined, out_ws, recs, int(feather)), details,
+                                          self._column_reading_details(extra, read), probe_width, page_d)
 
-    def _restore_page_records(self, who, image, recs, texts, char_boxes, scale, max_glyphs, overlap_glyphs, paste, details, extra, probe_width=384):
+    def _restore_page_records(self, who, image, recs, texts, char_boxes, scale, max_glyphs, overlap_glyphs, paste, details, extra, probe_width=384,
+                              page_d=None):
         """the one driver of the five ``restore_page*`` entry points, from their checked regions to the page on the host.  ``recs[i]``: region i's
         record as ``regions.normalize_regions`` gives it — ``kind`` "line" or "column" with ``box`` (a column that is restored: ``cuts``, ``widths``),
         "quad" (``quads.check_quads``' record) or "curve" (``curves.check_curves``') —; ``char_boxes`` in PAGE pixels.  Per kind the crop's size and
@@ -856,7 +963,8 @@ class MarconetPipeline:
         the join, then ``paste(out, joined, out_ws, live, plans)``, the caller's paste, and ``_page_finish`` with the caller's ``extra``.
         A region whose text is None is read first (``_read_regions``): the page goes to the device then, once; a line's probes are views of it, the
         quadrilaterals' and curves' probes one crop launch per kind into a buffer of their own; the reading's boxes are in crop coordinates, what
-        ``_plan_lines`` plans.  On such a page the lines' planned windows are views of the page too, in the place of the host crops and their upload."""
+        ``_plan_lines`` plans.  On such a page the lines' planned windows are views of the page too, in the place of the host crops and their upload.
+        ``page_d``: the page on the device, where the caller uploaded it already (to read its columns: ``_columns_read_first``); it is not copied again."""
         from . import columns as cl, curves as cv, lq_device, pages, quads as qd
         n = len(recs)
         cb = [None if char_boxes is None else char_boxes[i] for i in range(n)]
@@ -880,7 +988,7 @@ class MarconetPipeline:
                             cv.char_boxes_in_crop(cb[i], r["segs"], r["cw"], r["ch"])
             except ValueError as e:
                 raise ValueError("%s: region %d: %s" % (who, i, e)) from None
-        page_dev, W = [], int(image.shape[1])
+        page_dev, W = [] if page_d is None else [page_d], int(image.shape[1])     # ``page_d``: the page, where the caller has uploaded it already
 
         def page_on_device():                                           # the one copy of the page, made when it is first needed
             if not page_dev:
