@@ -11,7 +11,7 @@ The rules:
                   c0 + P < w, and the last one is flush right, c0 = w - P.  A probe OWNS the columns up to the middle of its overlap with each
                   neighbour, (c0_{k+1} + c1_k) // 2; the first owns from 0, the last to w.  An interior probe so owns its middle half: every
                   owned character stands at least a quarter probe from a cut.  ``probe_width`` < 512 leaves room for the encoder's 16 slots.
-    read_probe    labels = ``pipeline.collapse_indices`` of the probe's argmax row; the first min(len, 16) get boxes, the rest are dropped and
+    read_probe    labels = ``labels.collapse_indices`` of the probe's argmax row; the first min(len, 16) get boxes, the rest are dropped and
                   reported (``overflow``), as ``restore_images(texts=None)`` truncates.  Edges: c0 + float(loc) * 512 * h / 32 in fp64, x1 the
                   smaller and x2 the larger.  A character is kept iff 2 own_lo <= x1 + x2 < 2 own_hi (a centre on a boundary has one owner).
     merge         The kept characters of a line's probes → (labels, boxes [[x1, 0, x2, h]]).  Total: it never raises.  In order: edges that are
@@ -29,7 +29,8 @@ import math
 import numpy as np
 import torch
 
-from . import lq_device, lq_io
+from . import lq_device, lq_io, ops
+from .labels import collapse_indices
 from .lq_io import LQ_H, LQ_W, StripTooWide
 
 SLOTS = 16                    # TextViT returns 16 (left, right) pairs
@@ -78,7 +79,6 @@ def plan_probes(h, w, probe_width=384):
 def read_probe(indices64, locs32, probe, h):
     """one probe's prediction — its row of argmax indices and its row of fp32 (left, right) pairs — → (labels, boxes [(x1, x2)], overflow): the
     characters the probe owns, in the encoder's order, in the line's source columns"""
-    from .pipeline import collapse_indices
     c0, _, own_lo, own_hi = (int(v) for v in probe)
     row = [int(v) for v in indices64]
     lab = collapse_indices(row)
@@ -144,7 +144,6 @@ def decode(sizes, probes, rows, locs):
 def encode(pipe, lq):
     """the encoder on a batch of probes → (argmax indices, list of ΣP rows of 64 ints; the (left, right) pairs, fp32 numpy [ΣP, 32]): one forward,
     ``clear_labels_batch``'s argmax, ONE device→host copy of both (an index < 6736 is exact in fp32)"""
-    from . import ops
     logits, locs_lr, _ = pipe.encoder(lq)
     B, T, C = logits.shape
     with ops.on_device(logits):

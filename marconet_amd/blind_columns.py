@@ -35,7 +35,7 @@ import math
 import numpy as np
 import torch
 
-from . import blind, columns, lq_device, lq_io, pages
+from . import _lib, blind, columns, lq_device, lq_io, pages
 from .long_lines import Window
 
 LQ_H = columns.LQ_H
@@ -55,6 +55,17 @@ def row_ink(page, box):
     x1, y1, x2, y2 = (int(v) for v in box)
     y = luma(page[y1:y2, x1:x2])
     return np.abs(y[:, 1:] - y[:, :-1]).sum(axis=1).astype(np.int32)
+
+
+def ink_table(boxes, page_w):
+    """the integer ``boxes`` as views of a page ``page_w`` px wide → (numpy record array of ``mnet_ink_box`` — byte offset, pitch, h, w and the box's
+    first row in the one profile buffer —, those first rows, the buffer's length): ``mnet_row_ink_u8``'s table, the profiles one behind the other"""
+    tab, starts, total = np.zeros((len(boxes),), dtype=np.dtype(_lib.RowInkBox)), [], 0
+    for k, (x1, y1, x2, y2) in enumerate(boxes):
+        tab[k] = ((y1 * page_w + x1) * 3, 3 * page_w, y2 - y1, x2 - x1, total)
+        starts.append(total)
+        total += y2 - y1
+    return tab, starts, total
 
 
 def cell_count(box):
