@@ -57,6 +57,19 @@ extern "C" {
  *                channel (E8M0 of s * 2^-11), i.e. a packed weight tensor is cout*kh*kw*cin*4 + cout bytes (mnet_pack_weights).  The row's exponent is
  *                clamp(floor(log2 max|hi|) + 120, 11, 254) — no floor at 105: a row with 0 < max|hi| < 2^-15 is outside the format (256 W of a layer never is) —
  *                and 11 (trailing byte 0, signed-zero lo bytes as above) for a row whose every hi is +-0, e.g. a padding row. */
+/* Operand range of the convolutions (mnet_conv2d_nhwc; tests/conv_range.py is this paragraph as code, tests/test_conv_range_gpu.py holds every kernel build
+ * to it).  The kernels read every block the storages can hold — fp16-subnormal blocks at the floor E = 105, E = 0 blocks, blocks of one pixel or of neighbouring
+ * pixels under scales far apart, weight rows 2^10 apart — and each OUTPUT, judged alone, lies within
+ *     gamma * A_o + f_o + r_o      of the fp64 sum of the products its kernel family forms (finite operands, |y| inside the half range), where
+ *   A_o    = the sum of the absolute values of those products: an error is measured against the output's own window, not against the largest output of the map;
+ *   gamma  = the error of an fp32 accumulation, at most K * 2^-24 (K = kh * kw * cin); the kernels keep the tighter measured figure pinned in tests/conv_range.py;
+ *   f_o    = 0 for MNET_F32, MNET_F16 and the MNET_F16M LDS-DMA / strip / one-wave kernels: their operands enter the MFMAs as stored, fp16 subnormals included
+ *            (x_hi8 = e4m3(hi / s_x) is formed from subnormal halves as from normal ones).  MNET_F16X2 on every kernel, and MNET_F16M on the register-staged
+ *            kernel (lo bytes decoded to halves), multiply f16 lo halves, which stop at the f16-subnormal step: f_o = 2^-24 * (sum |W_hi| over the taps that hold
+ *            a live activation + sum |X_hi| over the taps that hold a live weight) / 256 — one step per element; the same holds for X' of an input transform;
+ *   r_o    = one step of the output storage at that value: the f16 ulp; the f16 ulp of the lo half (MNET_F16X2); one e4m3 step of the scaled residual under
+ *            the output block's scale (MNET_F16M); 0 for MNET_F32 and for MNET_CONV_ALGO_FLAG_F32_OUT.
+ * An output whose window holds no non-zero product is exactly 0. */
 typedef enum { MNET_F32 = 0, MNET_F16 = 1, MNET_F16X2 = 2, MNET_F16M = 3 } mnet_dtype;
 
 typedef enum {
