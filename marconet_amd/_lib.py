@@ -60,6 +60,14 @@ class RowInkBox(ctypes.Structure):
     _fields_ = [("offset", c_i64), ("pitch", c_int), ("h", c_int), ("w", c_int), ("out", c_int)]
 
 
+class BoxInkBox(ctypes.Structure):
+    """mirror of ``mnet_ink_box2`` (include/marconet_hip_boxink.h): one box of mnet_box_ink_u8's device table"""
+    _fields_ = [("offset", c_i64), ("pitch", c_int), ("h", c_int), ("w", c_int), ("out_rows", c_int), ("out_cols", c_int), ("reserved", c_int)]
+
+
+BOXINK_TILE_W, BOXINK_TILE_H = 256, 32      # the tile of one workgroup of mnet_box_ink_u8 (csrc/boxink_kernels.hip)
+
+
 class PanelStrip(ctypes.Structure):
     """mirror of ``mnet_panel_strip`` (include/marconet_hip.h): one strip of mnet_panel_u8's device table"""
     _fields_ = [("show_w", c_int), ("preview_index", c_int), ("glyph0", c_int), ("n_glyphs", c_int), ("step", c_double)]
@@ -268,6 +276,11 @@ ROWINK_SYMBOLS = {
     "mnet_row_ink_u8": (c_int, [c_void_p, c_i64, c_void_p, c_int, c_int, c_void_p, c_i64, c_void_p]),
 }
 
+# ... and the one include/marconet_hip_boxink.h declares (both ink profiles of boxes of a page above a noise floor: where a page's lines are)
+BOXINK_SYMBOLS = {
+    "mnet_box_ink_u8": (c_int, [c_void_p, c_i64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_i64, c_void_p]),
+}
+
 _lib = None
 
 
@@ -285,7 +298,7 @@ def load():
             "marconet_amd: %s not found — build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or marconet_amd/csrc/build.sh (there is no CPU/eager fallback)" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(UPFOLD_SYMBOLS.items()) + list(UPFOLD_F32Z_SYMBOLS.items()) + list(QUAD_SYMBOLS.items()) + list(COLUMN_SYMBOLS.items()) + list(CURVE_SYMBOLS.items()) + list(ORDERED_SYMBOLS.items()) + list(MIXED_SYMBOLS.items()) + list(WINDOW_SYMBOLS.items()) + list(ROWINK_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(UPFOLD_SYMBOLS.items()) + list(UPFOLD_F32Z_SYMBOLS.items()) + list(QUAD_SYMBOLS.items()) + list(COLUMN_SYMBOLS.items()) + list(CURVE_SYMBOLS.items()) + list(ORDERED_SYMBOLS.items()) + list(MIXED_SYMBOLS.items()) + list(WINDOW_SYMBOLS.items()) + list(ROWINK_SYMBOLS.items()) + list(BOXINK_SYMBOLS.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is absent
         fn.restype = res
         fn.argtypes = args

@@ -26,8 +26,9 @@ across kinds of region — a quadrilateral by ``quads.warp_paste_host``, a curve
 handles regular layouts without perspective only; rotated and quadrilateral regions are ``quads``' (``MarconetPipeline.restore_page_quads``).  Out of
 scope: vertical columns that are rotated or in perspective (upright columns of stacked characters are ``columns``': ``MarconetPipeline.
 restore_page_columns``; a page that mixes boxes, columns, quadrilaterals and curves, overlapping or not, is ``regions``':
-``MarconetPipeline.restore_page_regions``), any blend of overlapping regions other than painter's order, detection and recognition (the
-caller's), and several pages in one launch.
+``MarconetPipeline.restore_page_regions``), any blend of overlapping regions other than painter's order, detection beyond horizontal lines in columns on plain paper
+(``layout``: ``MarconetPipeline.find_lines`` / ``restore_page_auto`` find those from ink profiles; every other box is the caller's) and
+recognition beyond the encoder's own reading (``blind``), and several pages in one launch.
 """
 import math
 

@@ -8,7 +8,8 @@ import contextlib
 import numpy as np
 import torch
 
-from . import blind, blind_columns as bc, columns as cl, curves as cv, long_lines, lq_device, lq_io, ops, pages, panel_device, quads as qd, regions as rg
+from . import _lib, blind, blind_columns as bc, columns as cl, curves as cv, layout, long_lines, lq_device, lq_io, ops, pages, panel_device, quads as qd, \
+    regions as rg
 from .labels import clear_labels_batch, collapse_indices, locs_from_left_right, prepared_rows, script_skips
 
 
@@ -310,6 +311,36 @@ class RestoreFrontEnd:
         rows, locs = blind.encode(self, lq_device.prepare_packed(packed, shapes, offsets).lq)
         return bc.decode(plans, rows, locs, scale)
 
+    @torch.no_grad()
+    def find_lines(self, image, text_h=None, floor=layout.DEFAULT_FLOOR, pad=None, min_h=None, min_w=None, max_h=None):
+        """The text lines of a page nobody has boxed: ``image`` uint8 RGB [H, W, 3] → dict(boxes: integer [x1, y1, x2, y2] in page pixels, in
+        reading order; tight; skipped; passes) — ``layout.find_lines_host``'s result, ``==`` (``layout``'s head states the rules — a recursive XY-cut
+        over ink profiles above the noise floor ``floor`` — the defaults, and what is out of scope: anything but horizontal lines in columns
+        on plain paper, and any claim of detection quality).  ONE upload of the page; per pass of the cut ONE ``mnet_box_ink_u8`` launch over all
+        current boxes as views of the page and one device→host copy of their profiles; the cuts, a few thousand integers, run on the host through
+        the same ``layout.xy_cut``.  With the networks on no HIP device the host definition runs.  TypeError for a page that is not uint8
+        RGB HxWx3, ValueError for ``layout.line_params``' refusals, before anything is copied."""
+        image = pages._page_array(image)
+        with _named("find_lines"):
+            params = layout.line_params(image.shape[0], text_h, floor, pad, min_h, min_w, max_h)
+        if self._device().type != "cuda":
+            return layout.find_lines_host(image, **params)
+        return self._find_lines(page_to_device(image, self._device()), params)
+
+    def _find_lines(self, page_d, params):
+        """``find_lines`` of a page that is on the device: ``page_d`` uint8 RGB [H, W, 3], ``params``: ``layout.line_params``' dict"""
+        H, W, flat = int(page_d.shape[0]), int(page_d.shape[1]), page_d.reshape(-1)
+
+        def profiles(boxes, axis):
+            tab, starts, total = layout.ink_table(boxes, W, np.dtype(_lib.BoxInkBox))
+            tab_d, ink = ops.table_to_device(tab, page_d.device), torch.zeros((total,), dtype=torch.int32, device=page_d.device)
+            with ops.on_device(page_d):
+                for k0, k1 in layout.launch_chunks(tab["h"], tab["w"], _lib.BOXINK_TILE_H, _lib.BOXINK_TILE_W):      # one launch, but for a page of specks
+                    ops.box_ink_u8(flat, tab_d[k0:k1], int(tab["h"][k0:k1].max()), int(tab["w"][k0:k1].max()), params["floor"], dst=ink)
+            ink = ink.cpu().numpy()                                     # the pass' one device→host copy
+            return [ink[s[axis]:s[axis] + (b[3] - b[1] if axis == layout.AXIS_Y else b[2] - b[0])] for s, b in zip(starts, boxes)]
+        return layout.lines_from_profiles(profiles, H, W, params)
+
     def _blind_columns_first(self, who, image, blind_at, blind_columns, precheck, texts, char_boxes, restored, scale, probe_width):
         """the pre-pass of the two entry points that take columns: ``blind_at``: the positions of the columns whose text is None.  A column's
         cells are cut from its text, one per character, so without ``blind_columns`` such a column is refused.  With it: ``precheck()`` — the
@@ -505,11 +536,17 @@ class RestoreFrontEnd:
         and ``overflow`` (a probe held more than the encoder's 16 characters); None where it kept the background.
         Not covered: a blend of overlapping regions other than painter's order; vertical columns that are rotated or in perspective (upright columns of stacked characters:
         ``restore_page_columns``; rotated, quadrilateral and perspective regions: ``restore_page_quads``; curved text: ``restore_page_curves``; a page
-        that mixes these kinds, overlapping or not: ``restore_page_regions``); detection (the caller's: the boxes) and the QUALITY of a blind reading
+        that mixes these kinds, overlapping or not: ``restore_page_regions``); detection beyond ``restore_page_auto``'s — horizontal lines in columns
+        on plain paper, found by ``find_lines``' XY-cut; every other box is the caller's — and the QUALITY of a blind reading
         (the checkpoint's: a text the caller's recogniser supplies is used as given); repairing a probe that overflowed; reading a column
         (``restore_page_columns(blind_columns=True)`` does); several pages in one launch."""
         who = "restore_page"
         image, restored, texts = self._page_front(who, image, len(boxes), texts, [char_boxes], "one text (and one list of character boxes, or None) per box", "boxes")
+        return self._restore_page_boxes(who, image, boxes, texts, char_boxes, restored, scale, feather, max_glyphs, overlap_glyphs, details, overlap, probe_width)
+
+    def _restore_page_boxes(self, who, image, boxes, texts, char_boxes, restored, scale, feather, max_glyphs, overlap_glyphs, details, overlap, probe_width,
+                            page_d=None):
+        """``restore_page`` behind its intake, for ``restore_page_auto`` too: ``page_d``: the page on the device where the caller has uploaded it"""
         H, W = int(image.shape[0]), int(image.shape[1])
         boxes = [pages.round_box(b, H, W) for b in boxes]
         with _named(who):
@@ -520,7 +557,47 @@ class RestoreFrontEnd:
                 return pages.paste_ordered(out, joined, pages.as_cell(pages.build_table(rects, out_ws, feather, int(joined.shape[1]))))
             return pages.paste_rects(out, joined, rects, out_ws, feather)
         return self._restore_page_records(who, image, [dict(kind="line", box=b, rect=r) for b, r in zip(boxes, rects)], texts, char_boxes, scale, max_glyphs,
-                                          overlap_glyphs, paste, details, probe_width)
+                                          overlap_glyphs, paste, details, probe_width, page_d)
+
+    @torch.no_grad()
+    def restore_page_auto(self, image, scale=4, feather=8, details=False, probe_width=384, max_glyphs=16, overlap_glyphs=2, text_h=None,
+                          floor=layout.DEFAULT_FLOOR, pad=None, min_h=None, min_w=None, max_h=None):
+        """``restore_page`` for a bare page: nobody supplies the boxes, nobody the texts.  ``find_lines`` finds the page's text lines (``text_h``,
+        ``floor``, ``pad``, ``min_h``, ``min_w``, ``max_h`` are its arguments; ``layout``'s head states the rules), and the page — already on
+        the device, it is uploaded ONCE for the finding, the reading and the restoration — then goes exactly the way of ``restore_page(image, boxes,
+        texts=None, ...)``: a call that finds its lines returns, byte for byte, the call given ``details``' ``boxes``.  A found box whose rectangle
+        ``pages.region_rects`` would refuse (``scale`` · h · 16 < 128: under 8 output rows) is dropped and reported in ``skipped``, beside the boxes
+        ``find_lines`` skipped.  A page with no line returns the enlarged page.
+        ``details=True`` → ``(page, found)``: ``find_lines``' dict — ``boxes`` and ``tight`` without the dropped ones, ``skipped`` with them,
+        ``passes`` — plus ``regions`` (``restore_page``'s per-region dicts, None where a line kept the background) and ``text`` (per line what the
+        encoder read, None for an empty reading).
+        ValueError for ``scale``, ``feather`` and ``layout.line_params``' refusals, and where the networks are on no HIP device (the reading is the
+        encoder's), before anything is copied.
+        Not covered: what ``find_lines`` does not cover — vertical columns, rotated, skewed or curved text, tables with vertical rules, textured
+        backgrounds —, the QUALITY of the finding on real scans (its defaults are design choices, not measurements) and of the blind reading
+        (the checkpoint's); several pages in one launch."""
+        who = "restore_page_auto"
+        image = np.asarray(image)
+        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3 or image.size == 0:
+            raise TypeError("%s: uint8 RGB HxWx3 page expected" % who)
+        with _named(who):
+            pages.check_request(scale, feather, 0, 0, "box", "boxes")
+            params = layout.line_params(image.shape[0], text_h, floor, pad, min_h, min_w, max_h)
+        if self._device().type != "cuda":
+            raise ValueError("%s: the lines it finds are read by the encoder, which needs the networks on a HIP device (they are on %s) — find_lines alone "
+                             "runs its host definition there" % (who, self._device()))
+        page_d = page_to_device(image, self._device())
+        found = self._find_lines(page_d, params)
+        keep = [int(scale) * (b[3] - b[1]) * pages.MIN_RECT_H_DIV >= pages.ROW_H for b in found["boxes"]]
+        found["skipped"] = found["skipped"] + [dict(box=b, reason="%d rows high at scale %d: under the %d output rows a line can be reduced to"
+                                                    % (b[3] - b[1], int(scale), pages.ROW_H // pages.MIN_RECT_H_DIV)) for b, k in zip(found["boxes"], keep) if not k]
+        found["boxes"], found["tight"] = [b for b, k in zip(found["boxes"], keep) if k], [b for b, k in zip(found["tight"], keep) if k]
+        n = len(found["boxes"])
+        out = self._restore_page_boxes(who, image, found["boxes"], [None] * n, None, [True] * n, scale, feather, max_glyphs, overlap_glyphs, details, "refuse",
+                                       probe_width, page_d)
+        if not details:
+            return out
+        return out[0], dict(found, regions=out[1], text=[None if r is None else r["text"] for r in out[1]])
 
     @torch.no_grad()
     def restore_page_quads(self, image, quads, texts=None, char_boxes=None, scale=4, feather=8, max_glyphs=16, overlap_glyphs=2, details=False, probe_width=384):
@@ -686,7 +763,7 @@ class RestoreFrontEnd:
         is still raised before anything is copied, and the page is uploaded once.  ``details`` adds ``text``, ``char_boxes``, ``first_cuts`` and
         ``overflow`` for such a column; one whose reading is empty keeps the background.
         Not covered: a blend of overlapping regions other than painter's order; vertical columns that are rotated or curved; detection (the
-        caller's) and the quality of a blind reading (the checkpoint's) — for a column also that of its segmentation, and columns whose cells are
+        caller's; ``find_lines`` finds horizontal lines on plain paper only) and the quality of a blind reading (the checkpoint's) — for a column also that of its segmentation, and columns whose cells are
         far from square (``blind_columns``' head); several pages in one launch."""
         who, n = "restore_page_regions", len(regions)
         image, restored, texts = self._page_front(who, image, n, texts, [char_boxes], "one text (and one list of character boxes, or None) per region", "regions")
