@@ -68,6 +68,15 @@ class BoxInkBox(ctypes.Structure):
 BOXINK_TILE_W, BOXINK_TILE_H = 256, 32      # the tile of one workgroup of mnet_box_ink_u8 (csrc/boxink_kernels.hip)
 
 
+class SkewInkBox(ctypes.Structure):
+    """mirror of ``mnet_skew_box`` (include/marconet_hip_skewink.h): one record of mnet_skew_ink_u8's device table"""
+    _fields_ = [("c1", c_int), ("r1", c_int), ("c2", c_int), ("r2", c_int), ("slope", c_int), ("out_rows", c_int), ("out_cols", c_int),
+                ("px1", c_int), ("py1", c_int), ("px2", c_int), ("py2", c_int), ("reserved", c_int)]
+
+
+SKEWINK_TILE_W, SKEWINK_TILE_H = 256, 32    # the tile of one workgroup of mnet_skew_ink_u8 (csrc/skewink_kernels.hip)
+
+
 class PanelStrip(ctypes.Structure):
     """mirror of ``mnet_panel_strip`` (include/marconet_hip.h): one strip of mnet_panel_u8's device table"""
     _fields_ = [("show_w", c_int), ("preview_index", c_int), ("glyph0", c_int), ("n_glyphs", c_int), ("step", c_double)]
@@ -281,6 +290,11 @@ BOXINK_SYMBOLS = {
     "mnet_box_ink_u8": (c_int, [c_void_p, c_i64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_i64, c_void_p]),
 }
 
+# ... and the one include/marconet_hip_skewink.h declares (both ink profiles of boxes of a sheared frame of a page: a skewed page's slope and lines)
+SKEWINK_SYMBOLS = {
+    "mnet_skew_ink_u8": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_i64, c_void_p]),
+}
+
 _lib = None
 
 
@@ -298,7 +312,7 @@ def load():
             "marconet_amd: %s not found — build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or marconet_amd/csrc/build.sh (there is no CPU/eager fallback)" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(UPFOLD_SYMBOLS.items()) + list(UPFOLD_F32Z_SYMBOLS.items()) + list(QUAD_SYMBOLS.items()) + list(COLUMN_SYMBOLS.items()) + list(CURVE_SYMBOLS.items()) + list(ORDERED_SYMBOLS.items()) + list(MIXED_SYMBOLS.items()) + list(WINDOW_SYMBOLS.items()) + list(ROWINK_SYMBOLS.items()) + list(BOXINK_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(UPFOLD_SYMBOLS.items()) + list(UPFOLD_F32Z_SYMBOLS.items()) + list(QUAD_SYMBOLS.items()) + list(COLUMN_SYMBOLS.items()) + list(CURVE_SYMBOLS.items()) + list(ORDERED_SYMBOLS.items()) + list(MIXED_SYMBOLS.items()) + list(WINDOW_SYMBOLS.items()) + list(ROWINK_SYMBOLS.items()) + list(BOXINK_SYMBOLS.items()) + list(SKEWINK_SYMBOLS.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is absent
         fn.restype = res
         fn.argtypes = args

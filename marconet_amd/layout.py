@@ -31,7 +31,8 @@ The rules:
                       every side of the others grows by min(pad, allowance).
 
 Limits, stated and not solved here: the defaults are design choices, not measurements, and no claim of detection QUALITY is made.  Out of scope:
-vertical columns, rotated, skewed or curved text, tables with vertical rules (every row has ink), text on textured backgrounds, real scans."""
+vertical columns, rotated or curved text, tables with vertical rules (every row has ink), text on textured backgrounds, real scans.  A page skewed
+as a whole by up to about 7 degrees is ``skew``'s: the same cut in the coordinates of a sheared frame (``MarconetPipeline.find_lines_skewed``)."""
 import numpy as np
 
 from . import pages
@@ -165,9 +166,11 @@ def line_params(page_h, text_h=None, floor=DEFAULT_FLOOR, pad=None, min_h=None, 
     return p
 
 
-def lines_from_profiles(profiles, page_h, page_w, params):
-    """``find_lines_host`` from ``xy_cut`` on: what the host and the device paths share.  ``params``: ``line_params``' dict"""
-    cut_boxes, allows, passes = xy_cut(profiles, page_h, page_w, params["text_h"])
+def lines_from_profiles(profiles, page_h, page_w, params, frame=None):
+    """``find_lines_host`` from ``xy_cut`` on: what the host and the device paths share.  ``params``: ``line_params``' dict.  ``frame``: the box the
+    cut starts from instead of the page — ``skew``'s frame box, whose coordinates are the frame's; a box then grows by min(pad, allowance − 1),
+    one pixel less a side (``skew``'s head says why)"""
+    cut_boxes, allows, passes = xy_cut(profiles, page_h, page_w, params["text_h"], start=None if frame is None else ([list(frame)], [[0, 0, 0, 0]]))
     boxes, tight, skipped = [], [], []
     for b, al in zip(cut_boxes, allows):
         h, w = b[3] - b[1], b[2] - b[0]
@@ -176,7 +179,7 @@ def lines_from_profiles(profiles, page_h, page_w, params):
         if h > params["max_h"]:
             skipped.append(dict(box=list(b), reason="%d rows high, over max_h = %d: a figure, or lines the cut could not part" % (h, params["max_h"])))
             continue
-        g = [min(params["pad"], a) for a in al]
+        g = [min(params["pad"], a if frame is None else max(a - 1, 0)) for a in al]
         tight.append(list(b))
         boxes.append([b[0] - g[0], b[1] - g[1], b[2] + g[2], b[3] + g[3]])
     return dict(boxes=boxes, tight=tight, skipped=skipped, passes=passes)

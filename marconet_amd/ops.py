@@ -18,7 +18,7 @@ from .packing import MX_DTYPE, SPLIT_DTYPE, is_split, mx_weight_rows, new_tensor
 
 __all__ = ["conv2d", "linear", "nchw_to_nhwc", "nhwc_to_nchw", "upsample2x", "affine_act", "groupnorm_affine",
            "adain_crop_concat", "adain_crop_concat_gn", "glyph_scatter_affine", "layernorm", "token_mix", "attention", "pixelnorm",
-           "embed_gather", "demod", "argmax_rows", "convert", "fused_bias_act", "sr_postprocess", "lq_from_u8", "lq_windows_u8", "row_ink_u8", "box_ink_u8", "panel_u8", "paste_u8", "quad_crop_u8", "quad_paste_u8", "curve_crop_u8", "curve_paste_u8", "paste_ordered_u8", "conv3x3_rgb", "torgb", "stats",
+           "embed_gather", "demod", "argmax_rows", "convert", "fused_bias_act", "sr_postprocess", "lq_from_u8", "lq_windows_u8", "row_ink_u8", "box_ink_u8", "skew_ink_u8", "panel_u8", "paste_u8", "quad_crop_u8", "quad_paste_u8", "curve_crop_u8", "curve_paste_u8", "paste_ordered_u8", "conv3x3_rgb", "torgb", "stats",
            "pack_weights", "pack_wsq", "gather_rows", "style_rows", "nonfinite_flag", "compare_stats", "gn_partial_buffer", "can_emit_gn_partial", "groupnorm_affine_from_partial",
            "polyphase_plan", "upconv3x3_polyphase", "polyphase_ring_fix", "groupnorm_affine_from_partial_ring", "upfold_plan", "upfold3x3",
            "ACT_NONE", "ACT_RELU", "ACT_LRELU", "ACT_LRELU_SQRT2", "ACT_TANH", "ACT_GELU", "ACT_SIGMOID"]
@@ -930,6 +930,28 @@ def box_ink_u8(src, boxes, max_h, max_w, floor, dst_len=None, dst=None):
     _check_table("box_ink_u8", "box table", boxes, _lib.BoxInkBox, 8)
     _lib.check(lib.mnet_box_ink_u8(_p(src), int(src.numel()), _p(boxes), int(boxes.shape[0]), int(max_h), int(max_w), int(floor), _p(dst), int(dst.numel()),
                                    _stream()), "mnet_box_ink_u8")
+    return dst
+
+
+def skew_ink_u8(page, boxes, max_h, max_w, floor, dst_len=None, dst=None):
+    """mnet_skew_ink_u8 (``skew.frame_ink``, record by record, with ==): ``page`` uint8 [H,W,3] RGB; ``boxes`` uint8 [n, sizeof(mnet_skew_box)]
+    (``_lib.SkewInkBox``: frame box, slope, the first index of the row profile and of the column profile in ``dst`` — −1: not wanted —, the page
+    rectangle to scan) — on the device; ``max_h`` / ``max_w``: the largest scan rectangle of the table; ``floor``: 0..255.  The kernel ADDS the
+    profiles: ``dst_len`` → a new int32 [dst_len] of zeros holds them; ``dst`` (instead) → an int32 [len] tensor of the caller's they are added to.
+    −1 in the wanted, in-range profiles of a record that cannot be followed (include/marconet_hip_skewink.h).  One launch for all records; the
+    profiles' tensor is returned."""
+    lib = _lib.load()
+    if (dst is None) == (dst_len is None):
+        raise TypeError("skew_ink_u8: either dst_len (the profiles are returned in a new tensor of zeros) or dst (they are added to it)")
+    if dst is None:
+        dst = torch.zeros((int(dst_len),), dtype=torch.int32, device=page.device)
+    _need_cuda(page, boxes, dst)
+    _need_u8("skew_ink_u8", "page", page, 3)
+    if dst.dtype != torch.int32 or dst.dim() != 1:
+        raise TypeError("skew_ink_u8: int32 [len] dst expected")
+    _check_table("skew_ink_u8", "record table", boxes, _lib.SkewInkBox, 8)
+    _lib.check(lib.mnet_skew_ink_u8(_p(page), int(page.shape[0]), int(page.shape[1]), _p(boxes), int(boxes.shape[0]), int(max_h), int(max_w), int(floor),
+                                    _p(dst), int(dst.numel()), _stream()), "mnet_skew_ink_u8")
     return dst
 
 

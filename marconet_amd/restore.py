@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib, blind, blind_columns as bc, columns as cl, curves as cv, layout, long_lines, lq_device, lq_io, ops, pages, panel_device, quads as qd, \
-    regions as rg
+    regions as rg, skew
 from .labels import clear_labels_batch, collapse_indices, locs_from_left_right, prepared_rows, script_skips
 
 
@@ -316,7 +316,7 @@ class RestoreFrontEnd:
         """The text lines of a page nobody has boxed: ``image`` uint8 RGB [H, W, 3] → dict(boxes: integer [x1, y1, x2, y2] in page pixels, in
         reading order; tight; skipped; passes) — ``layout.find_lines_host``'s result, ``==`` (``layout``'s head states the rules — a recursive XY-cut
         over ink profiles above the noise floor ``floor`` — the defaults, and what is out of scope: anything but horizontal lines in columns
-        on plain paper, and any claim of detection quality).  ONE upload of the page; per pass of the cut ONE ``mnet_box_ink_u8`` launch over all
+        on plain paper, and any claim of detection quality; a page skewed as a whole is ``find_lines_skewed``'s).  ONE upload of the page; per pass of the cut ONE ``mnet_box_ink_u8`` launch over all
         current boxes as views of the page and one device→host copy of their profiles; the cuts, a few thousand integers, run on the host through
         the same ``layout.xy_cut``.  With the networks on no HIP device the host definition runs.  TypeError for a page that is not uint8
         RGB HxWx3, ValueError for ``layout.line_params``' refusals, before anything is copied."""
@@ -340,6 +340,67 @@ class RestoreFrontEnd:
             ink = ink.cpu().numpy()                                     # the pass' one device→host copy
             return [ink[s[axis]:s[axis] + (b[3] - b[1] if axis == layout.AXIS_Y else b[2] - b[0])] for s, b in zip(starts, boxes)]
         return layout.lines_from_profiles(profiles, H, W, params)
+
+    @torch.no_grad()
+    def estimate_skew(self, image, floor=layout.DEFAULT_FLOOR, max_slope=6144):
+        """The skew of a scanned page: ``image`` uint8 RGB [H, W, 3] → dict(slope: Q16, the text runs along (1, slope / 65536); scores: [(m, S(m))]
+        of every candidate) — ``skew.estimate_host``'s result, ``==`` (``skew``'s head states the rule, Postl's criterion on the row profiles of a
+        sheared frame, its two stages and its defaults, which are design choices).  ONE upload of the page; per stage ONE ``mnet_skew_ink_u8`` launch
+        whose table is the page's frame box at every candidate slope, rows only, and one device→host copy of the profiles; the scores are Python
+        integers, computed on the host.  With the networks on no HIP device the host definition runs.  TypeError for a page that is not uint8
+        RGB HxWx3, ValueError for ``skew.estimate_params``' refusals, before anything is copied.  Not covered: skew beyond ``max_slope`` (at most
+        8192, about 7 degrees), 90 / 180 degree orientation, perspective, per-block skew, and the estimate's quality on real scans."""
+        image = pages._page_array(image)
+        with _named("estimate_skew"):
+            params = skew.estimate_params(floor, max_slope)
+        if self._device().type != "cuda":
+            return skew.estimate_host(image, **params)
+        return self._estimate_skew(page_to_device(image, self._device()), params)
+
+    def _skew_profiles(self, page_d, records, floor):
+        """``skew.frame_ink`` of every record of ``records`` — (frame box, slope, columns wanted) each — of the page on the device → per record (rows,
+        cols or None): ONE ``mnet_skew_ink_u8`` launch and one device→host copy"""
+        H, W = int(page_d.shape[0]), int(page_d.shape[1])
+        tab, starts, total = skew.ink_table(records, H, W, np.dtype(_lib.SkewInkBox))
+        hs, ws = np.maximum(tab["py2"] - tab["py1"], 1), np.maximum(tab["px2"] - tab["px1"], 1)
+        tab_d, ink = ops.table_to_device(tab, page_d.device), torch.zeros((total,), dtype=torch.int32, device=page_d.device)
+        with ops.on_device(page_d):
+            for k0, k1 in layout.launch_chunks(hs, ws, _lib.SKEWINK_TILE_H, _lib.SKEWINK_TILE_W):         # one launch, but for a page of specks
+                ops.skew_ink_u8(page_d, tab_d[k0:k1], int(hs[k0:k1].max()), int(ws[k0:k1].max()), floor, dst=ink)
+        ink = ink.cpu().numpy()                                         # the one device→host copy
+        return [(ink[sr:sr + b[3] - b[1]], None if sc is None else ink[sc:sc + b[2] - b[0]]) for (sr, sc), (b, _, _) in zip(starts, records)]
+
+    def _estimate_skew(self, page_d, params):
+        """``estimate_skew`` of a page that is on the device; ``params``: ``skew.estimate_params``' dict"""
+        H, W = int(page_d.shape[0]), int(page_d.shape[1])
+        return skew.estimate(lambda slopes: [rows for rows, _ in self._skew_profiles(page_d, [(skew.frame_box(H, W, m), m, False) for m in slopes],
+                                                                                       params["floor"])], params)
+
+    @torch.no_grad()
+    def find_lines_skewed(self, image, slope=None, text_h=None, floor=layout.DEFAULT_FLOOR, pad=None, min_h=None, min_w=None, max_h=None):
+        """``find_lines`` for a page that was scanned skewed: ``image`` uint8 RGB [H, W, 3] → dict(slope, frame_boxes, tight, quads, skipped, passes,
+        scores) — ``skew.find_lines_host``'s result, ``==`` (``skew``'s head states the rules: ``layout``'s cut in the coordinates of a frame sheared
+        by ``slope``, Q16; ``quads[i]``: the four page corners of line i, what ``restore_page_quads`` takes).  ``slope=None``: ``estimate_skew`` runs
+        first, on the same upload.  Per pass of the cut ONE ``mnet_skew_ink_u8`` launch over all current frame boxes and one device→host copy of
+        their profiles; the cuts run on the host through the same ``layout.xy_cut``.  With the networks on no HIP device the host definition runs.
+        TypeError for a page that is not uint8 RGB HxWx3, ValueError for ``layout.line_params``' refusals and a ``slope`` that is no integer within
+        ±8192, before anything is copied.  Not covered: what ``estimate_skew`` and ``find_lines`` do not cover."""
+        image = pages._page_array(image)
+        with _named("find_lines_skewed"):
+            params = layout.line_params(image.shape[0], text_h, floor, pad, min_h, min_w, max_h)
+            slope = None if slope is None else skew.check_slope(slope)
+        if self._device().type != "cuda":
+            return skew.find_lines_host(image, slope, **params)
+        return self._find_lines_skewed(page_to_device(image, self._device()), params, slope)
+
+    def _find_lines_skewed(self, page_d, params, slope):
+        """``find_lines_skewed`` of a page that is on the device; ``slope``: checked, or None"""
+        est = dict(slope=slope, scores=[]) if slope is not None else self._estimate_skew(page_d, skew.estimate_params(params["floor"]))
+        m = est["slope"]
+
+        def profiles(boxes, axis):
+            return [p[axis] for p in self._skew_profiles(page_d, [(b, m, axis == layout.AXIS_X) for b in boxes], params["floor"])]
+        return skew.lines_from_frame_profiles(profiles, int(page_d.shape[0]), int(page_d.shape[1]), m, params, est["scores"])
 
     def _blind_columns_first(self, who, image, blind_at, blind_columns, precheck, texts, char_boxes, restored, scale, probe_width):
         """the pre-pass of the two entry points that take columns: ``blind_at``: the positions of the columns whose text is None.  A column's
@@ -561,7 +622,7 @@ class RestoreFrontEnd:
 
     @torch.no_grad()
     def restore_page_auto(self, image, scale=4, feather=8, details=False, probe_width=384, max_glyphs=16, overlap_glyphs=2, text_h=None,
-                          floor=layout.DEFAULT_FLOOR, pad=None, min_h=None, min_w=None, max_h=None):
+                          floor=layout.DEFAULT_FLOOR, pad=None, min_h=None, min_w=None, max_h=None, deskew=False):
         """``restore_page`` for a bare page: nobody supplies the boxes, nobody the texts.  ``find_lines`` finds the page's text lines (``text_h``,
         ``floor``, ``pad``, ``min_h``, ``min_w``, ``max_h`` are its arguments; ``layout``'s head states the rules), and the page — already on
         the device, it is uploaded ONCE for the finding, the reading and the restoration — then goes exactly the way of ``restore_page(image, boxes,
@@ -573,9 +634,15 @@ class RestoreFrontEnd:
         encoder read, None for an empty reading).
         ValueError for ``scale``, ``feather`` and ``layout.line_params``' refusals, and where the networks are on no HIP device (the reading is the
         encoder's), before anything is copied.
-        Not covered: what ``find_lines`` does not cover — vertical columns, rotated, skewed or curved text, tables with vertical rules, textured
-        backgrounds —, the QUALITY of the finding on real scans (its defaults are design choices, not measurements) and of the blind reading
-        (the checkpoint's); several pages in one launch."""
+        ``deskew=True``: for a page scanned skewed.  The page — still uploaded ONCE, for the estimate, the finding, the reading and the restoration
+        — goes through ``estimate_skew`` and ``find_lines_skewed`` (``skew``'s head states the rules), and the found quadrilaterals go exactly the way
+        of ``restore_page_quads(image, quads, texts=None, ...)``: the result is, byte for byte, that call given ``details``' ``quads``.  A quadrilateral
+        ``quads.check_quads`` would refuse for its size goes to ``skipped``.  ``details`` is then ``find_lines_skewed``'s dict — ``slope``,
+        ``frame_boxes``, ``tight``, ``quads``, ``skipped``, ``passes``, ``scores`` — plus ``regions`` (``restore_page_quads``' dicts) and ``text``.
+        Not covered: what ``find_lines`` does not cover — vertical columns, rotated or curved text, tables with vertical rules, textured
+        backgrounds; without ``deskew`` any skew, with it skew beyond about 5 degrees (the range ``estimate_skew`` searches), 90 / 180 degree
+        orientation, perspective and per-block skew (ONE slope is found per page) —, the QUALITY of the finding and of the skew estimate on real
+        scans (their defaults are design choices, not measurements) and of the blind reading (the checkpoint's); several pages in one launch."""
         who = "restore_page_auto"
         image = np.asarray(image)
         if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3 or image.size == 0:
@@ -587,6 +654,8 @@ class RestoreFrontEnd:
             raise ValueError("%s: the lines it finds are read by the encoder, which needs the networks on a HIP device (they are on %s) — find_lines alone "
                              "runs its host definition there" % (who, self._device()))
         page_d = page_to_device(image, self._device())
+        if deskew:
+            return self._restore_page_deskewed(who, image, page_d, params, scale, feather, details, probe_width, max_glyphs, overlap_glyphs)
         found = self._find_lines(page_d, params)
         keep = [int(scale) * (b[3] - b[1]) * pages.MIN_RECT_H_DIV >= pages.ROW_H for b in found["boxes"]]
         found["skipped"] = found["skipped"] + [dict(box=b, reason="%d rows high at scale %d: under the %d output rows a line can be reduced to"
@@ -595,6 +664,25 @@ class RestoreFrontEnd:
         n = len(found["boxes"])
         out = self._restore_page_boxes(who, image, found["boxes"], [None] * n, None, [True] * n, scale, feather, max_glyphs, overlap_glyphs, details, "refuse",
                                        probe_width, page_d)
+        if not details:
+            return out
+        return out[0], dict(found, regions=out[1], text=[None if r is None else r["text"] for r in out[1]])
+
+    def _restore_page_deskewed(self, who, image, page_d, params, scale, feather, details, probe_width, max_glyphs, overlap_glyphs):
+        """``restore_page_auto(deskew=True)`` behind its intake: ``page_d``: the page on the device, ``params``: ``layout.line_params``' dict"""
+        found, s = self._find_lines_skewed(page_d, params, None), int(scale)
+        rows = [s * qd.crop_size(q)[1] for q in found["quads"]]
+        keep = [h * pages.MIN_RECT_H_DIV >= pages.ROW_H for h in rows]
+        found["skipped"] = found["skipped"] + [dict(box=b, reason="%d rows high at scale %d: under the %d output rows a line can be reduced to"
+                                                    % (h, s, pages.ROW_H // pages.MIN_RECT_H_DIV)) for b, h, k in zip(found["frame_boxes"], rows, keep) if not k]
+        for key in ("frame_boxes", "tight", "quads"):
+            found[key] = [v for v, k in zip(found[key], keep) if k]
+        n = len(found["quads"])
+        with _named(who):
+            regions = qd.check_quads(int(image.shape[0]), int(image.shape[1]), found["quads"], [True] * n, scale, feather)
+        out = self._restore_page_records(who, image, [dict(r, kind="quad") for r in regions], [None] * n, None, scale, max_glyphs, overlap_glyphs,
+                                         lambda out, joined, out_ws, live, plans: qd.paste_quads(out, joined, out_ws, regions, int(feather)), details,
+                                         probe_width, page_d)
         if not details:
             return out
         return out[0], dict(found, regions=out[1], text=[None if r is None else r["text"] for r in out[1]])
