@@ -65,7 +65,7 @@ class BoxInkBox(ctypes.Structure):
     _fields_ = [("offset", c_i64), ("pitch", c_int), ("h", c_int), ("w", c_int), ("out_rows", c_int), ("out_cols", c_int), ("reserved", c_int)]
 
 
-BOXINK_TILE_W, BOXINK_TILE_H = 256, 32      # the tile of one workgroup of mnet_box_ink_u8 (csrc/boxink_kernels.hip)
+BOXINK_TILE_W, BOXINK_TILE_H = 256, 32      # the tile of one workgroup of mnet_box_ink_u8 (csrc/ink_kernels.hip)
 
 
 class SkewInkBox(ctypes.Structure):
@@ -74,7 +74,7 @@ class SkewInkBox(ctypes.Structure):
                 ("px1", c_int), ("py1", c_int), ("px2", c_int), ("py2", c_int), ("reserved", c_int)]
 
 
-SKEWINK_TILE_W, SKEWINK_TILE_H = 256, 32    # the tile of one workgroup of mnet_skew_ink_u8 (csrc/skewink_kernels.hip)
+SKEWINK_TILE_W, SKEWINK_TILE_H = 256, 32    # the tile of one workgroup of mnet_skew_ink_u8 (csrc/ink_kernels.hip)
 
 
 class PanelStrip(ctypes.Structure):
@@ -312,7 +312,7 @@ def load():
             "marconet_amd: %s not found — build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or marconet_amd/csrc/build.sh (there is no CPU/eager fallback)" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(UPFOLD_SYMBOLS.items()) + list(UPFOLD_F32Z_SYMBOLS.items()) + list(QUAD_SYMBOLS.items()) + list(COLUMN_SYMBOLS.items()) + list(CURVE_SYMBOLS.items()) + list(ORDERED_SYMBOLS.items()) + list(MIXED_SYMBOLS.items()) + list(WINDOW_SYMBOLS.items()) + list(ROWINK_SYMBOLS.items()) + list(BOXINK_SYMBOLS.items()) + list(SKEWINK_SYMBOLS.items()):
+    for name, (res, args) in [f for k, table in sorted(globals().items()) if k.endswith("SYMBOLS") for f in table.items()]:      # every header's table
         fn = getattr(lib, name)          # AttributeError if the symbol is absent
         fn.restype = res
         fn.argtypes = args

@@ -6,9 +6,8 @@ probes of whole cells, as ``blind`` reads a wide line.  This module is the pure-
 
 The rules:
 
-    row_ink           ink[r] = Σ_x |Y(x + 1, r) − Y(x, r)| over the box's row r, Y = (77 R + 150 G + 29 B + 128) >> 8: the row's total horizontal
-                      variation of integer luma.  It does not depend on polarity and is 0 on a flat row.  An exact integer: ``mnet_row_ink_u8``
-                      returns it with ==.
+    row_ink           ``ink.row_ink``: per row of the box its total horizontal variation of integer luma (``ink``'s head defines it).  An exact
+                      integer: ``mnet_row_ink_u8`` returns it with ==.
     first_cuts        n = max(1, (2 ch + cw) // (2 cw)) cells, about square.  The cuts are found top to bottom, each relative to the one before
                       (a global grid drifts): with ``left`` cells to cut from the ``rem`` rows below c_{j−1}, the nominal cut is t = c_{j−1} +
                       rem / left rounded half up, and c_j is the row r within R = rem // (4 left) of t — and such that every cell above and below
@@ -35,37 +34,12 @@ import math
 import numpy as np
 import torch
 
-from . import _lib, blind, columns, lq_device, lq_io, pages
+from . import blind, columns, lq_device, lq_io, pages
+from .ink import luma, row_ink, row_table as ink_table                                # noqa: F401  (the profile: ``ink``'s)
 from .long_lines import Window
 
 LQ_H = columns.LQ_H
 ROW_H = columns.ROW_H
-
-
-# --------------------------------------------------------------------------------------------------------------------------- the profile
-def luma(rgb):
-    """Y = (77 R + 150 G + 29 B + 128) >> 8 of a uint8 RGB array [..., 3] → int32 [...]"""
-    rgb = np.asarray(rgb).astype(np.int32)
-    return (77 * rgb[..., 0] + 150 * rgb[..., 1] + 29 * rgb[..., 2] + 128) >> 8
-
-
-def row_ink(page, box):
-    """the ink profile of ``page[y1:y2, x1:x2]``, int32 [y2 − y1] (the module's head states it): the numpy definition of ``mnet_row_ink_u8``"""
-    page = pages._page_array(page)
-    x1, y1, x2, y2 = (int(v) for v in box)
-    y = luma(page[y1:y2, x1:x2])
-    return np.abs(y[:, 1:] - y[:, :-1]).sum(axis=1).astype(np.int32)
-
-
-def ink_table(boxes, page_w):
-    """the integer ``boxes`` as views of a page ``page_w`` px wide → (numpy record array of ``mnet_ink_box`` — byte offset, pitch, h, w and the box's
-    first row in the one profile buffer —, those first rows, the buffer's length): ``mnet_row_ink_u8``'s table, the profiles one behind the other"""
-    tab, starts, total = np.zeros((len(boxes),), dtype=np.dtype(_lib.RowInkBox)), [], 0
-    for k, (x1, y1, x2, y2) in enumerate(boxes):
-        tab[k] = ((y1 * page_w + x1) * 3, 3 * page_w, y2 - y1, x2 - x1, total)
-        starts.append(total)
-        total += y2 - y1
-    return tab, starts, total
 
 
 def cell_count(box):

@@ -11,7 +11,7 @@ if [ "${MNET_CLEAN:-0}" != "0" ]; then rm -f "$OUT"/*.o "$OUT"/*.o.tmp "$OUT"/*.
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 PIDS=()
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function"
-SRCS="api conv_igemm conv_igemm_dma conv_dma_swp_gn conv_dma_w4 conv_dma_w4_shuf conv_dma_w4_f32 conv_strip_dma conv_skinny aux_kernels upfold_kernels vit_kernels pack_kernels lq_kernels panel_kernels compare_kernels stitch_kernels page_kernels quad_kernels column_kernels curve_kernels mixed_kernels window_kernels rowink_kernels boxink_kernels skewink_kernels"
+SRCS="api conv_igemm conv_igemm_dma conv_dma_swp_gn conv_dma_w4 conv_dma_w4_shuf conv_dma_w4_f32 conv_strip_dma conv_skinny aux_kernels upfold_kernels vit_kernels pack_kernels lq_kernels panel_kernels compare_kernels stitch_kernels page_kernels quad_kernels column_kernels curve_kernels mixed_kernels window_kernels ink_kernels"
 # per-source extra flags (conv_dma_swp_gn: see the note at its top; lq_kernels / panel_kernels / page_kernels: their taps must not be contracted, see lq_taps.h / panel_taps.h)
 # (curve_kernels: quad_kernels' reason, see curve_map.h; mixed_kernels: page_kernels', quad_kernels' and curve_kernels' reasons together)
 # (window_kernels: lq_kernels' reason, it is that kernel on a source with a row pitch)
@@ -19,7 +19,7 @@ SRCS="api conv_igemm conv_igemm_dma conv_dma_swp_gn conv_dma_w4 conv_dma_w4_shuf
 extra() { case "$1" in conv_dma_swp_gn) echo "-mllvm -greedy-reverse-local-assignment=1" ;; lq_kernels) echo "-ffp-contract=off" ;; panel_kernels) echo "-ffp-contract=off" ;; page_kernels) echo "-ffp-contract=off" ;; quad_kernels) echo "-ffp-contract=off" ;; column_kernels) echo "-ffp-contract=off" ;; curve_kernels) echo "-ffp-contract=off" ;; mixed_kernels) echo "-ffp-contract=off" ;; window_kernels) echo "-ffp-contract=off" ;; *) echo "" ;; esac; }
 HDRS="$HERE/common.h $HERE/conv_args.h $HERE/conv_dma_common.h $HERE/../../include/marconet_hip.h"
 CCVER="$("$HIPCC" --version 2>/dev/null | head -3 | tr '\n' ' ')"
-stamp() { { cat "$HERE/$1.hip" $HDRS; [ "$1" = conv_dma_swp_gn ] && cat "$HERE/conv_igemm_dma.hip"; [ "$1" = conv_dma_w4_shuf ] && cat "$HERE/conv_dma_w4.hip"; [ "$1" = conv_dma_w4_f32 ] && cat "$HERE/conv_dma_w4.hip"; [ "$1" = lq_kernels ] && cat "$HERE/lq_taps.h" "$HERE/page_tile.h"; [ "$1" = panel_kernels ] && cat "$HERE/panel_taps.h"; [ "$1" = stitch_kernels ] && cat "$HERE/stitch_blend.h"; [ "$1" = upfold_kernels ] && cat "$HERE/../../include/marconet_hip_upfold.h" "$HERE/../../include/marconet_hip_upfold_f32.h"; [ "$1" = page_kernels ] && cat "$HERE/lq_taps.h" "$HERE/page_blend.h" "$HERE/page_tile.h" "$HERE/../../include/marconet_hip_columns.h" "$HERE/cell_paste.h"; [ "$1" = quad_kernels ] && cat "$HERE/quad_map.h" "$HERE/lq_taps.h" "$HERE/page_blend.h" "$HERE/page_tile.h" "$HERE/../../include/marconet_hip_quad.h" "$HERE/warp_paste.h" "$HERE/curve_map.h" "$HERE/../../include/marconet_hip_curve.h"; [ "$1" = column_kernels ] && cat "$HERE/lq_taps.h" "$HERE/page_tile.h" "$HERE/../../include/marconet_hip_columns.h"; [ "$1" = curve_kernels ] && cat "$HERE/curve_map.h" "$HERE/quad_map.h" "$HERE/lq_taps.h" "$HERE/page_blend.h" "$HERE/page_tile.h" "$HERE/../../include/marconet_hip_curve.h" "$HERE/warp_paste.h" "$HERE/../../include/marconet_hip_quad.h"; [ "$1" = mixed_kernels ] && cat "$HERE/cell_paste.h" "$HERE/warp_paste.h" "$HERE/curve_map.h" "$HERE/quad_map.h" "$HERE/lq_taps.h" "$HERE/page_blend.h" "$HERE/page_tile.h" "$HERE/../../include/marconet_hip_columns.h" "$HERE/../../include/marconet_hip_ordered.h" "$HERE/../../include/marconet_hip_quad.h" "$HERE/../../include/marconet_hip_curve.h" "$HERE/../../include/marconet_hip_mixed.h"; [ "$1" = window_kernels ] && cat "$HERE/lq_taps.h" "$HERE/page_tile.h" "$HERE/../../include/marconet_hip_windows.h"; [ "$1" = rowink_kernels ] && cat "$HERE/../../include/marconet_hip_rowink.h"; [ "$1" = boxink_kernels ] && cat "$HERE/../../include/marconet_hip_boxink.h"; [ "$1" = skewink_kernels ] && cat "$HERE/../../include/marconet_hip_skewink.h"; echo "$FLAGS $(extra "$1") ${EXTRA_HIPCC_FLAGS:-} | $CCVER"; } | sha256sum | cut -d' ' -f1; }
+stamp() { { cat "$HERE/$1.hip" $HDRS; [ "$1" = conv_dma_swp_gn ] && cat "$HERE/conv_igemm_dma.hip"; [ "$1" = conv_dma_w4_shuf ] && cat "$HERE/conv_dma_w4.hip"; [ "$1" = conv_dma_w4_f32 ] && cat "$HERE/conv_dma_w4.hip"; [ "$1" = lq_kernels ] && cat "$HERE/lq_taps.h" "$HERE/page_tile.h"; [ "$1" = panel_kernels ] && cat "$HERE/panel_taps.h"; [ "$1" = stitch_kernels ] && cat "$HERE/stitch_blend.h"; [ "$1" = upfold_kernels ] && cat "$HERE/../../include/marconet_hip_upfold.h" "$HERE/../../include/marconet_hip_upfold_f32.h"; [ "$1" = page_kernels ] && cat "$HERE/lq_taps.h" "$HERE/page_blend.h" "$HERE/page_tile.h" "$HERE/../../include/marconet_hip_columns.h" "$HERE/cell_paste.h"; [ "$1" = quad_kernels ] && cat "$HERE/quad_map.h" "$HERE/lq_taps.h" "$HERE/page_blend.h" "$HERE/page_tile.h" "$HERE/../../include/marconet_hip_quad.h" "$HERE/warp_paste.h" "$HERE/curve_map.h" "$HERE/../../include/marconet_hip_curve.h"; [ "$1" = column_kernels ] && cat "$HERE/lq_taps.h" "$HERE/page_tile.h" "$HERE/../../include/marconet_hip_columns.h"; [ "$1" = curve_kernels ] && cat "$HERE/curve_map.h" "$HERE/quad_map.h" "$HERE/lq_taps.h" "$HERE/page_blend.h" "$HERE/page_tile.h" "$HERE/../../include/marconet_hip_curve.h" "$HERE/warp_paste.h" "$HERE/../../include/marconet_hip_quad.h"; [ "$1" = mixed_kernels ] && cat "$HERE/cell_paste.h" "$HERE/warp_paste.h" "$HERE/curve_map.h" "$HERE/quad_map.h" "$HERE/lq_taps.h" "$HERE/page_blend.h" "$HERE/page_tile.h" "$HERE/../../include/marconet_hip_columns.h" "$HERE/../../include/marconet_hip_ordered.h" "$HERE/../../include/marconet_hip_quad.h" "$HERE/../../include/marconet_hip_curve.h" "$HERE/../../include/marconet_hip_mixed.h"; [ "$1" = window_kernels ] && cat "$HERE/lq_taps.h" "$HERE/page_tile.h" "$HERE/../../include/marconet_hip_windows.h"; [ "$1" = ink_kernels ] && cat "$HERE/ink.h" "$HERE/../../include/marconet_hip_rowink.h" "$HERE/../../include/marconet_hip_boxink.h" "$HERE/../../include/marconet_hip_skewink.h"; echo "$FLAGS $(extra "$1") ${EXTRA_HIPCC_FLAGS:-} | $CCVER"; } | sha256sum | cut -d' ' -f1; }
 for f in $SRCS; do
   want="$(stamp "$f")"
   if [ ! -f "$OUT/$f.o" ] || [ ! -f "$OUT/$f.o.sha" ] || [ "$(cat "$OUT/$f.o.sha")" != "$want" ]; then

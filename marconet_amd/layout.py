@@ -6,11 +6,9 @@ returns exactly this (tests/test_layout_gpu.py compares the two with ``==``).  I
 
 The rules:
 
-    box_ink           Y = (77 R + 150 G + 29 B + 128) >> 8; d(x, r) = |Y(x + 1, r) − Y(x, r)|; e(x, r) = d if d >= floor, else 0 (the noise floor:
-                      paper grain and JPEG ripple are differences of a few levels, a stroke's edge is tens; 0 and 1 are the same floor).
-                      rows[r] = Σ_{x = 0 .. w − 2} e(x, r);  cols[x] = Σ_{r = 0 .. h − 1} e(x, r) for x <= w − 2, cols[w − 1] = 0: a pair is filed
-                      under its LEFT pixel.  Exact integers: ``mnet_box_ink_u8`` returns both with ==.  With floor <= 1 ``rows`` is
-                      ``blind_columns.row_ink``.
+    box_ink           ``ink.box_ink`` (``ink``'s head defines Y, d and e): rows[r] = Σ_{x = 0 .. w − 2} e(x, r);  cols[x] = Σ_{r = 0 .. h − 1} e(x, r)
+                      for x <= w − 2, cols[w − 1] = 0: a pair is filed under its LEFT pixel.  Exact integers: ``mnet_box_ink_u8`` returns both
+                      with ==.  With floor <= 1 ``rows`` is ``blind_columns.row_ink``.
     cut               an entry of a profile is blank iff it is 0.  The blank ends are trimmed; the rest is split at every inner blank run of
                       ``min_gap`` entries or more → half-open segments [a, b); an all-blank profile → [].  For the Y axis the profile is ``rows``.
                       For the X axis it is the PIXEL profile c[x] = cols[x − 1] + cols[x] (cols[−1] = 0): an edge keeps both of its pixels, so a
@@ -36,56 +34,13 @@ as a whole by up to about 7 degrees is ``skew``'s: the same cut in the coordinat
 import numpy as np
 
 from . import pages
-from .blind_columns import luma
+from .ink import MAX_LAUNCH_BOXES, MAX_LAUNCH_TILES, box_ink, box_table as ink_table, launch_chunks, luma             # noqa: F401  (the profiles: ``ink``'s)
 
 DEFAULT_FLOOR = 24
 AXIS_Y, AXIS_X = 0, 1
 
 
 # --------------------------------------------------------------------------------------------------------------------------- the profiles
-def box_ink(page, box, floor):
-    """both ink profiles of ``page[y1:y2, x1:x2]`` above ``floor`` → (rows int32 [y2 − y1], cols int32 [x2 − x1]) (the module's head states them):
-    the numpy definition of ``mnet_box_ink_u8``"""
-    page = pages._page_array(page)
-    x1, y1, x2, y2 = (int(v) for v in box)
-    y = luma(page[y1:y2, x1:x2])
-    d = np.abs(y[:, 1:] - y[:, :-1])
-    e = np.where(d >= int(floor), d, 0)
-    cols = np.zeros((y.shape[1],), np.int32)
-    cols[:max(y.shape[1] - 1, 0)] = e.sum(axis=0)
-    return e.sum(axis=1).astype(np.int32), cols
-
-
-def ink_table(boxes, page_w, dtype):
-    """the integer ``boxes`` as views of a page ``page_w`` px wide → (numpy record array of ``mnet_ink_box2`` (``dtype``: ``np.dtype(_lib.BoxInkBox)``) —
-    byte offset, pitch, h, w and the first index of each profile in the one buffer —, per box (first index of rows, of cols), the buffer's
-    length): ``mnet_box_ink_u8``'s table, a box's two profiles one behind the other"""
-    tab, starts, total = np.zeros((len(boxes),), dtype=dtype), [], 0
-    for k, (x1, y1, x2, y2) in enumerate(boxes):
-        h, w = y2 - y1, x2 - x1
-        tab[k] = ((y1 * page_w + x1) * 3, 3 * page_w, h, w, total, total + h, 0)
-        starts.append((total, total + h))
-        total += h + w
-    return tab, starts, total
-
-
-MAX_LAUNCH_BOXES, MAX_LAUNCH_TILES = 65535, 2 ** 24 - 1          # mnet_box_ink_u8's grid: its third axis, and 2^32 − 1 threads in workgroups of 256
-
-
-def launch_chunks(hs, ws, tile_h, tile_w):
-    """the boxes of a table (their heights ``hs`` and widths ``ws``) → [(k0, k1)]: consecutive runs that one ``mnet_box_ink_u8`` launch takes — at
-    most 65535 boxes and (tiles of the run's largest box) x (boxes) <= 2^24 − 1 workgroups.  One run, unless a page breaks into many thousands of
-    boxes beside a large one."""
-    out, k0, mh, mw = [], 0, 0, 0
-    for k, (h, w) in enumerate(zip(hs, ws)):
-        nh, nw = max(mh, -(-int(h) // tile_h)), max(mw, -(-int(w) // tile_w))
-        if k > k0 and (k - k0 + 1 > MAX_LAUNCH_BOXES or nh * nw * (k - k0 + 1) > MAX_LAUNCH_TILES):
-            out.append((k0, k))
-            k0, nh, nw = k, -(-int(h) // tile_h), -(-int(w) // tile_w)
-        mh, mw = nh, nw
-    return out + [(k0, len(hs))] if len(hs) else out
-
-
 def pixel_profile(cols):
     """c[x] = cols[x − 1] + cols[x]: the X axis' profile per PIXEL of a profile per pair"""
     cols = np.asarray(cols).astype(np.int64)

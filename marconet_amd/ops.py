@@ -893,21 +893,36 @@ def column_gather_u8(page, cells, max_dw, dst_h, dst):
     return dst
 
 
+def _ink_dst(who, src, dst_len, dst):
+    """the rule of the two ink kernels that ADD: either ``dst_len`` → a new int32 tensor of zeros beside ``src``, or the caller's ``dst``"""
+    if (dst is None) == (dst_len is None):
+        raise TypeError("%s: either dst_len (the profiles are returned in a new tensor of zeros) or dst (they are added to it)" % who)
+    return torch.zeros((int(dst_len),), dtype=torch.int32, device=src.device) if dst is None else dst
+
+
+def _ink(fn, who, src, as_page, what, table, struct, dims, dst):
+    """the one wrapper of the three ink-profile kernels, ``fn`` the entry point of ``who``: ``src`` — the page as uint8 [bytes], or ``as_page``: [H,W,3]
+    and its size — is read through ``table``, ``who``'s ``what``, into the int32 ``dst``, which is returned; ``dims``: the call's integers between them"""
+    _need_cuda(src, table, dst)
+    if as_page:
+        _need_u8(who, "page", src, 3)
+    elif src.dtype != torch.uint8 or src.dim() != 1:
+        raise TypeError("%s: uint8 [bytes] pixels expected" % who)
+    if dst.dtype != torch.int32 or dst.dim() != 1:
+        raise TypeError("%s: int32 [len] dst expected" % who)
+    _check_table(who, what, table, struct, 8)
+    status = fn(_p(src), *(src.shape[:2] if as_page else (src.numel(),)), _p(table), table.shape[0], *dims, _p(dst), dst.numel(), _stream())
+    if status:
+        _lib.check(status, "mnet_" + who)
+    return dst
+
+
 def row_ink_u8(src, boxes, max_h, dst):
     """mnet_row_ink_u8 (``blind_columns.row_ink``, box by box, with ==): ``src`` uint8 [bytes], the page; ``boxes`` uint8 [n, sizeof(mnet_ink_box)]
     (``_lib.RowInkBox``: first byte, row pitch, size, first index in ``dst``); ``dst`` int32 [len] — all on the device; ``max_h``: the largest box
     height of the table.  ``dst[out + r]`` = row r's total horizontal variation of integer luma, written for the rows of the boxes only (−1 for a
     box that does not lie inside ``src``; nothing for rows that do not lie inside ``dst``); ``dst`` is returned.  One launch for all boxes."""
-    lib = _lib.load()
-    _need_cuda(src, boxes, dst)
-    if src.dtype != torch.uint8 or src.dim() != 1:
-        raise TypeError("row_ink_u8: uint8 [bytes] pixels expected")
-    if dst.dtype != torch.int32 or dst.dim() != 1:
-        raise TypeError("row_ink_u8: int32 [len] dst expected")
-    _check_table("row_ink_u8", "box table", boxes, _lib.RowInkBox, 8)
-    _lib.check(lib.mnet_row_ink_u8(_p(src), int(src.numel()), _p(boxes), int(boxes.shape[0]), int(max_h), _p(dst), int(dst.numel()), _stream()),
-               "mnet_row_ink_u8")
-    return dst
+    return _ink(_lib.load().mnet_row_ink_u8, "row_ink_u8", src, False, "box table", boxes, _lib.RowInkBox, (int(max_h),), dst)
 
 
 def box_ink_u8(src, boxes, max_h, max_w, floor, dst_len=None, dst=None):
@@ -917,20 +932,8 @@ def box_ink_u8(src, boxes, max_h, max_w, floor, dst_len=None, dst=None):
     the profiles: ``dst_len`` → a new int32 [dst_len] of zeros holds them; ``dst`` (instead) → an int32 [len] tensor of the caller's they are added
     to.  −1 in both profiles of a box that does not lie inside ``src``, nothing for a box whose ranges do not lie inside ``dst``.  One launch for
     all boxes; the profiles' tensor is returned."""
-    lib = _lib.load()
-    if (dst is None) == (dst_len is None):
-        raise TypeError("box_ink_u8: either dst_len (the profiles are returned in a new tensor of zeros) or dst (they are added to it)")
-    if dst is None:
-        dst = torch.zeros((int(dst_len),), dtype=torch.int32, device=src.device)
-    _need_cuda(src, boxes, dst)
-    if src.dtype != torch.uint8 or src.dim() != 1:
-        raise TypeError("box_ink_u8: uint8 [bytes] pixels expected")
-    if dst.dtype != torch.int32 or dst.dim() != 1:
-        raise TypeError("box_ink_u8: int32 [len] dst expected")
-    _check_table("box_ink_u8", "box table", boxes, _lib.BoxInkBox, 8)
-    _lib.check(lib.mnet_box_ink_u8(_p(src), int(src.numel()), _p(boxes), int(boxes.shape[0]), int(max_h), int(max_w), int(floor), _p(dst), int(dst.numel()),
-                                   _stream()), "mnet_box_ink_u8")
-    return dst
+    return _ink(_lib.load().mnet_box_ink_u8, "box_ink_u8", src, False, "box table", boxes, _lib.BoxInkBox, (int(max_h), int(max_w), int(floor)),
+                _ink_dst("box_ink_u8", src, dst_len, dst))
 
 
 def skew_ink_u8(page, boxes, max_h, max_w, floor, dst_len=None, dst=None):
@@ -940,19 +943,8 @@ def skew_ink_u8(page, boxes, max_h, max_w, floor, dst_len=None, dst=None):
     profiles: ``dst_len`` → a new int32 [dst_len] of zeros holds them; ``dst`` (instead) → an int32 [len] tensor of the caller's they are added to.
     −1 in the wanted, in-range profiles of a record that cannot be followed (include/marconet_hip_skewink.h).  One launch for all records; the
     profiles' tensor is returned."""
-    lib = _lib.load()
-    if (dst is None) == (dst_len is None):
-        raise TypeError("skew_ink_u8: either dst_len (the profiles are returned in a new tensor of zeros) or dst (they are added to it)")
-    if dst is None:
-        dst = torch.zeros((int(dst_len),), dtype=torch.int32, device=page.device)
-    _need_cuda(page, boxes, dst)
-    _need_u8("skew_ink_u8", "page", page, 3)
-    if dst.dtype != torch.int32 or dst.dim() != 1:
-        raise TypeError("skew_ink_u8: int32 [len] dst expected")
-    _check_table("skew_ink_u8", "record table", boxes, _lib.SkewInkBox, 8)
-    _lib.check(lib.mnet_skew_ink_u8(_p(page), int(page.shape[0]), int(page.shape[1]), _p(boxes), int(boxes.shape[0]), int(max_h), int(max_w), int(floor),
-                                    _p(dst), int(dst.numel()), _stream()), "mnet_skew_ink_u8")
-    return dst
+    return _ink(_lib.load().mnet_skew_ink_u8, "skew_ink_u8", page, True, "record table", boxes, _lib.SkewInkBox, (int(max_h), int(max_w), int(floor)),
+                _ink_dst("skew_ink_u8", page, dst_len, dst))
 
 
 def page_tiles(page_h, page_w):

@@ -8,7 +8,7 @@ import contextlib
 import numpy as np
 import torch
 
-from . import _lib, blind, blind_columns as bc, columns as cl, curves as cv, layout, long_lines, lq_device, lq_io, ops, pages, panel_device, quads as qd, \
+from . import blind, blind_columns as bc, columns as cl, curves as cv, ink, layout, long_lines, lq_device, lq_io, ops, pages, panel_device, quads as qd, \
     regions as rg, skew
 from .labels import clear_labels_batch, collapse_indices, locs_from_left_right, prepared_rows, script_skips
 
@@ -301,12 +301,7 @@ class RestoreFrontEnd:
     def _read_columns(self, page_d, boxes, scale, probe_width, regions=None):
         """``read_columns`` of a page that is on the device: ``page_d`` uint8 RGB [H, W, 3], ``boxes``: integer boxes inside it; ``regions[k]``: the
         number a refusal gives column k"""
-        tab, starts, total = bc.ink_table(boxes, int(page_d.shape[1]))
-        ink = torch.empty((total,), dtype=torch.int32, device=page_d.device)
-        with ops.on_device(page_d):
-            ops.row_ink_u8(page_d.reshape(-1), ops.table_to_device(tab, page_d.device), int(tab["h"].max()), ink)
-        ink = ink.cpu().numpy()                                         # the one device→host copy of all profiles
-        plans = bc.plan_columns(boxes, [ink[s:s + b[3] - b[1]] for s, b in zip(starts, boxes)], probe_width, regions)
+        plans = bc.plan_columns(boxes, ink.row_profiles(page_d.reshape(-1), int(page_d.shape[1]), boxes), probe_width, regions)
         packed, shapes, offsets = cl.gather_columns(page_d, [(p["box"], p["first_cuts"], p["widths"], bc.probe_windows(p["probes"])) for p in plans])
         rows, locs = blind.encode(self, lq_device.prepare_packed(packed, shapes, offsets).lq)
         return bc.decode(plans, rows, locs, scale)
@@ -330,16 +325,7 @@ class RestoreFrontEnd:
     def _find_lines(self, page_d, params):
         """``find_lines`` of a page that is on the device: ``page_d`` uint8 RGB [H, W, 3], ``params``: ``layout.line_params``' dict"""
         H, W, flat = int(page_d.shape[0]), int(page_d.shape[1]), page_d.reshape(-1)
-
-        def profiles(boxes, axis):
-            tab, starts, total = layout.ink_table(boxes, W, np.dtype(_lib.BoxInkBox))
-            tab_d, ink = ops.table_to_device(tab, page_d.device), torch.zeros((total,), dtype=torch.int32, device=page_d.device)
-            with ops.on_device(page_d):
-                for k0, k1 in layout.launch_chunks(tab["h"], tab["w"], _lib.BOXINK_TILE_H, _lib.BOXINK_TILE_W):      # one launch, but for a page of specks
-                    ops.box_ink_u8(flat, tab_d[k0:k1], int(tab["h"][k0:k1].max()), int(tab["w"][k0:k1].max()), params["floor"], dst=ink)
-            ink = ink.cpu().numpy()                                     # the pass' one device→host copy
-            return [ink[s[axis]:s[axis] + (b[3] - b[1] if axis == layout.AXIS_Y else b[2] - b[0])] for s, b in zip(starts, boxes)]
-        return layout.lines_from_profiles(profiles, H, W, params)
+        return layout.lines_from_profiles(lambda boxes, axis: ink.box_profiles(flat, W, boxes, params["floor"], axis), H, W, params)
 
     @torch.no_grad()
     def estimate_skew(self, image, floor=layout.DEFAULT_FLOOR, max_slope=6144):
@@ -357,23 +343,10 @@ class RestoreFrontEnd:
             return skew.estimate_host(image, **params)
         return self._estimate_skew(page_to_device(image, self._device()), params)
 
-    def _skew_profiles(self, page_d, records, floor):
-        """``skew.frame_ink`` of every record of ``records`` — (frame box, slope, columns wanted) each — of the page on the device → per record (rows,
-        cols or None): ONE ``mnet_skew_ink_u8`` launch and one device→host copy"""
-        H, W = int(page_d.shape[0]), int(page_d.shape[1])
-        tab, starts, total = skew.ink_table(records, H, W, np.dtype(_lib.SkewInkBox))
-        hs, ws = np.maximum(tab["py2"] - tab["py1"], 1), np.maximum(tab["px2"] - tab["px1"], 1)
-        tab_d, ink = ops.table_to_device(tab, page_d.device), torch.zeros((total,), dtype=torch.int32, device=page_d.device)
-        with ops.on_device(page_d):
-            for k0, k1 in layout.launch_chunks(hs, ws, _lib.SKEWINK_TILE_H, _lib.SKEWINK_TILE_W):         # one launch, but for a page of specks
-                ops.skew_ink_u8(page_d, tab_d[k0:k1], int(hs[k0:k1].max()), int(ws[k0:k1].max()), floor, dst=ink)
-        ink = ink.cpu().numpy()                                         # the one device→host copy
-        return [(ink[sr:sr + b[3] - b[1]], None if sc is None else ink[sc:sc + b[2] - b[0]]) for (sr, sc), (b, _, _) in zip(starts, records)]
-
     def _estimate_skew(self, page_d, params):
         """``estimate_skew`` of a page that is on the device; ``params``: ``skew.estimate_params``' dict"""
         H, W = int(page_d.shape[0]), int(page_d.shape[1])
-        return skew.estimate(lambda slopes: [rows for rows, _ in self._skew_profiles(page_d, [(skew.frame_box(H, W, m), m, False) for m in slopes],
+        return skew.estimate(lambda slopes: [rows for rows, _ in ink.frame_profiles(page_d, [(skew.frame_box(H, W, m), m, False) for m in slopes],
                                                                                        params["floor"])], params)
 
     @torch.no_grad()
@@ -399,7 +372,7 @@ class RestoreFrontEnd:
         m = est["slope"]
 
         def profiles(boxes, axis):
-            return [p[axis] for p in self._skew_profiles(page_d, [(b, m, axis == layout.AXIS_X) for b in boxes], params["floor"])]
+            return [p[axis] for p in ink.frame_profiles(page_d, [(b, m, axis == layout.AXIS_X) for b in boxes], params["floor"])]
         return skew.lines_from_frame_profiles(profiles, int(page_d.shape[0]), int(page_d.shape[1]), m, params, est["scores"])
 
     def _blind_columns_first(self, who, image, blind_at, blind_columns, precheck, texts, char_boxes, restored, scale, probe_width):

@@ -12,8 +12,8 @@ The rules:
                       (x, r) → (x + t r, r − t x), is a rotation by atan t times a uniform scale of sqrt(1 + t²): the blank rows and gutters
                       of a page skewed by atan t are blank again in the frame, an axis-aligned box of the frame is a true rotated rectangle of the
                       page, and disjoint frame boxes give disjoint page quadrilaterals.
-    frame_ink         Y, d and e as ``layout.box_ink`` has them.  For a frame box [c1, r1, c2, r2), whose coordinates may be negative, every pair
-                      (x, r) with 0 <= x <= W − 2, 0 <= r < H, r1 <= r' < r2 and c1 <= c', c' + 1 < c2 adds e(x, r) to rows[r' − r1] and to
+    frame_ink         ``ink.frame_ink``, with Y, d and e as ``ink``'s head defines them.  For a frame box [c1, r1, c2, r2), whose coordinates may be
+                      negative, every pair (x, r) with 0 <= x <= W − 2, 0 <= r < H, r1 <= r' < r2 and c1 <= c', c' + 1 < c2 adds e(x, r) to rows[r' − r1] and to
                       cols[c' − c1]: both pixels of a pair lie in the box and the pair is filed under its LEFT pixel, so cols[−1] = 0 and at
                       m = 0, for a box inside the page, this is ``layout.box_ink`` with ==.  Exact integers: ``mnet_skew_ink_u8`` returns both with ==.
     frame_box         the smallest frame box that holds every page pixel.
@@ -38,17 +38,10 @@ orientation, perspective, per-block skew (ONE slope is found per page), and ever
 import numpy as np
 
 from . import layout, pages
-from .blind_columns import luma
+from .ink import frame_ink, frame_table as ink_table, luma, pair_ink, profiles_of, scan_rect, sh      # noqa: F401  (the profiles: ``ink``'s)
 
 MAX_SLOPE = 8192
 Q = 65536
-
-
-def sh(v, m):
-    """floor((v m + 32768) / 65536) for an integer or an integer array ``v``"""
-    if isinstance(v, np.ndarray):
-        return (v.astype(np.int64) * int(m) + 32768) >> 16
-    return (int(v) * int(m) + 32768) >> 16
 
 
 def check_slope(m):
@@ -59,73 +52,10 @@ def check_slope(m):
 
 
 # --------------------------------------------------------------------------------------------------------------------------- the profiles
-def pair_ink(page, floor):
-    """e(x, r) of the whole page, int32 [H, W − 1] (the module's head; ``layout.box_ink``'s)"""
-    y = luma(pages._page_array(page))
-    d = np.abs(y[:, 1:] - y[:, :-1])
-    return np.where(d >= int(floor), d, 0).astype(np.int32)
-
-
 def frame_box(H, W, m):
     """the smallest frame box [c1, r1, c2, r2) that holds every pixel of an H x W page (sh is monotone: its extremes lie at the page's sides)"""
     sx, sr = (sh(0, m), sh(int(W) - 1, m)), (sh(0, m), sh(int(H) - 1, m))
     return [min(sr), -max(sx), int(W) + max(sr), int(H) - min(sx)]
-
-
-def scan_rect(box, m, H, W):
-    """a page rectangle [px1, py1, px2, py2), inside the page, that holds every pixel (x, r) whose frame coordinates can lie in ``box`` — empty
-    (px2 <= px1 or py2 <= py1, still inside the page) where there is none.  x = c' − sh(r) and r = r' + sh(x): each range is bounded by the
-    other's, three times in turn."""
-    c1, r1, c2, r2 = (int(v) for v in box)
-    H, W = int(H), int(W)
-    x_lo, x_hi, y_lo, y_hi = 0, W - 1, 0, H - 1                                                     # inclusive
-    for _ in range(3):
-        if x_lo > x_hi or y_lo > y_hi:
-            break
-        s = (sh(y_lo, m), sh(y_hi, m))
-        x_lo, x_hi = max(x_lo, c1 - max(s)), min(x_hi, c2 - 1 - min(s))
-        if x_lo > x_hi:
-            break
-        s = (sh(x_lo, m), sh(x_hi, m))
-        y_lo, y_hi = max(y_lo, r1 + min(s)), min(y_hi, r2 - 1 + max(s))
-    if x_lo > x_hi or y_lo > y_hi:
-        return [0, 0, 0, 0]
-    return [x_lo, y_lo, x_hi + 1, y_hi + 1]
-
-
-def profiles_of(e, box, m, rect=None):
-    """``frame_ink`` of the page whose pair ink is ``e`` (``pair_ink``); ``rect``: the page rectangle to scan, ``scan_rect``'s unless given"""
-    c1, r1, c2, r2 = (int(v) for v in box)
-    H, W = int(e.shape[0]), int(e.shape[1]) + 1
-    h, w = max(r2 - r1, 0), max(c2 - c1, 0)
-    px1, py1, px2, py2 = scan_rect(box, m, H, W) if rect is None else (int(v) for v in rect)
-    px2 = min(px2, W - 1)                                                                           # a pair is filed under its left pixel
-    if h == 0 or w == 0 or px2 <= px1 or py2 <= py1:
-        return np.zeros((h,), np.int32), np.zeros((w,), np.int32)
-    x, r, sub = np.arange(px1, px2, dtype=np.int64), np.arange(py1, py2, dtype=np.int64), e[py1:py2, px1:px2]
-    rp, cp = r[:, None] - sh(x, m)[None, :] - r1, x[None, :] + sh(r, m)[:, None] - c1
-    keep = (rp >= 0) & (rp < h) & (cp >= 0) & (cp + 1 < w) & (sub != 0)
-    ink = sub[keep].astype(np.float64)                                                              # sums under 2^25: exact
-    return (np.bincount(rp[keep], weights=ink, minlength=h).astype(np.int32), np.bincount(cp[keep], weights=ink, minlength=w).astype(np.int32))
-
-
-def frame_ink(page, box, m, floor):
-    """both ink profiles of the frame box ``box`` = [c1, r1, c2, r2) of ``page`` at slope ``m`` above ``floor`` → (rows int32 [r2 − r1], cols int32
-    [c2 − c1]) (the module's head states them): the numpy definition of ``mnet_skew_ink_u8``"""
-    return profiles_of(pair_ink(page, floor), box, m)
-
-
-def ink_table(records, H, W, dtype):
-    """``records``: (frame box, slope, columns wanted) each, of an H x W page → (numpy record array of ``mnet_skew_box`` (``dtype``:
-    ``np.dtype(_lib.SkewInkBox)``), per record (first index of rows, of cols — None where not wanted), the buffer's length):
-    ``mnet_skew_ink_u8``'s table with ``scan_rect``'s rectangles, a record's profiles one behind the other"""
-    tab, starts, total = np.zeros((len(records),), dtype=dtype), [], 0
-    for k, (box, m, want_cols) in enumerate(records):
-        h, w = box[3] - box[1], box[2] - box[0]
-        tab[k] = tuple(box) + (m, total, total + h if want_cols else -1) + tuple(scan_rect(box, m, H, W)) + (0,)
-        starts.append((total, total + h if want_cols else None))
-        total += h + (w if want_cols else 0)
-    return tab, starts, total
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ the skew

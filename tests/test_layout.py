@@ -251,17 +251,32 @@ def test_boxink_header_declares_exactly_the_bound_symbol_and_the_descriptor_layo
     assert len(others) >= 10 and not any(set(_lib.BOXINK_SYMBOLS) & set(t) for t in others)
     rowink = re.sub(r"/\*.*?\*/", "", open(os.path.join(INCLUDE, "marconet_hip_rowink.h")).read(), flags=re.S)
     assert set(re.findall(r"\b(mnet_\w+)\s*\(", rowink)) == {"mnet_row_ink_u8"}                     # the old header is as it was
-    src = open(os.path.join(ROOT, "marconet_amd", "csrc", "boxink_kernels.hip")).read()
+    src = open(os.path.join(ROOT, "marconet_amd", "csrc", "ink_kernels.hip")).read()
     assert (_lib.BOXINK_TILE_W, _lib.BOXINK_TILE_H) == tuple(int(re.search(r"BOXINK_TILE_%s = (\d+)" % a, src).group(1)) for a in "WH")
 
 
 def test_build_sh_lists_the_source_and_stamps_its_header():
     sh = open(os.path.join(ROOT, "marconet_amd", "csrc", "build.sh")).read()
     srcs = re.search(r'^SRCS="([^"]*)"', sh, flags=re.M).group(1).split()
-    assert "boxink_kernels" in srcs and "rowink_kernels" in srcs and len(srcs) == len(set(srcs))
-    assert '[ "$1" = boxink_kernels ] && cat "$HERE/../../include/marconet_hip_boxink.h"' in sh
+    assert "ink_kernels" in srcs and len(srcs) == len(set(srcs))
+    assert '[ "$1" = ink_kernels ] && cat "$HERE/ink.h" "$HERE/../../include/marconet_hip_rowink.h" "$HERE/../../include/marconet_hip_boxink.h" ' \
+           '"$HERE/../../include/marconet_hip_skewink.h"' in sh
     from marconet_amd import ops
     assert "box_ink_u8" in ops.__all__ and "row_ink_u8" in ops.__all__
+
+
+def test_load_binds_every_symbol_table_as_it_is_written():
+    lib = _lib.load()
+    tables = {name: getattr(_lib, name) for name in dir(_lib) if name.endswith("SYMBOLS")}
+    declared = set()
+    for header in os.listdir(INCLUDE):                                                              # one table per header, every declared function bound
+        declared |= set(re.findall(r"\b(mnet_\w+)\s*\(", re.sub(r"/\*.*?\*/", "", open(os.path.join(INCLUDE, header)).read(), flags=re.S)))
+    assert len(tables) == len(os.listdir(INCLUDE)) and "SYMBOLS" in tables
+    assert sorted(n for t in tables.values() for n in t) == sorted(declared)                        # no name twice, none missing
+    for table in tables.values():
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name)
+            assert fn.restype is res and list(fn.argtypes) == list(args), name
 
 
 def test_boxink_entry_point_validates_arguments_without_device():

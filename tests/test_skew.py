@@ -274,7 +274,7 @@ def test_skewink_header_declares_exactly_the_bound_symbol_and_the_record_layout(
     assert len(others) >= 11 and not any(set(_lib.SKEWINK_SYMBOLS) & set(t) for t in others)
     boxink = re.sub(r"/\*.*?\*/", "", open(os.path.join(INCLUDE, "marconet_hip_boxink.h")).read(), flags=re.S)
     assert set(re.findall(r"\b(mnet_\w+)\s*\(", boxink)) == {"mnet_box_ink_u8"}                     # the old header is as it was
-    src = open(os.path.join(ROOT, "marconet_amd", "csrc", "skewink_kernels.hip")).read()
+    src = open(os.path.join(ROOT, "marconet_amd", "csrc", "ink_kernels.hip")).read()
     assert (_lib.SKEWINK_TILE_W, _lib.SKEWINK_TILE_H) == tuple(int(re.search(r"SKEWINK_TILE_%s = (\d+)" % a, src).group(1)) for a in "WH")
     assert int(re.search(r"SKEWINK_MAX_SLOPE = (\d+)", src).group(1)) == skew.MAX_SLOPE
     # the table the front end builds: a record per (box, slope), its profiles one behind the other, the scan rectangle inside the page
@@ -286,8 +286,9 @@ def test_skewink_header_declares_exactly_the_bound_symbol_and_the_record_layout(
 def test_build_sh_lists_the_source_and_stamps_its_header():
     sh = open(os.path.join(ROOT, "marconet_amd", "csrc", "build.sh")).read()
     srcs = re.search(r'^SRCS="([^"]*)"', sh, flags=re.M).group(1).split()
-    assert "skewink_kernels" in srcs and "boxink_kernels" in srcs and len(srcs) == len(set(srcs))
-    assert '[ "$1" = skewink_kernels ] && cat "$HERE/../../include/marconet_hip_skewink.h"' in sh
+    assert "ink_kernels" in srcs and len(srcs) == len(set(srcs))
+    assert '[ "$1" = ink_kernels ] && cat "$HERE/ink.h" "$HERE/../../include/marconet_hip_rowink.h" "$HERE/../../include/marconet_hip_boxink.h" ' \
+           '"$HERE/../../include/marconet_hip_skewink.h"' in sh
     from marconet_amd import ops
     assert "skew_ink_u8" in ops.__all__ and "box_ink_u8" in ops.__all__
 

@@ -25,7 +25,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from marconet_amd import _lib, blind_columns as bc, checkpoints, columns, lq_device, ops          # noqa: E402
+from marconet_amd import blind_columns as bc, checkpoints, columns, lq_device, ops                # noqa: E402
 from marconet_amd.pipeline import MarconetPipeline                                               # noqa: E402
 
 PAGE_W, PAGE_H, SCALE = 2480, 3508, 4
@@ -80,10 +80,7 @@ def main():
     page = np.random.default_rng(1).integers(0, 256, (PAGE_H, PAGE_W, 3), dtype=np.uint8)
     boxes = [[20 + 60 * c, 100, 70 + 60 * c, 100 + 30 * 110] for c in range(40)]
     page_d = torch.from_numpy(page).to(dev)
-    tab, total = np.zeros((len(boxes),), dtype=np.dtype(_lib.RowInkBox)), 0
-    for k, (x1, y1, x2, y2) in enumerate(boxes):
-        tab[k] = ((y1 * PAGE_W + x1) * 3, 3 * PAGE_W, y2 - y1, x2 - x1, total)
-        total += y2 - y1
+    tab, _, total = bc.ink_table(boxes, PAGE_W)
     ink_d = torch.empty((total,), dtype=torch.int32, device=dev)
     state = {}
 

@@ -30,7 +30,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from layout_time import PAGE_H, PAGE_W, a4_scene, timed_events, timed_host               # noqa: E402
-from marconet_amd import _lib, checkpoints, layout, ops, skew                                    # noqa: E402
+from marconet_amd import _lib, checkpoints, ink, layout, ops, skew                               # noqa: E402
 from marconet_amd.pipeline import MarconetPipeline                                               # noqa: E402
 from tests.skew_scene import rotate_nearest                                                      # noqa: E402
 
@@ -94,7 +94,7 @@ def main():
 
     def recording(boxes, axis):
         per_pass.append(([list(b) for b in boxes], axis))
-        return [p[axis] for p in pipe._skew_profiles(page_d, [(b, m, axis == layout.AXIS_X) for b in boxes], params["floor"])]
+        return [p[axis] for p in ink.frame_profiles(page_d, [(b, m, axis == layout.AXIS_X) for b in boxes], params["floor"])]
     layout.xy_cut(recording, PAGE_H, PAGE_W, params["text_h"], start=([skew.frame_box(PAGE_H, PAGE_W, m)], [[0, 0, 0, 0]]))
     for boxes, axis in per_pass:
         row = dict(axis="Y" if axis == layout.AXIS_Y else "X")
